@@ -18,11 +18,16 @@ accounts hash-partitioned by owner, 125M uniform transfers per GPU (1B over 8), 
 in their source GPU's HBM for `value` (host memory for `host_path`).  Per-GPU work is fixed as N
 grows: scaling is weak.
 
-The JSON line also carries:
+A plain run sets up, warms up, times --steps steps and prints the JSON line: `value`, `ms_per_step`
+and what the timed steps measure of themselves (their kernels' device-clock spans: `roofline`).
+--dump-outputs DIR writes what the last timed step computed (dump_outputs).  Every other leg runs
+with --full only: `host_path`, the staged leg, the batch latency, write-back, host commits, the
+replica path, the C3 / C4 lines, and
+
   roofline      the dominant kernel's algorithmic bytes per launch / its average launch time
                 (device clock, inside the timed steps) against 8 TB/s; `traffic` (HBM bytes per
                 launch) comes from the PMC_FILE (rocprofv3 PMC passes), with rocprof's mean launch
-                time of the same kernel beside it.
+                time of the same kernel beside it; --full adds `access_mix`.
   cpu_baseline  the C oracle (reference semantics restated, single thread) timed on this host on
                 a bounded prefix of the same workload.
   parity        the same prefix committed on the GPU from a fresh state through the timed path (and
@@ -62,6 +67,9 @@ CHUNK_PREPARES = {"c2": 64, "c3": 64, "c3h": 64, "c4": 128}
 # 64- / 256- / 512-prepare blocks (1024: 1.76; round 6, profiles/r06/node/lib_ab/).  Per GPU a
 # 512-prepare block costs ~1 GB of send buffer and 2 GB of owner-leg regions at N = 8.
 NODE_CHUNK_PREPARES = {"c2": 512, "c3": 64, "c3h": 64, "c4": 128}
+# The options that size the legs beside the headline: those legs run with --full only.
+FULL_LEGS = ("latency_steps", "staged_steps", "host_steps", "secondary", "secondary_device", "cpu_sample", "access_mix",
+             "host_prepares", "replica_prepares", "write_back")
 
 
 def parse():
@@ -118,9 +126,22 @@ def parse():
     p.add_argument("--launch-check", action="store_true",
                    help="launcher rehearsal (CPU): every rank reports its place in the process group and exits "
                         "before touching a GPU")
+    p.add_argument("--full", action="store_true",
+                   help="also run every leg beside the headline (batch latency, staged and host paths, write-back, "
+                        "full-run checks, access mix, CPU baseline and parity, host commits, replica path, C3 / C4 "
+                        "lines); without it only the timed steps run and the options that size those legs are ignored")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps write what the last one computed as DIR/<name>.npy (float64): every "
+                        "prepare's reply size, a seeded sample of the events' result codes and stored transfers, and "
+                        "a seeded sample of the accounts (--gpus 1)")
     args = p.parse_args()
     if args.steps < 1:
         p.error("--steps must be at least 1 (the headline is measured over the timed steps)")
+    if args.dump_outputs and args.gpus > 1:
+        p.error("--dump-outputs is written by the single-GPU run (--gpus 1)")
+    if not args.full:
+        for leg in FULL_LEGS:
+            setattr(args, leg, 0)
     return args
 
 
@@ -639,6 +660,60 @@ def launch_check(args, world, rank):
                           "ranks": ranks, "worlds": worlds}), flush=True)
 
 
+DUMP_ACCOUNTS = 1 << 16        # sampled account records
+DUMP_TRANSFER_RUNS = 256       # sampled runs of consecutive events ...
+DUMP_TRANSFER_RUN = 256        # ... of this many events each
+
+
+def dump_outputs(out_dir, engine, args, lens, src, res_dev, rb_dev):
+    """What the last timed step computed, as float64 arrays (every integer in them is below 2^32, so
+    exact): what tbgpu_commit_device_async hands its caller, and samples of the state it left behind.
+    The samples are drawn from a generator seeded with --seed alone: the same arguments give the same
+    rows, whatever the build.
+
+      reply_bytes.npy  [prepares]     bytes of each prepare's reply
+      results.npy      [t, 3]         the sampled events' results, decoded from the replies: (prepare, index in
+                                      the prepare, result code; 0 where the reply holds no record: ok)
+      accounts.npy     [a, 32]        sampled account records (export order), as 32-bit little-endian words
+      transfers.npy    [t, 33]        sampled events' stored transfers, looked up by id (tbgpu_fetch_transfers):
+                                      the record as 32-bit words, then its state (0 absent, 1 + posted)"""
+    from tigerbeetle_amd.types import TRANSFER_DTYPE
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(args.seed)
+    n_prep, n_events = len(lens), int(sum(lens))
+    rb = engine.to_host(rb_dev, n_prep * 4).view(np.uint32)
+    np.save(os.path.join(out_dir, "reply_bytes.npy"), rb.astype(np.float64))
+
+    accts = engine.export_accounts()
+    pick = np.sort(rng.choice(len(accts), size=min(len(accts), DUMP_ACCOUNTS), replace=False))
+    np.save(os.path.join(out_dir, "accounts.npy"),
+            np.ascontiguousarray(accts[pick]).view(np.uint32).reshape(len(pick), 32).astype(np.float64))
+
+    run = min(DUMP_TRANSFER_RUN, n_events)
+    slots = n_events // run
+    first = np.sort(rng.choice(slots, size=min(slots, DUMP_TRANSFER_RUNS), replace=False)) * run
+    pos = (first[:, None] + np.arange(run)).reshape(-1)  # the sampled events' places in the step
+
+    lens_a = np.asarray(lens, dtype=np.int64)
+    starts = np.cumsum(lens_a) - lens_a
+    prep = np.searchsorted(starts, pos, side="right") - 1
+    code = np.zeros(len(pos), dtype=np.int64)
+    counts = (rb // 8).astype(np.int64)
+    if counts.sum():  # sparse replies at the prepare's event offset: (index, result), ascending by index
+        res = engine.to_host(res_dev, n_events * 8).view(np.uint32).reshape(-1, 2)
+        r_prep = np.repeat(np.arange(n_prep), counts)
+        rows = starts[r_prep] + np.arange(counts.sum()) - np.repeat(np.cumsum(counts) - counts, counts)
+        failed_at = starts[r_prep] + res[rows, 0]
+        at = np.minimum(np.searchsorted(failed_at, pos), len(failed_at) - 1)
+        code = np.where(failed_at[at] == pos, res[rows, 1][at], 0)
+    np.save(os.path.join(out_dir, "results.npy"), np.stack([prep, pos - starts[prep], code], axis=1).astype(np.float64))
+
+    events = np.concatenate([engine.to_host(src + int(f) * 128, run * 128) for f in first]).view(TRANSFER_DTYPE)
+    stored, state = engine.fetch_transfers(np.stack([events["id_lo"], events["id_hi"]], axis=1))
+    np.save(os.path.join(out_dir, "transfers.npy"),
+            np.concatenate([stored.view(np.uint32).reshape(len(stored), 32), state[:, None]], axis=1).astype(np.float64))
+
+
 def main():
     args = parse()
     if args.chunk_prepares is None:
@@ -725,9 +800,11 @@ def main():
 
     # -- transfers (synthetic, resident in HBM) ----------------------------------------------
     xfer_lens = batches(args.transfers, args.batch)
-    events_dev = engine.alloc(args.transfers * 128)
-    engine.generate_transfers(events_dev, 0, args.transfers, args.accounts, seed=seed, kind=KINDS[args.workload],
-                              limit_permille=wl["limit_permille"], hot_limited=wl.get("hot_limited", 0))
+    events_dev = None  # the separate HBM buffer: the in-place headline alone places its prepares in the log window
+    if args.full or not args.inplace:
+        events_dev = engine.alloc(args.transfers * 128)
+        engine.generate_transfers(events_dev, 0, args.transfers, args.accounts, seed=seed, kind=KINDS[args.workload],
+                                  limit_permille=wl["limit_permille"], hot_limited=wl.get("hot_limited", 0))
     engine.sync()
 
     def place(dst, count=None):
@@ -783,15 +860,19 @@ def main():
             issue_ms.append((t_issue - t0) * 1e3)
             sync_ms.append((t_sync - t0) * 1e3)
     stats = engine.stats()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, engine, args, xfer_lens, src, res_dev, rb_dev)
     # The batch latency: the same steps again, each pass between a HIP event pair (not timed).
-    engine.reset_stats()
-    engine.profile_mask(engine.PROF_PASS)
-    for _ in range(args.latency_steps):
-        src = headline_input()
-        ts, t_cursor = timestamps(xfer_lens, t_cursor + 10, wl["gap_every"])
-        engine.commit_device_async(129, ts, xfer_lens, src, res_dev, rb_dev)
-        engine.sync()
-    pass_lat = engine.pass_latencies()
+    pass_lat = []
+    if args.latency_steps:
+        engine.reset_stats()
+        engine.profile_mask(engine.PROF_PASS)
+        for _ in range(args.latency_steps):
+            src = headline_input()
+            ts, t_cursor = timestamps(xfer_lens, t_cursor + 10, wl["gap_every"])
+            engine.commit_device_async(129, ts, xfer_lens, src, res_dev, rb_dev)
+            engine.sync()
+        pass_lat = engine.pass_latencies()
     rb = engine.to_host(rb_dev, len(xfer_lens) * 4).view(np.uint32)
     n_failed = int(rb.sum()) // 8
 
@@ -891,24 +972,27 @@ def main():
 
     # -- full-run checks (size-independent properties) of the last timed step ---------------------
     # (the write-back leg committed other transfers since: re-run one untimed step to check them)
-    src = headline_input()
-    ts, t_cursor = timestamps(xfer_lens, t_cursor + 10, wl["gap_every"])
-    engine.commit_device_async(129, ts, xfer_lens, src, res_dev, rb_dev)
-    engine.sync()
-    rb = engine.to_host(rb_dev, len(xfer_lens) * 4).view(np.uint32)
-    accts = engine.export_accounts()
-    check_stats = engine.stats()
+    parity = None
+    if args.full:
+        src = headline_input()
+        ts, t_cursor = timestamps(xfer_lens, t_cursor + 10, wl["gap_every"])
+        engine.commit_device_async(129, ts, xfer_lens, src, res_dev, rb_dev)
+        engine.sync()
+        rb = engine.to_host(rb_dev, len(xfer_lens) * 4).view(np.uint32)
+        accts = engine.export_accounts()
+        check_stats = engine.stats()
 
-    def total(field):
-        return sum(int(x) for x in accts[field + "_lo"]) + (sum(int(x) for x in accts[field + "_hi"]) << 64)
+        def total(field):
+            return sum(int(x) for x in accts[field + "_lo"]) + (sum(int(x) for x in accts[field + "_hi"]) << 64)
 
-    dpost, cpost = total("debits_posted"), total("credits_posted")
-    # C2: every transfer commits.  Every config: each committed transfer is one record; debits equal
-    # credits in total, posted and pending.
-    full_ok = bool(check_stats["transfers"] == args.transfers - n_failed and dpost == cpost and dpost > 0
-                   and total("debits_pending") == total("credits_pending") and len(accts) == args.accounts
-                   and (n_failed == 0 or args.workload != "c2") and int(rb.sum()) // 8 == n_failed
-                   and n_failed_host == n_failed)
+        dpost, cpost = total("debits_posted"), total("credits_posted")
+        # C2: every transfer commits.  Every config: each committed transfer is one record; debits equal
+        # credits in total, posted and pending.
+        full_ok = bool(check_stats["transfers"] == args.transfers - n_failed and dpost == cpost and dpost > 0
+                       and total("debits_pending") == total("credits_pending") and len(accts) == args.accounts
+                       and (n_failed == 0 or args.workload != "c2") and int(rb.sum()) // 8 == n_failed
+                       and n_failed_host == n_failed)
+        parity = {"full_run_properties": full_ok}
 
     total_ms = sum(step_ms)
     n_total = args.transfers * world * args.steps
@@ -934,7 +1018,6 @@ def main():
 
     # -- CPU baseline + bit-exact sample parity (rank 0, N=1 only) ---------------------------
     cpu = None
-    parity = {"full_run_properties": full_ok}
     if rank == 0 and world == 1 and args.cpu_sample > 0:
         sample_lens = batches(min(args.cpu_sample, args.transfers), args.batch)
         sample_ts, t_cursor = timestamps(sample_lens, t_cursor + 10, wl["gap_every"])
@@ -986,7 +1069,8 @@ def main():
     # index, the resident prepares) is released first, so they run on the same memory a standalone
     # `--workload c3|c4` run gets.
     for ptr in (events_dev, res_dev, rb_dev):
-        engine.free(ptr)
+        if ptr is not None:
+            engine.free(ptr)
     engine.close()
     replica_path = None
     if rank == 0 and world == 1 and args.replica_prepares > 0:
@@ -996,7 +1080,7 @@ def main():
         for kind in ("c3", "c3h", "c4"):
             secondary[kind] = run_secondary(args, kind, local_rank)
 
-    pass_lat = np.sort(np.array(pass_lat)) if len(pass_lat) else np.array([float("nan")])
+    pass_lat = np.sort(np.array(pass_lat))
     line = {
         "metric": METRIC,
         "value": round(value, 1),
@@ -1020,12 +1104,12 @@ def main():
                              "prepare bodies resident in HBM when the timed region starts (tbgpu_commit_device_async)")
                             + "; replies written to HBM; the PCIe-inclusive rate is `host_path`",
                    "host_numa_node": args.numa_node, "parallelism": "single"},
-        "p99_batch_latency_ms": round(ref_percentile(pass_lat, 99), 3),
+        "p99_batch_latency_ms": round(ref_percentile(pass_lat, 99), 3) if len(pass_lat) else None,
         "batch_latency_ms": dict(deciles(pass_lat), definition=(
             "per prepare, commit to reply: its device pass's duration (a prepare's reply is complete when its "
             "%d-prepare pass is; device clock, HIP events around each pass, in %d steps run after the timed "
             "ones so that no event pair sits among the timed launches); percentiles by "
-            "src/benchmark.zig:454-471" % (args.pass_batches, args.latency_steps))),
+            "src/benchmark.zig:454-471" % (args.pass_batches, args.latency_steps))) if len(pass_lat) else None,
         "host_path": host_path,
         "device_resident_staged": staged,
         "dependent_events": stats["dependent_events"],

@@ -10,7 +10,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 CHILD = r"""
 import json, sys
-sys.argv = ["bench.py", "--secondary", "10000000"]
+sys.argv = ["bench.py", "--full", "--secondary", "10000000"]
 import bench
 from tigerbeetle_amd.state_machine import Engine
 seen = {}

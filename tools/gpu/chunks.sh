@@ -9,7 +9,7 @@ shift
 kinds=${*:-"c3 c4"}
 for k in $kinds; do
   for c in $sizes; do
-    timeout -k 10 300 python -u bench.py --workload $k --accounts 1000000 --transfers 10000000 --steps 2 --warmup 1 \
+    timeout -k 10 300 python -u bench.py --full --workload $k --accounts 1000000 --transfers 10000000 --steps 2 --warmup 1 \
       --chunk-prepares $c --cpu-sample 0 --host-prepares 0 --device-steps 0 --secondary 0 --access-mix 0 \
       > gpurun_out/chunks_${k}_$c.log 2>&1 || { echo FAIL $k $c; tail -5 gpurun_out/chunks_${k}_$c.log; exit 1; }
     python - "$k" "$c" <<'EOF'
