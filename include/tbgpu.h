@@ -15,6 +15,8 @@
  *     input, output) -> usize (:508-540)                     tbgpu_commit_many (N prepares, one
  *                                                             device pass; same bytes as N commits)
  *   execute_lookup_accounts / _transfers (:700-736)        tbgpu_commit with operation 130 / 131
+ *   the transfers groove's account-id index trees          tbgpu_get_account_transfers (no reference
+ *     (:140-178; no reference operation reads them)          operation: specified below)
  *   `setup` action of the table tests (:1398-1407)         tbgpu_test_set_balances (test only)
  *   StateMachine.commit_timestamp field (:251)             tbgpu_commit_timestamp
  *
@@ -268,6 +270,55 @@ int tbgpu_load_transfers(tbgpu_t* engine, const void* transfers, const uint8_t* 
  * cold query on its home shard. */
 int tbgpu_evict_transfers(tbgpu_t* engine, uint64_t keep, uint64_t* evicted);
 int tbgpu_transfers_maybe_cold(tbgpu_t* engine, const uint64_t* ids, uint32_t n, uint8_t* cold);
+
+/* get_account_transfers: which transfers touched one account.  The reference maintains the
+ * debit_account_id / credit_account_id index trees of the transfers groove for this query
+ * (src/state_machine.zig:140-178) but has no operation that reads them, and its Operation enum has no
+ * number for it — so it is an entry point of its own (tbgpu_commit keeps refusing operations outside
+ * 128-131), and this comment is its specification.
+ *   What matches: a committed, resident transfer (its record is live: the id index holds its id at
+ *     that log position) whose debit account id equals account_id under DEBITS, or whose credit
+ *     account id equals it under CREDITS (a record matching on both sides is returned once), with its
+ *     timestamp in [timestamp_min, timestamp_max] (0 leaves that end open).  Post / void records carry
+ *     their pending transfer's account ids (src/state_machine.zig:971-985) and match under those.
+ *     Failed events, withdrawn speculative records and rolled-back chain members never match.
+ *   What is returned: the first min(limit, out_cap_records, TBGPU_BATCH_EVENTS_MAX) matches (one reply
+ *     is one message body) by timestamp ascending, or descending from the newest under REVERSED —
+ *     whole 128-byte records, the bytes lookup_transfers returns for the same ids — whatever order the
+ *     log holds them in (loads and upserts append out of timestamp order).  `matched` counts all.
+ *   Invalid filters are never a status: account_id 0 or 2^128-1, timestamp_min or timestamp_max
+ *     2^64-1, a non-zero timestamp_max below timestamp_min, limit 0, neither DEBITS nor CREDITS, an
+ *     unknown flag bit, a non-zero reserved byte — each returns TBGPU_STATUS_OK with count = matched
+ *     = 0.  A NULL filter, out or result is TBGPU_STATUS_INVALID.
+ *   Synchronous; drains a pending tbgpu_commit_device_async first, as tbgpu_commit does.  A read: it
+ *     changes nothing (commit_timestamp, balances, log, index, stats, the write-back snapshot), works
+ *     on an engine a device panic stopped, allocates nothing, and is legal while an asynchronous
+ *     write-back is in flight.
+ *   A node engine has the same contract: every home shard scans its own log on its own device and the
+ *     host merges the shards' answers by timestamp under the limit. */
+#define TBGPU_FILTER_DEBITS   (1u << 0)  /* match debit_account_id  == account_id */
+#define TBGPU_FILTER_CREDITS  (1u << 1)  /* match credit_account_id == account_id */
+#define TBGPU_FILTER_REVERSED (1u << 2)  /* newest first */
+
+typedef struct tbgpu_account_filter {    /* 64 bytes, little-endian, no padding */
+    uint64_t account_id_lo, account_id_hi;
+    uint64_t timestamp_min;              /* inclusive; 0 = no lower bound */
+    uint64_t timestamp_max;              /* inclusive; 0 = no upper bound */
+    uint32_t limit;
+    uint32_t flags;
+    uint8_t  reserved[24];               /* must be zero */
+} tbgpu_account_filter;
+
+typedef struct tbgpu_query_result {
+    uint32_t count;     /* records written to out */
+    uint32_t complete;  /* 1: no transfer was ever evicted from this engine (any shard of a node), so
+                           `out` is the ledger's answer; 0: only the resident transfers were searched,
+                           and the caller merges with its forest */
+    uint64_t matched;   /* resident transfers matching the filter, before the limit */
+} tbgpu_query_result;
+
+int tbgpu_get_account_transfers(tbgpu_t* engine, const tbgpu_account_filter* filter,
+                                void* out, uint32_t out_cap_records, tbgpu_query_result* result);
 
 /* The replica writes StateMachine.commit_timestamp itself: the header timestamp after every commit
  * (src/vsr/replica.zig:3664-3665) and the checkpoint's value on open / state sync.  The wrapper

@@ -63,6 +63,12 @@ int tbgpu_bench_walk_merge_max(tbgpu_t* engine, uint32_t segments);
  * closes exit (k_flow.h fl_admit), as under a co-tenant. */
 int tbgpu_bench_flow_launch(tbgpu_t* engine, uint32_t workgroups);
 
+/* tbgpu_get_account_transfers on a log out of timestamp order (loads, upserts) runs in rounds over
+ * ranges of the log whose matches fit a key buffer made at init: use at most this many of its keys
+ * (clamped to [256, the buffer's size]; 0: all of it), so a test sees several rounds on a small log.
+ * Exact either way. */
+int tbgpu_bench_query_keys_max(tbgpu_t* engine, uint32_t keys);
+
 /* The memory-access mix of tb_transfers_validate without its logic, on scratch buffers sized like
  * this engine's account table and transfer index, for `transfers` events (one pass): mean ms of
  * {stream, probe, cas, stream+probe, stream+cas, probe+cas, all three} (k_workload.h).  The
@@ -96,6 +102,9 @@ int tbgpu_device_alloc(tbgpu_t* engine, uint64_t bytes, void** out);
 int tbgpu_device_free(tbgpu_t* engine, void* ptr);
 int tbgpu_copy_to_host(tbgpu_t* engine, void* dst, const void* src_dev, uint64_t bytes);
 int tbgpu_copy_to_device(tbgpu_t* engine, void* dst_dev, const void* src, uint64_t bytes);
+/* Device to device, enqueued on the engine's stream (time it between two tbgpu_marker calls): the
+ * yardstick tools/gpu/query_scan.py holds the account-filter scan to. */
+int tbgpu_copy_device_async(tbgpu_t* engine, void* dst_dev, const void* src_dev, uint64_t bytes);
 
 /* Device-side timing of the last tbgpu_sync'ed work: elapsed ms between two markers recorded on
  * the engine stream. */

@@ -38,6 +38,16 @@ class tbgpu_delta_counts(ctypes.Structure):
                 ("created_after", ctypes.c_uint64)]
 
 
+class tbgpu_account_filter(ctypes.Structure):
+    _fields_ = [("account_id_lo", ctypes.c_uint64), ("account_id_hi", ctypes.c_uint64),
+                ("timestamp_min", ctypes.c_uint64), ("timestamp_max", ctypes.c_uint64),
+                ("limit", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint8 * 24)]
+
+
+class tbgpu_query_result(ctypes.Structure):
+    _fields_ = [("count", ctypes.c_uint32), ("complete", ctypes.c_uint32), ("matched", ctypes.c_uint64)]
+
+
 class tbgpu_stats(ctypes.Structure):
     _fields_ = [
         ("passes", ctypes.c_uint64),
@@ -156,6 +166,8 @@ SIGNATURES = [
     ("tbgpu_export_accounts", ctypes.c_int, [_P, _P, _U64, ctypes.POINTER(_U64)]),
     ("tbgpu_export_transfers", ctypes.c_int, [_P, _P, _U64, ctypes.POINTER(_U64)]),
     ("tbgpu_export_posted", ctypes.c_int, [_P, _P, _U64, ctypes.POINTER(_U64)]),
+    ("tbgpu_get_account_transfers", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
+    ("tbgpu_bench_query_keys_max", ctypes.c_int, [_P, _U32]),
     ("tbgpu_get_stats", ctypes.c_int, [_P, ctypes.POINTER(tbgpu_stats)]),
     ("tbgpu_reset_stats", None, [_P]),
     ("tbgpu_last_error", ctypes.c_char_p, []),
@@ -188,6 +200,7 @@ SIGNATURES = [
     ("tbgpu_transfers_maybe_cold", ctypes.c_int, [_P, _P, _U32, _P]),
     ("tbgpu_unregister_host", ctypes.c_int, [_P, _P]),
     ("tbgpu_copy_to_device", ctypes.c_int, [_P, _P, _P, _U64]),
+    ("tbgpu_copy_device_async", ctypes.c_int, [_P, _P, _P, _U64]),
     ("tbgpu_marker", ctypes.c_int, [_P, _U32]),
     ("tbgpu_marker_elapsed_ms", ctypes.c_double, [_P, _U32, _U32]),
     # include/tbgpu_shard.h

@@ -32,6 +32,7 @@
 #include "k_node.h"
 #include "k_workload.h"
 #include "k_evict.h"
+#include "k_query.h"
 #include "checksum.h"
 
 static thread_local std::string g_err;
@@ -153,6 +154,31 @@ struct WbBufs {
     std::vector<u64> ids_inflight;
 };
 
+// tbgpu_get_account_transfers (k_query.h): every buffer made at tbgpu_init, none shared with the
+// write-back or the lookups (a write-back may be in flight beside a query).
+#define QUERY_KEYS_CAP (1u << 16)  // {timestamp, position} keys of one round of the unordered path
+struct QueryBufs {
+    u64 nb_cap = 0;            // tiles of QUERY_THREADS log positions in the whole log
+    u32* d_counts = nullptr;   // [nb_cap] matches per tile
+    u64* d_mins = nullptr;     // [nb_cap] their smallest timestamp
+    u64* d_maxs = nullptr;     // [nb_cap] ... and largest
+    u32* d_ordered = nullptr;  // [nb_cap] 1: the tile's matches rise with position
+    u64* d_base = nullptr;     // [nb_cap] exclusive prefix of d_counts
+    u64* d_res = nullptr;      // {total, ordered}
+    u64* h_res = nullptr;      // pinned mirror
+    u8* d_out = nullptr;       // [BATCH_EVENTS_MAX] the answer's records
+    u64* d_keys = nullptr;     // [QUERY_KEYS_CAP][2] unordered path: a round's keys; then the chosen positions
+    u64* h_keys = nullptr;     // pinned mirror
+    u64* h_base = nullptr;     // pinned [nb_cap + 1]: the bases, read back on the unordered path only
+    u32 keys_max = QUERY_KEYS_CAP;  // tbgpu_bench_query_keys_max
+    bool coop = false;         // tb_query_count's load shape (TBGPU_QUERY_COOP=1: cooperative 16-B chunks)
+    // One query in flight between query_enqueue and query_collect.
+    QueryFilter F{};
+    u32 k = 0;
+    bool reversed = false;
+    u64 n = 0;
+};
+
 struct tbgpu {
     tbgpu_config cfg{};
     TbNode* node = nullptr;  // set: this handle is a node engine; every call goes to node.h
@@ -261,6 +287,7 @@ struct tbgpu {
     u32 legs_min = LEGS_MIN_EVENTS;
     u64 wall_khz = 0;  // device wall clock (flow phase timing)
     WbBufs wb;
+    QueryBufs q;
     // Groove write-back snapshot (tbgpu_checkpoint_delta).
     u64* ckpt_bal = nullptr;  // balances at the previous write-back: the two planes of T.bal (tb_device.h BalView)
     u32* ckpt_mark = nullptr;        // per slot: the write-back epoch that last covered it
@@ -525,6 +552,8 @@ static int node_fetch(TbNode* N, bool accounts, const u64* ids, u32 n, u8* out, 
 static int node_api_accounts_in(TbNode* N, const void* records, u32 n, bool load);
 static int node_api_transfers_in(TbNode* N, const void* records, const u8* state, u32 n, bool load);
 static int node_api_set_commit_timestamp(TbNode* N, u64 timestamp);
+static int node_get_account_transfers(TbNode* N, const QueryFilter& F, bool valid, u32 k, bool reversed, u8* out,
+                                      tbgpu_query_result* result);
 
 extern "C" int tbgpu_init(const tbgpu_config* config, tbgpu_t** out) {
     if (config && config->device_count > 1) return node_api_init(config, out);
@@ -791,6 +820,22 @@ extern "C" int tbgpu_init(const tbgpu_config* config, tbgpu_t** out) {
         INIT_CK(tbEventCreateWithFlags(&W.read_done, hipEventDisableTiming));
         INIT_CK(tbEventCreateWithFlags(&W.captured, hipEventDisableTiming));
     }
+    {  // tbgpu_get_account_transfers: per-tile counts and bounds, the answer, the unordered path's keys
+        QueryBufs& Q = E->q;
+        Q.nb_cap = (E->xlog_cap + QUERY_THREADS - 1) / QUERY_THREADS;
+        INIT_CK(tbMalloc(&Q.d_counts, Q.nb_cap * 4));
+        INIT_CK(tbMalloc(&Q.d_mins, Q.nb_cap * 8));
+        INIT_CK(tbMalloc(&Q.d_maxs, Q.nb_cap * 8));
+        INIT_CK(tbMalloc(&Q.d_ordered, Q.nb_cap * 4));
+        INIT_CK(tbMalloc(&Q.d_base, Q.nb_cap * 8));
+        INIT_CK(tbMalloc(&Q.d_res, 16));
+        INIT_CK(tbHostMalloc(&Q.h_res, 16, hipHostMallocDefault));
+        INIT_CK(tbMalloc(&Q.d_out, (u64)BATCH_EVENTS_MAX * 128));
+        INIT_CK(tbMalloc(&Q.d_keys, (u64)QUERY_KEYS_CAP * 16));
+        INIT_CK(tbHostMalloc(&Q.h_keys, (u64)QUERY_KEYS_CAP * 16, hipHostMallocDefault));
+        INIT_CK(tbHostMalloc(&Q.h_base, (Q.nb_cap + 1) * 8, hipHostMallocDefault));
+        if (const char* v = getenv("TBGPU_QUERY_COOP")) Q.coop = atoi(v) != 0;  // the load-shape measurement
+    }
     INIT_CK(tbHostMalloc(&E->h_pub, 8, hipHostMallocDefault));
     INIT_CK(tbMalloc(&E->kclock, (u64)KCLOCK_SLOTS * KCLOCK_WORDS * 8));
     INIT_CK(tbHostMalloc(&E->h_kclock, (u64)KCLOCK_SLOTS * KCLOCK_WORDS * 8, hipHostMallocDefault));
@@ -827,6 +872,7 @@ extern "C" void tbgpu_deinit(tbgpu_t* E) {
                     E->lookup_ids, E->lookup_out, E->lookup_found, E->d_status, E->pf_staging, E->kclock, E->r_home,
                     E->wb.d_bc, E->wb.d_base, E->wb.d_out, E->wb.d_ids, E->wb.d_pv, E->wb.d_pairs, E->wb.d_hids,
                     E->wb.d_acc, E->wb.d_before, E->wb.d_slots, E->wb.d_cap, E->wb.d_cnt,
+                    E->q.d_counts, E->q.d_mins, E->q.d_maxs, E->q.d_ordered, E->q.d_base, E->q.d_res, E->q.d_out, E->q.d_keys,
                     E->r_block_counts, E->r_words, E->r_meta, E->resolve_slow, E->leg_w, E->leg_off, E->leg_tot,
                     E->F.f_pe, E->F.f_batch, E->F.f_len, E->F.need, E->F.nsucc, E->F.queue, E->F.uflags, E->F.nacct, E->F.rpos, E->F.succ,
                     E->F.run, E->F.keys[0], E->F.keys[1], E->F.vals[0], E->F.vals[1], E->F.hist, E->F.words, E->F.undo,
@@ -849,6 +895,7 @@ extern "C" void tbgpu_deinit(tbgpu_t* E) {
     if (E->h_rmeta) (void)hipHostFree(E->h_rmeta);
     if (E->h_kclock) (void)hipHostFree(E->h_kclock);
     if (E->h_pub) (void)hipHostFree(E->h_pub);
+    for (u64* p : {E->q.h_res, E->q.h_keys, E->q.h_base}) if (p) (void)hipHostFree(p);
     if (E->wb.h_cnt) (void)hipHostFree(E->wb.h_cnt);
     if (E->wb.stream) {
         (void)hipStreamSynchronize(E->wb.stream);
@@ -2411,6 +2458,16 @@ extern "C" int tbgpu_bench_flow_launch(tbgpu_t* E, uint32_t workgroups) {
     return TBGPU_STATUS_OK;
 }
 
+extern "C" int tbgpu_bench_query_keys_max(tbgpu_t* E, uint32_t keys) {
+    API_ENTER(E, false);
+    if (E->node) {
+        for (u32 d = 0; d < node_world(E->node); d++) tbgpu_bench_query_keys_max(node_engine(E->node, d), keys);
+        return TBGPU_STATUS_OK;
+    }
+    E->q.keys_max = keys ? std::min<u32>(std::max<u32>(keys, QUERY_THREADS), QUERY_KEYS_CAP) : QUERY_KEYS_CAP;
+    return TBGPU_STATUS_OK;
+}
+
 extern "C" int tbgpu_bench_legs_min_events(tbgpu_t* E, uint32_t events) {
     API_ENTER(E, false);
     if (E->node) {
@@ -2609,6 +2666,14 @@ extern "C" int tbgpu_copy_to_device(tbgpu_t* E, void* dst_dev, const void* src, 
     HIPCK(hipSetDevice(E->device));
     HIPCK(hipStreamSynchronize(E->stream));
     HIPCK(hipMemcpy(dst_dev, src, bytes, hipMemcpyHostToDevice));
+    return TBGPU_STATUS_OK;
+}
+
+extern "C" int tbgpu_copy_device_async(tbgpu_t* E, void* dst_dev, const void* src_dev, uint64_t bytes) {
+    API_ENTER(E, false);
+    if (E->node) E = node_engine(E->node, 0);
+    HIPCK(hipSetDevice(E->device));
+    HIPCK(hipMemcpyAsync(dst_dev, src_dev, bytes, hipMemcpyDeviceToDevice, E->stream));
     return TBGPU_STATUS_OK;
 }
 
@@ -3251,6 +3316,148 @@ extern "C" int tbgpu_set_commit_timestamp(tbgpu_t* E, uint64_t timestamp) {
     E->last_batch_ts = timestamp;
     HIPCK(hipMemcpyAsync(&E->g->commit_timestamp, &E->commit_ts, 8, hipMemcpyHostToDevice, E->stream));
     HIPCK(hipStreamSynchronize(E->stream));
+    return TBGPU_STATUS_OK;
+}
+
+// ---- get_account_transfers (k_query.h, include/tbgpu.h) -------------------------------------------
+// The scan of one engine's log in two halves, so that a node runs its shards' scans side by side:
+// query_enqueue puts count -> scan -> scatter on the engine stream (nothing crosses PCIe but the
+// {total, ordered} word); query_collect waits, copies the answer's records, and runs the exact path
+// of a log out of timestamp order when the scan found one.  The stream is drained before (a pending
+// tbgpu_commit_device_async), so log_next is the log's end and nothing writes beside the scan.
+static int query_enqueue(tbgpu* E, const QueryFilter& F, u32 k, bool reversed) {
+    QueryBufs& Q = E->q;
+    HIPCK(hipSetDevice(E->device));
+    if (E->pending) {
+        int st = engine_sync(E);
+        if (st) return st;
+    }
+    Q.F = F;
+    Q.k = k;
+    Q.reversed = reversed;
+    Q.n = E->log_next;
+    Q.h_res[0] = Q.h_res[1] = 0;
+    const u64 nb = (Q.n + QUERY_THREADS - 1) / QUERY_THREADS;
+    if (nb == 0) return TBGPU_STATUS_OK;
+    if (nb > Q.nb_cap) return fail(TBGPU_STATUS_PANIC, "query: the log's end %llu is past its capacity", (unsigned long long)Q.n);
+    if (Q.coop) {
+        hipLaunchKernelGGL(tb_query_count<true>, dim3((unsigned)nb), dim3(QUERY_THREADS), 0, E->stream, E->T, F, Q.n,
+                           Q.d_counts, Q.d_mins, Q.d_maxs, Q.d_ordered);
+    } else {
+        hipLaunchKernelGGL(tb_query_count<false>, dim3((unsigned)nb), dim3(QUERY_THREADS), 0, E->stream, E->T, F, Q.n,
+                           Q.d_counts, Q.d_mins, Q.d_maxs, Q.d_ordered);
+    }
+    hipLaunchKernelGGL(tb_query_scan, dim3(1), dim3(1024), 0, E->stream, Q.d_counts, Q.d_mins, Q.d_maxs, Q.d_ordered, nb,
+                       Q.d_base, Q.d_res);
+    hipLaunchKernelGGL(tb_query_scatter, dim3((unsigned)nb), dim3(QUERY_THREADS), 0, E->stream, E->T, F, Q.n, Q.d_counts,
+                       Q.d_base, Q.d_res, k, reversed ? 1u : 0u, Q.d_out);
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpyAsync(Q.h_res, Q.d_res, 16, hipMemcpyDeviceToHost, E->stream));
+    return TBGPU_STATUS_OK;
+}
+
+// out: room for the enqueued k records.  *count = records written, *matched = every match.
+static int query_collect(tbgpu* E, u8* out, u32* count, u64* matched) {
+    QueryBufs& Q = E->q;
+    *count = 0;
+    *matched = 0;
+    const u64 nb = (Q.n + QUERY_THREADS - 1) / QUERY_THREADS;
+    if (nb == 0) return TBGPU_STATUS_OK;
+    HIPCK(hipSetDevice(E->device));
+    HIPCK(hipStreamSynchronize(E->stream));
+    const u64 total = Q.h_res[0];
+    const bool ordered = Q.h_res[1] != 0;
+    const u32 m = (u32)std::min<u64>(Q.k, total);
+    *matched = total;
+    if (m == 0) return TBGPU_STATUS_OK;
+    if (!ordered) {
+        // Exact with bounded memory: rounds over ranges of tiles whose matches fit the key buffer (the
+        // bases say which), the best m keys kept across rounds, then one gather of their records.
+        HIPCK(hipMemcpyAsync(Q.h_base, Q.d_base, nb * 8, hipMemcpyDeviceToHost, E->stream));
+        HIPCK(hipStreamSynchronize(E->stream));
+        Q.h_base[nb] = total;
+        typedef std::pair<u64, u64> Key;  // {timestamp, position}
+        std::vector<Key> best;
+        const bool rev = Q.reversed;
+        auto before = [rev](const Key& a, const Key& b) { return rev ? a > b : a < b; };
+        auto cut = [&]() {
+            if (best.size() <= m) return;
+            std::nth_element(best.begin(), best.begin() + m, best.end(), before);
+            best.resize(m);
+        };
+        u64 b0 = 0;
+        while (b0 < nb && Q.h_base[b0] < total) {
+            // Skip tiles without a match, then take tiles while their matches fit (a tile holds at most
+            // QUERY_THREADS <= keys_max, so every round advances).
+            b0 = (u64)(std::upper_bound(Q.h_base + b0, Q.h_base + nb + 1, Q.h_base[b0]) - Q.h_base) - 1;
+            const u64 b1 = (u64)(std::upper_bound(Q.h_base + b0, Q.h_base + nb + 1, Q.h_base[b0] + Q.keys_max) - Q.h_base) - 1;
+            const u64 keys = Q.h_base[b1] - Q.h_base[b0];
+            if (b1 <= b0 || keys > Q.keys_max) return fail(TBGPU_STATUS_PANIC, "query: a round of %llu keys", (unsigned long long)keys);
+            hipLaunchKernelGGL(tb_query_keys, dim3((unsigned)(b1 - b0)), dim3(QUERY_THREADS), 0, E->stream, E->T, Q.F, Q.n, b0,
+                               Q.d_counts, Q.d_base, Q.d_keys, (u64)Q.keys_max);
+            HIPCK(hipGetLastError());
+            HIPCK(hipMemcpyAsync(Q.h_keys, Q.d_keys, keys * 16, hipMemcpyDeviceToHost, E->stream));
+            HIPCK(hipStreamSynchronize(E->stream));
+            for (u64 i = 0; i < keys; i++) best.push_back(Key(Q.h_keys[2 * i], Q.h_keys[2 * i + 1]));
+            if (best.size() > 2 * (size_t)m + Q.keys_max) cut();
+            b0 = b1;
+        }
+        cut();
+        std::sort(best.begin(), best.end(), before);
+        if (best.size() != m) return fail(TBGPU_STATUS_PANIC, "query: %zu keys for %u matches", best.size(), m);
+        for (u32 i = 0; i < m; i++) Q.h_keys[i] = best[i].second;
+        HIPCK(hipMemcpyAsync(Q.d_keys, Q.h_keys, (u64)m * 8, hipMemcpyHostToDevice, E->stream));
+        hipLaunchKernelGGL(tb_query_gather, dim3((m + QUERY_THREADS - 1) / QUERY_THREADS), dim3(QUERY_THREADS), 0, E->stream,
+                           E->T, Q.d_keys, m, Q.n, Q.d_out);
+        HIPCK(hipGetLastError());
+    }
+    HIPCK(hipMemcpyAsync(out, Q.d_out, (u64)m * 128, hipMemcpyDeviceToHost, E->stream));
+    HIPCK(hipStreamSynchronize(E->stream));
+    *count = m;
+    return TBGPU_STATUS_OK;
+}
+
+// The filter's rules (tbgpu.h): an invalid filter answers nothing, it is never a status.
+static bool query_filter_valid(const tbgpu_account_filter* f) {
+    if (tb_id_reserved(f->account_id_lo, f->account_id_hi)) return false;
+    if (f->timestamp_min == ~0ULL || f->timestamp_max == ~0ULL) return false;
+    if (f->timestamp_max != 0 && f->timestamp_max < f->timestamp_min) return false;
+    if (f->limit == 0) return false;
+    if (!(f->flags & (TBGPU_FILTER_DEBITS | TBGPU_FILTER_CREDITS))) return false;
+    if (f->flags & ~(TBGPU_FILTER_DEBITS | TBGPU_FILTER_CREDITS | TBGPU_FILTER_REVERSED)) return false;
+    for (u8 b : f->reserved) if (b) return false;
+    return true;
+}
+
+extern "C" int tbgpu_get_account_transfers(tbgpu_t* E, const tbgpu_account_filter* filter, void* out,
+                                           uint32_t out_cap_records, tbgpu_query_result* result) {
+    API_ENTER(E, false);  // a read: legal on a stopped engine, like the exports
+    if (!filter || !out || !result) return fail(TBGPU_STATUS_INVALID, "get_account_transfers: a NULL filter, out or result");
+    result->count = 0;
+    result->matched = 0;
+    result->complete = 0;
+    QueryFilter F{};
+    F.id_lo = filter->account_id_lo;
+    F.id_hi = filter->account_id_hi;
+    F.ts_min = filter->timestamp_min;
+    F.ts_max = filter->timestamp_max ? filter->timestamp_max : ~0ULL;
+    F.debits = (filter->flags & TBGPU_FILTER_DEBITS) != 0;
+    F.credits = (filter->flags & TBGPU_FILTER_CREDITS) != 0;
+    const bool reversed = (filter->flags & TBGPU_FILTER_REVERSED) != 0;
+    const bool valid = query_filter_valid(filter);
+    // One reply is one message body.
+    const u32 k = std::min<u32>(std::min<u32>(filter->limit, out_cap_records), BATCH_EVENTS_MAX);
+    if (E->node) return node_get_account_transfers(E->node, F, valid, k, reversed, (u8*)out, result);
+    result->complete = E->evicted_total == 0;
+    if (!valid) return TBGPU_STATUS_OK;
+    int st = query_enqueue(E, F, k, reversed);
+    if (st) return st;
+    u32 count = 0;
+    u64 matched = 0;
+    st = query_collect(E, (u8*)out, &count, &matched);
+    if (st) return st;
+    result->count = count;
+    result->matched = matched;
     return TBGPU_STATUS_OK;
 }
 

@@ -1,0 +1,233 @@
+// k_query.h — get_account_transfers (include/tbgpu.h tbgpu_get_account_transfers): which resident
+// transfers touched one account, by timestamp, under a limit.
+//
+// The reference keeps debit_account_id / credit_account_id index trees on the transfers groove for
+// this query (src/state_machine.zig:140-178).  Here the transfer log is an array of 128-B records in
+// HBM whose order is timestamp order (except after a load or an upsert), so the query
+// is a scan of 40 bytes of every record followed by an ordered compaction under the limit:
+//   tb_query_count    a tile of QUERY_THREADS log positions per workgroup: how many match, their
+//                     smallest and largest timestamp, and whether they rise with position;
+//   tb_query_scan     one workgroup: the exclusive bases, the total, and whether the whole log's
+//                     matches are in timestamp order (every tile ordered, its minimum above the
+//                     running maximum);
+//   tb_query_scatter  ordered: the matches whose rank falls among the wanted k write their record at
+//                     that rank (from the other end under REVERSED); every other workgroup exits;
+//   tb_query_keys /   unordered (loads and upserts only): {timestamp, position} keys of the matches
+//   tb_query_gather   of a range of tiles that fits the key buffer, a round at a time; the host keeps
+//                     the best k and one gather copies their records.
+// Plain launches: no grid barrier, no spin, no wait on another workgroup; every loop is bounded by
+// the grid or by k.
+#pragma once
+
+#include "pass.h"
+
+#define QUERY_THREADS 256
+#define QUERY_WAVES (QUERY_THREADS / 64)
+
+struct QueryFilter {
+    u64 id_lo, id_hi;
+    u64 ts_min, ts_max;  // inclusive; ts_max = ~0: no upper bound
+    u32 debits, credits;
+};
+
+struct QueryFields {
+    u64 dlo, dhi, clo, chi, ts;
+};
+
+// The 40 bytes the test needs of the record at `pos`: both account ids (bytes 16-47) and the
+// timestamp (byte 120).  COOP = false: the lane reads its own record (two 16-B loads and one 8-B
+// load, 128 B apart from its neighbours').  COOP = true: the wave reads chunks 1, 2 and 7 of its 64
+// records with neighbouring lanes on neighbouring chunks and hands them over through LDS.
+template <bool COOP>
+__device__ static inline QueryFields tb_query_fields(const Tables& T, u64 tile0, u64 n, u64* s_raw) {
+    QueryFields f{0, 0, 0, 0, 0};
+    if (!COOP) {
+        const u64 pos = tile0 + threadIdx.x;
+        if (pos < n) {
+            const ulonglong2* c = (const ulonglong2*)&T.xlog[pos];
+            const ulonglong2 d = c[1], cr = c[2];
+            f.ts = ((const u64*)c)[15];
+            f.dlo = d.x, f.dhi = d.y, f.clo = cr.x, f.chi = cr.y;
+        }
+        return f;
+    }
+    const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const u64 wave0 = tile0 + (u64)wave * 64;
+    ulonglong2* s = (ulonglong2*)s_raw + wave * 192;
+#pragma unroll
+    for (u32 j = 0; j < 3; j++) {
+        const u32 idx = j * 64 + lane, r = idx / 3, q = idx % 3;
+        ulonglong2 v{0, 0};
+        if (wave0 + r < n) v = ((const ulonglong2*)&T.xlog[wave0 + r])[q == 2 ? 7 : q + 1];
+        s[idx] = v;
+    }
+    __syncthreads();
+    const ulonglong2 d = s[lane * 3], cr = s[lane * 3 + 1], t = s[lane * 3 + 2];
+    f.dlo = d.x, f.dhi = d.y, f.clo = cr.x, f.chi = cr.y, f.ts = t.y;
+    return f;
+}
+
+// Whether the record at `pos` answers the filter: the account on a wanted side, the timestamp in the
+// window, and — only then — live: the id index holds its id at this position (tb_delta_live's test).
+// A dead position (a failed event, a withdrawn speculative record, a rolled-back chain member) can
+// hold any bytes, so reserved ids never reach the probe.
+__device__ static inline bool tb_query_hit(const Tables& T, const QueryFilter& F, u64 pos, u64 n, const QueryFields& f) {
+    if (pos >= n || f.ts == 0 || f.ts < F.ts_min || f.ts > F.ts_max) return false;
+    const bool side = (F.debits && f.dlo == F.id_lo && f.dhi == F.id_hi) || (F.credits && f.clo == F.id_lo && f.chi == F.id_hi);
+    if (!side) return false;
+    const u64* idw = (const u64*)&T.xlog[pos];
+    const u64 lo = idw[0], hi = idw[1];
+    if (tb_id_reserved(lo, hi)) return false;
+    return tb_transfer_find(T, lo, hi) == (u32)pos;
+}
+
+template <bool COOP>
+__global__ __launch_bounds__(QUERY_THREADS) void tb_query_count(Tables T, QueryFilter F, u64 n, u32* counts, u64* mins,
+                                                                u64* maxs, u32* ordered) {
+    __shared__ __attribute__((aligned(16))) u64 s_chunks[COOP ? QUERY_WAVES * 192 * 2 : 2];
+    __shared__ u64 s_max[QUERY_WAVES], s_min[QUERY_WAVES];
+    __shared__ u32 s_cnt[QUERY_WAVES], s_bad[QUERY_WAVES];
+    const u64 tile0 = (u64)blockIdx.x * QUERY_THREADS;
+    const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const QueryFields f = tb_query_fields<COOP>(T, tile0, n, s_chunks);
+    const bool hit = tb_query_hit(T, F, tile0 + threadIdx.x, n, f);
+    // The largest matched timestamp at the lanes before this one: the wave's prefix maximum.
+    u64 incl = hit ? f.ts : 0;
+#pragma unroll
+    for (u32 off = 1; off < 64; off <<= 1) {
+        const u64 o = __shfl_up((unsigned long long)incl, off);
+        if (lane >= off && o > incl) incl = o;
+    }
+    u64 before = __shfl_up((unsigned long long)incl, 1);
+    if (lane == 0) before = 0;
+    u64 lo = hit ? f.ts : ~0ULL;
+#pragma unroll
+    for (u32 off = 32; off > 0; off >>= 1) {
+        const u64 o = __shfl_xor((unsigned long long)lo, off);
+        if (o < lo) lo = o;
+    }
+    const u64 m = __ballot(hit);
+    if (lane == 63) s_max[wave] = incl;
+    if (lane == 0) {
+        s_min[wave] = lo;
+        s_cnt[wave] = __popcll(m);
+    }
+    __syncthreads();
+    for (u32 w = 0; w < wave; w++) before = max(before, s_max[w]);
+    const u64 bad = __ballot(hit && f.ts <= before);
+    if (lane == 0) s_bad[wave] = bad != 0;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        u32 c = 0, b = 0;
+        u64 mn = ~0ULL, mx = 0;
+        for (u32 w = 0; w < QUERY_WAVES; w++) {
+            c += s_cnt[w];
+            b |= s_bad[w];
+            mn = min(mn, s_min[w]);
+            mx = max(mx, s_max[w]);
+        }
+        counts[blockIdx.x] = c;
+        mins[blockIdx.x] = mn;
+        maxs[blockIdx.x] = mx;
+        ordered[blockIdx.x] = !b;
+    }
+}
+
+// One workgroup, each thread a run of tiles (tb_delta_scan_blocks' shape): base[k] = matches before
+// tile k, res[0] = the total, res[1] = 1 when the matches are in timestamp order over the whole log.
+__global__ __launch_bounds__(1024) void tb_query_scan(const u32* counts, const u64* mins, const u64* maxs, const u32* ordered,
+                                                      u64 nblocks, u64* base, u64* res) {
+    __shared__ u32 s_wave[1024 / 64];
+    __shared__ u64 s_wmax[1024 / 64];
+    const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const u64 per = (nblocks + 1023) / 1024;
+    const u64 k0 = min(nblocks, (u64)threadIdx.x * per), k1 = min(nblocks, k0 + per);
+    u32 local = 0;
+    u64 lmax = 0;
+    for (u64 k = k0; k < k1; k++) {
+        local += counts[k];
+        if (counts[k]) lmax = max(lmax, maxs[k]);
+    }
+    u32 all;
+    u64 run = tb_block_excl_sum(local, s_wave, &all);
+    // The largest matched timestamp in the runs before this thread's.
+    u64 incl = lmax;
+#pragma unroll
+    for (u32 off = 1; off < 64; off <<= 1) {
+        const u64 o = __shfl_up((unsigned long long)incl, off);
+        if (lane >= off && o > incl) incl = o;
+    }
+    u64 seen = __shfl_up((unsigned long long)incl, 1);
+    if (lane == 0) seen = 0;
+    if (lane == 63) s_wmax[wave] = incl;
+    __syncthreads();
+    for (u32 w = 0; w < wave; w++) seen = max(seen, s_wmax[w]);
+    int bad = 0;
+    for (u64 k = k0; k < k1; k++) {
+        base[k] = run;
+        run += counts[k];
+        if (counts[k]) {
+            bad |= !ordered[k] || mins[k] <= seen;
+            seen = max(seen, maxs[k]);
+        }
+    }
+    bad = __syncthreads_or(bad);
+    if (threadIdx.x == 0) {
+        res[0] = all;
+        res[1] = !bad;
+    }
+}
+
+// The lane's rank among its tile's matches.
+__device__ static inline u32 tb_query_tile_rank(bool hit, u32* s_cnt) {
+    const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const u64 m = __ballot(hit);
+    if (lane == 0) s_cnt[wave] = __popcll(m);
+    __syncthreads();
+    u32 r = __popcll(m & ((1ULL << lane) - 1));
+    for (u32 w = 0; w < wave; w++) r += s_cnt[w];
+    return r;
+}
+
+// Ordered log: rank = position among the matches = position by timestamp.  The first k ranks (the
+// last k under `reversed`, newest first) write their whole record to out[0, k).
+__global__ __launch_bounds__(QUERY_THREADS) void tb_query_scatter(Tables T, QueryFilter F, u64 n, const u32* counts,
+                                                                  const u64* base, const u64* res, u32 k, u32 reversed,
+                                                                  u8* out) {
+    __shared__ u32 s_cnt[QUERY_WAVES];
+    const u64 total = res[0], b0 = base[blockIdx.x], c = counts[blockIdx.x];
+    const u64 kk = min((u64)k, total), lo = reversed ? total - kk : 0, hi = lo + kk;
+    if (!res[1] || c == 0 || b0 >= hi || b0 + c <= lo) return;  // the whole workgroup alike
+    const u64 pos = (u64)blockIdx.x * QUERY_THREADS + threadIdx.x;
+    const QueryFields f = tb_query_fields<false>(T, (u64)blockIdx.x * QUERY_THREADS, n, nullptr);
+    const bool hit = tb_query_hit(T, F, pos, n, f);
+    const u64 rank = b0 + tb_query_tile_rank(hit, s_cnt);
+    if (!hit || rank < lo || rank >= hi) return;
+    const u64 dst = reversed ? total - 1 - rank : rank;
+    if (dst < k) *(Transfer*)(out + dst * 128) = T.xlog[pos];
+}
+
+// Unordered log, one round: the matches of tiles [wg0, wg0 + gridDim.x) as {timestamp, position}
+// keys, in log order from keys[0]; the host chose the range so that they fit keys_cap.
+__global__ __launch_bounds__(QUERY_THREADS) void tb_query_keys(Tables T, QueryFilter F, u64 n, u64 wg0, const u32* counts,
+                                                               const u64* base, u64* keys, u64 keys_cap) {
+    __shared__ u32 s_cnt[QUERY_WAVES];
+    const u64 b = wg0 + blockIdx.x;
+    if (counts[b] == 0) return;
+    const u64 pos = b * QUERY_THREADS + threadIdx.x;
+    const QueryFields f = tb_query_fields<false>(T, b * QUERY_THREADS, n, nullptr);
+    const bool hit = tb_query_hit(T, F, pos, n, f);
+    const u64 rank = base[b] - base[wg0] + tb_query_tile_rank(hit, s_cnt);
+    if (hit && rank < keys_cap) {
+        keys[2 * rank] = f.ts;
+        keys[2 * rank + 1] = pos;
+    }
+}
+
+// The records at m chosen log positions, in that order.
+__global__ __launch_bounds__(QUERY_THREADS) void tb_query_gather(Tables T, const u64* positions, u32 m, u64 n, u8* out) {
+    const u32 i = blockIdx.x * QUERY_THREADS + threadIdx.x;
+    if (i >= m) return;
+    const u64 pos = positions[i];
+    if (pos < n) *(Transfer*)(out + (u64)i * 128) = T.xlog[pos];
+}

@@ -1705,6 +1705,52 @@ static int node_lookup(TbNode* N, bool accounts, const void* input, u32 input_le
     return TBGPU_STATUS_OK;
 }
 
+// get_account_transfers on a node (tbgpu.h): a transfer lives on its home shard only, so every shard
+// scans its own log on its own device and stream, side by side (engine.hip query_enqueue), and the
+// host merges the shards' answers — each its first k by timestamp, its last k under `reversed` —
+// under the limit, summing the matches.
+static int node_get_account_transfers(TbNode* N, const QueryFilter& F, bool valid, u32 k, bool reversed, u8* out,
+                                      tbgpu_query_result* result) {
+    result->complete = 1;
+    for (u32 d = 0; d < N->world; d++) {
+        if (N->D[d].E->evicted_total) result->complete = 0;
+    }
+    if (!valid) return TBGPU_STATUS_OK;
+    for (u32 d = 0; d < N->world; d++) {
+        const int st = query_enqueue(N->D[d].E, F, k, reversed);
+        if (st) return st;
+    }
+    std::vector<std::vector<u8>> recs(N->world);
+    std::vector<u32> cnt(N->world, 0), at(N->world, 0);
+    int status = TBGPU_STATUS_OK;
+    for (u32 d = 0; d < N->world; d++) {  // every shard is waited for, whatever an earlier one returned
+        recs[d].resize((u64)std::max<u32>(k, 1) * 128);
+        u64 m = 0;
+        const int st = query_collect(N->D[d].E, recs[d].data(), &cnt[d], &m);
+        if (st && status == TBGPU_STATUS_OK) status = st;
+        result->matched += m;
+    }
+    if (status) {
+        result->matched = 0;
+        return status;
+    }
+    u32 w = 0;
+    for (; w < k; w++) {
+        u32 pick = N->world;
+        u64 best = 0;
+        for (u32 d = 0; d < N->world; d++) {
+            if (at[d] == cnt[d]) continue;
+            const u64 ts = *(const u64*)&recs[d][(u64)at[d] * 128 + 120];
+            if (pick == N->world || (reversed ? ts > best : ts < best)) pick = d, best = ts;
+        }
+        if (pick == N->world) break;
+        memcpy(out + (u64)w * 128, &recs[pick][(u64)at[pick] * 128], 128);
+        at[pick]++;
+    }
+    result->count = w;
+    return TBGPU_STATUS_OK;
+}
+
 // -- the tbgpu.h entry points of a node engine --------------------------------------------------------
 
 static int node_api_init(const tbgpu_config* config, tbgpu_t** out) {

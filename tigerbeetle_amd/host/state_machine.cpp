@@ -280,6 +280,13 @@ void StateMachine::checkpoint(const Callback& callback) {
     callback(*this);
 }
 
+tbgpu_query_result StateMachine::get_account_transfers(const tbgpu_account_filter& filter, void* out,
+                                                       uint32_t out_cap_records) {
+    tbgpu_query_result r{};
+    check(tbgpu_get_account_transfers(engine_, &filter, out, out_cap_records, &r), "get_account_transfers");
+    return r;
+}
+
 void StateMachine::test_set_balances(u128 id, u128 dp, u128 dpost, u128 cp, u128 cpost) {
     const uint64_t b[8] = {(uint64_t)dp, (uint64_t)(dp >> 64), (uint64_t)dpost, (uint64_t)(dpost >> 64),
                            (uint64_t)cp, (uint64_t)(cp >> 64), (uint64_t)cpost, (uint64_t)(cpost >> 64)};

@@ -227,6 +227,13 @@ public:
     // init): otherwise the first bar's compact does.
     void reserve_write_back();
 
+    // The account-filter query (tbgpu_get_account_transfers; no operation number in the reference's
+    // enum, so not a commit): the resident transfers that touched filter.account_id, by timestamp
+    // (newest first under TBGPU_FILTER_REVERSED), at most filter.limit and one message body, written
+    // to `out` (room for out_cap_records 128-B records).  An invalid filter matches nothing.
+    // result.complete == 0: the engine has evicted transfers, and the caller merges with its forest.
+    tbgpu_query_result get_account_transfers(const tbgpu_account_filter& filter, void* out, uint32_t out_cap_records);
+
     // Test-only: the table harness `setup` action (state_machine.zig:1398-1407).
     void test_set_balances(u128 account_id, u128 debits_pending, u128 debits_posted, u128 credits_pending,
                            u128 credits_posted);

@@ -2,6 +2,7 @@
 // mirror (tb::StateMachine) on the GPU engine.
 //
 //   tb_table_runner <tests/golden/state_machine_tables.txt> [device]
+//   tb_table_runner --query <prepares.bin> <answer.bin> [device]     (run_query below)
 //
 // The fixture holds the 18 check() tables of src/state_machine.zig:1531-2074 verbatim.  Row DSL:
 // src/testing/table.zig:8-100 (tokens, `_` defaults, letter labels, `-N` = maxInt - N); action
@@ -292,12 +293,68 @@ std::string run_table(tb::StateMachine& sm, const std::string& text) {
     return "";
 }
 
+// --query: prepares then one account filter through tb::StateMachine, for tests/test_gpu_query_cpp.py
+// to compare with the Python mirror's answer.  <prepares.bin>: {u64 timestamp, u32 operation, u32
+// body bytes, body} per prepare, then {0, 0, 64, a tbgpu_account_filter}.  <answer.bin> receives the
+// 16-byte tbgpu_query_result and the records.
+int run_query(tb::StateMachine& sm, const char* in_path, const char* out_path) {
+    std::ifstream in(in_path, std::ios::binary);
+    if (!in) {
+        fprintf(stderr, "cannot open %s\n", in_path);
+        return 2;
+    }
+    std::vector<uint8_t> body, reply;
+    uint64_t op = 0;
+    for (;;) {
+        uint64_t ts = 0;
+        uint32_t operation = 0, len = 0;
+        in.read((char*)&ts, 8).read((char*)&operation, 4).read((char*)&len, 4);
+        body.resize(len);
+        if (!in || !in.read((char*)body.data(), len)) {
+            fprintf(stderr, "%s: truncated\n", in_path);
+            return 2;
+        }
+        if (operation == 0) break;
+        reply.resize((size_t)len / 128 * 8 + 8);
+        sm.commit(0, ++op, ts, (tb::Operation)operation, body.data(), body.size(), reply.data());
+    }
+    tbgpu_account_filter f;
+    if (body.size() != sizeof(f)) {
+        fprintf(stderr, "%s: a filter is %zu bytes\n", in_path, sizeof(f));
+        return 2;
+    }
+    memcpy(&f, body.data(), sizeof(f));
+    std::vector<uint8_t> out((size_t)TBGPU_BATCH_EVENTS_MAX * 128);
+    const tbgpu_query_result r = sm.get_account_transfers(f, out.data(), TBGPU_BATCH_EVENTS_MAX);
+    std::ofstream o(out_path, std::ios::binary);
+    o.write((const char*)&r, sizeof(r)).write((const char*)out.data(), (size_t)r.count * 128);
+    printf("query: %u of %llu records, complete %u\n", r.count, (unsigned long long)r.matched, r.complete);
+    return o ? 0 : 2;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
-    if (argc < 2) {
-        fprintf(stderr, "usage: %s <state_machine_tables.txt> [device]\n", argv[0]);
+    const bool query = argc > 1 && std::string(argv[1]) == "--query";
+    if (argc < 2 || (query && argc < 4)) {
+        fprintf(stderr, "usage: %s <state_machine_tables.txt> [device]\n       %s --query <prepares.bin> <answer.bin> [device]\n",
+                argv[0], argv[0]);
         return 2;
+    }
+    if (query) {
+        tb::Options o;
+        o.accounts_max = 4096;
+        o.transfers_max = 1 << 14;
+        o.pass_events_max = 8192 * 4;
+        o.pass_batches_max = 64;
+        o.device = argc > 4 ? atoi(argv[4]) : 0;
+        try {
+            tb::StateMachine sm(o);
+            return run_query(sm, argv[2], argv[3]);
+        } catch (const std::exception& e) {
+            fprintf(stderr, "query failed: %s\n", e.what());
+            return 255;
+        }
     }
     std::ifstream in(argv[1]);
     if (!in) {

@@ -22,7 +22,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from .types import ACCOUNT_DTYPE, BATCH_MAX, TRANSFER_DTYPE, U64_MAX, Operation
+from .types import (ACCOUNT_DTYPE, ACCOUNT_FILTER_DTYPE, BATCH_MAX, FILTER_CREDITS, FILTER_DEBITS, FILTER_REVERSED,
+                    TRANSFER_DTYPE, U64_MAX, Operation)
 
 
 @dataclass
@@ -236,6 +237,38 @@ class Engine:
         _lib.check(self.lib.tbgpu_export_posted(self.h, out.ctypes.data, cap, ctypes.byref(n)))
         return out[:n.value]
 
+    # -- queries -----------------------------------------------------------------------------
+    def get_account_transfers(self, account_id, *, debits=True, credits=True, reversed=False, timestamp_min=0,
+                              timestamp_max=0, limit=8190, out_cap_records=None):
+        """The resident transfers that touched `account_id` (tbgpu_get_account_transfers): by
+        timestamp ascending, newest first under `reversed`, at most `limit` (and one message body).
+        Returns (records ndarray of TRANSFER_DTYPE, matched, complete): `matched` counts every match
+        before the limit; `complete` is False once the engine has evicted transfers (the caller
+        merges with its forest).  An invalid filter matches nothing."""
+        f = np.zeros(1, dtype=ACCOUNT_FILTER_DTYPE)
+        f["account_id_lo"], f["account_id_hi"] = account_id & U64_MAX, account_id >> 64
+        f["timestamp_min"], f["timestamp_max"], f["limit"] = timestamp_min, timestamp_max, limit
+        f["flags"] = ((FILTER_DEBITS if debits else 0) | (FILTER_CREDITS if credits else 0)
+                      | (FILTER_REVERSED if reversed else 0))
+        return self.get_account_transfers_raw(f.tobytes(), out_cap_records)
+
+    def get_account_transfers_raw(self, filter_bytes, out_cap_records=None):
+        """The same query from the 64 bytes of a tbgpu_account_filter (ACCOUNT_FILTER_DTYPE)."""
+        filter_bytes = bytes(filter_bytes)
+        if len(filter_bytes) != ACCOUNT_FILTER_DTYPE.itemsize:
+            raise ValueError("an account filter is %d bytes" % ACCOUNT_FILTER_DTYPE.itemsize)
+        limit = int(np.frombuffer(filter_bytes, dtype=ACCOUNT_FILTER_DTYPE)["limit"][0])
+        cap = min(limit, BATCH_MAX) if out_cap_records is None else int(out_cap_records)
+        out = np.zeros(max(cap, 1), dtype=TRANSFER_DTYPE)
+        res = _lib.tbgpu_query_result()
+        src = ctypes.create_string_buffer(filter_bytes, len(filter_bytes))
+        _lib.check(self.lib.tbgpu_get_account_transfers(self.h, src, out.ctypes.data, cap, ctypes.byref(res)))
+        return out[:res.count], int(res.matched), bool(res.complete)
+
+    def query_keys_max(self, keys):
+        """Keys per round of a query over a log out of timestamp order (tbgpu_bench_query_keys_max)."""
+        _lib.check(self.lib.tbgpu_bench_query_keys_max(self.h, int(keys)))
+
     def stats(self):
         s = _lib.tbgpu_stats()
         _lib.check(self.lib.tbgpu_get_stats(self.h, ctypes.byref(s)))
@@ -447,6 +480,10 @@ class Engine:
         array = np.ascontiguousarray(array)
         _lib.check(self.lib.tbgpu_copy_to_device(self.h, ptr, array.ctypes.data, array.nbytes))
 
+    def copy_device_async(self, dst_dev, src_dev, nbytes):
+        """Device to device on the engine's stream (tbgpu_copy_device_async): time it with markers."""
+        _lib.check(self.lib.tbgpu_copy_device_async(self.h, dst_dev, src_dev, int(nbytes)))
+
     def generate_accounts(self, out_dev, first, count, seed=42, limit_permille=0, account_count=0, hot_limited=0):
         """hot_limited > 0 (the hottest Zipf ranks get a limit flag too) needs account_count."""
         w = _lib.tbgpu_workload(seed, account_count, 0, limit_permille, 0.0, hot_limited, 0)
@@ -529,6 +566,11 @@ class StateMachine:
         reply = self.engine.commit(int(operation), timestamp, body)
         self.commit_timestamp = self.engine.commit_timestamp
         return reply
+
+    def get_account_transfers(self, account_id, **filter):
+        """The account-filter query (Engine.get_account_transfers): a read, no operation number in
+        the reference's enum, so it does not go through commit."""
+        return self.engine.get_account_transfers(account_id, **filter)
 
     def compact(self, callback, op):
         del op

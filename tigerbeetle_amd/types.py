@@ -101,6 +101,13 @@ RESULT_DTYPE = np.dtype([("index", "<u4"), ("result", "<u4")])
 
 assert ACCOUNT_DTYPE.itemsize == 128 and TRANSFER_DTYPE.itemsize == 128 and RESULT_DTYPE.itemsize == 8
 
+# tbgpu_account_filter (include/tbgpu.h tbgpu_get_account_transfers): 64 bytes, no padding.
+ACCOUNT_FILTER_DTYPE = np.dtype(
+    _u128("account_id") + [("timestamp_min", "<u8"), ("timestamp_max", "<u8"), ("limit", "<u4"), ("flags", "<u4"),
+                           ("reserved", "u1", (24,))])
+assert ACCOUNT_FILTER_DTYPE.itemsize == 64
+FILTER_DEBITS, FILTER_CREDITS, FILTER_REVERSED = 1, 2, 4
+
 ACCOUNT_FIELDS = ("id", "debits_pending", "debits_posted", "credits_pending", "credits_posted",
                   "user_data_128", "user_data_64", "user_data_32", "reserved", "ledger", "code",
                   "flags", "timestamp")
