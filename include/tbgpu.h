@@ -17,6 +17,8 @@
  *   execute_lookup_accounts / _transfers (:700-736)        tbgpu_commit with operation 130 / 131
  *   the transfers groove's account-id index trees          tbgpu_get_account_transfers (no reference
  *     (:140-178; no reference operation reads them)          operation: specified below)
+ *   both grooves' user_data / ledger / code / timestamp     tbgpu_query_transfers, tbgpu_query_accounts
+ *     index trees (:103-169; likewise unread)                (likewise)
  *   `setup` action of the table tests (:1398-1407)         tbgpu_test_set_balances (test only)
  *   StateMachine.commit_timestamp field (:251)             tbgpu_commit_timestamp
  *
@@ -319,6 +321,56 @@ typedef struct tbgpu_query_result {
 
 int tbgpu_get_account_transfers(tbgpu_t* engine, const tbgpu_account_filter* filter,
                                 void* out, uint32_t out_cap_records, tbgpu_query_result* result);
+
+/* query_transfers / query_accounts: which transfers, or accounts, carry these field values.  The
+ * reference maintains the user_data_128 / user_data_64 / user_data_32 / ledger / code / timestamp
+ * index trees of both grooves (src/state_machine.zig:103-169) and no operation reads them; later
+ * references read them through a QueryFilter.  Entry points of their own, as above,
+ * and this comment is their specification.
+ *   What matches: every non-zero field of the filter equals the object's stored field (AND; a 128-bit
+ *     field compares both words), and the object's timestamp lies in [timestamp_min, timestamp_max]
+ *     (0 leaves that end open).  A filter with every field zero is valid and matches every object in
+ *     the window.
+ *     Transfers: liveness as for tbgpu_get_account_transfers — failed events, withdrawn speculative
+ *     records and rolled-back chain members never match; post / void records match on the bytes they
+ *     store (src/state_machine.zig:971-985).
+ *     Accounts: a live slot of the account table (a non-zero timestamp, an id that is not reserved).
+ *   What is returned: the first min(limit, out_cap_records, TBGPU_BATCH_EVENTS_MAX) matches by timestamp
+ *     ascending, or descending from the newest under REVERSED — whole 128-byte records, the bytes
+ *     lookup_transfers / lookup_accounts return for the same ids; for accounts that is the current
+ *     balances.  `matched` counts every match before the limit.
+ *   complete: transfers, the rule above (no transfer was ever evicted, on any shard); accounts, always
+ *     1 (accounts are never evicted).  An engine that was loaded lazily holds only what was loaded:
+ *     INTEGRATION.md.
+ *   Invalid filters are never a status: timestamp_min or timestamp_max 2^64-1, a non-zero
+ *     timestamp_max below timestamp_min, limit 0, an unknown flag bit, a non-zero reserved byte — each
+ *     returns TBGPU_STATUS_OK with count = matched = 0.  A NULL filter, out or result is
+ *     TBGPU_STATUS_INVALID.
+ *   The call contract of tbgpu_get_account_transfers: synchronous, drains a pending
+ *     tbgpu_commit_device_async first, changes nothing, works on a stopped engine, allocates nothing,
+ *     legal beside an asynchronous write-back.
+ *   A node engine: transfers as above.  An account is answered by its owner shard only (a home's
+ *     imported copies of foreign accounts and the sequencer's loaded copies never match), so it
+ *     appears once, with the owner's balances; the host merges the shards' answers by timestamp. */
+#define TBGPU_QUERY_REVERSED (1u << 0)   /* newest first */
+
+typedef struct tbgpu_query_filter {      /* 64 bytes, little-endian, no padding */
+    uint64_t user_data_128_lo, user_data_128_hi;   /* 0 (both words) = not filtered */
+    uint64_t user_data_64;                         /* 0 = not filtered */
+    uint32_t user_data_32;                         /* 0 = not filtered */
+    uint32_t ledger;                               /* 0 = not filtered */
+    uint16_t code;                                 /* 0 = not filtered */
+    uint8_t  reserved[6];                          /* must be zero */
+    uint64_t timestamp_min;                        /* inclusive; 0 = open */
+    uint64_t timestamp_max;                        /* inclusive; 0 = open */
+    uint32_t limit;
+    uint32_t flags;
+} tbgpu_query_filter;
+
+int tbgpu_query_transfers(tbgpu_t* engine, const tbgpu_query_filter* filter, void* out, uint32_t out_cap_records,
+                          tbgpu_query_result* result);
+int tbgpu_query_accounts(tbgpu_t* engine, const tbgpu_query_filter* filter, void* out, uint32_t out_cap_records,
+                         tbgpu_query_result* result);
 
 /* The replica writes StateMachine.commit_timestamp itself: the header timestamp after every commit
  * (src/vsr/replica.zig:3664-3665) and the checkpoint's value on open / state sync.  The wrapper

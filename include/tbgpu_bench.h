@@ -69,6 +69,10 @@ int tbgpu_bench_flow_launch(tbgpu_t* engine, uint32_t workgroups);
  * Exact either way. */
 int tbgpu_bench_query_keys_max(tbgpu_t* engine, uint32_t keys);
 
+/* Table scans the radix select of the last tbgpu_query_accounts made (0: at most `limit` matches, or
+ * one timestamp); on a node engine, its first shard's.  For tools/gpu/query_scan.py. */
+int tbgpu_bench_query_select_scans(tbgpu_t* engine, uint64_t* scans);
+
 /* The memory-access mix of tb_transfers_validate without its logic, on scratch buffers sized like
  * this engine's account table and transfer index, for `transfers` events (one pass): mean ms of
  * {stream, probe, cas, stream+probe, stream+cas, probe+cas, all three} (k_workload.h).  The

@@ -44,6 +44,13 @@ class tbgpu_account_filter(ctypes.Structure):
                 ("limit", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint8 * 24)]
 
 
+class tbgpu_query_filter(ctypes.Structure):
+    _fields_ = [("user_data_128_lo", ctypes.c_uint64), ("user_data_128_hi", ctypes.c_uint64),
+                ("user_data_64", ctypes.c_uint64), ("user_data_32", ctypes.c_uint32), ("ledger", ctypes.c_uint32),
+                ("code", ctypes.c_uint16), ("reserved", ctypes.c_uint8 * 6), ("timestamp_min", ctypes.c_uint64),
+                ("timestamp_max", ctypes.c_uint64), ("limit", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
 class tbgpu_query_result(ctypes.Structure):
     _fields_ = [("count", ctypes.c_uint32), ("complete", ctypes.c_uint32), ("matched", ctypes.c_uint64)]
 
@@ -167,7 +174,10 @@ SIGNATURES = [
     ("tbgpu_export_transfers", ctypes.c_int, [_P, _P, _U64, ctypes.POINTER(_U64)]),
     ("tbgpu_export_posted", ctypes.c_int, [_P, _P, _U64, ctypes.POINTER(_U64)]),
     ("tbgpu_get_account_transfers", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
+    ("tbgpu_query_transfers", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
+    ("tbgpu_query_accounts", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_bench_query_keys_max", ctypes.c_int, [_P, _U32]),
+    ("tbgpu_bench_query_select_scans", ctypes.c_int, [_P, ctypes.POINTER(_U64)]),
     ("tbgpu_get_stats", ctypes.c_int, [_P, ctypes.POINTER(tbgpu_stats)]),
     ("tbgpu_reset_stats", None, [_P]),
     ("tbgpu_last_error", ctypes.c_char_p, []),

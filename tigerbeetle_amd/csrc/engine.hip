@@ -33,6 +33,7 @@
 #include "k_workload.h"
 #include "k_evict.h"
 #include "k_query.h"
+#include "k_query_filter.h"
 #include "checksum.h"
 
 static thread_local std::string g_err;
@@ -154,8 +155,9 @@ struct WbBufs {
     std::vector<u64> ids_inflight;
 };
 
-// tbgpu_get_account_transfers (k_query.h): every buffer made at tbgpu_init, none shared with the
-// write-back or the lookups (a write-back may be in flight beside a query).
+// tbgpu_get_account_transfers and tbgpu_query_transfers (k_query.h; one scan, two predicates): every
+// buffer made at tbgpu_init, none shared with the write-back or the lookups (a write-back may be in
+// flight beside a query).
 #define QUERY_KEYS_CAP (1u << 16)  // {timestamp, position} keys of one round of the unordered path
 struct QueryBufs {
     u64 nb_cap = 0;            // tiles of QUERY_THREADS log positions in the whole log
@@ -174,10 +176,28 @@ struct QueryBufs {
     bool coop = false;         // tb_query_count's load shape (TBGPU_QUERY_COOP=1: cooperative 16-B chunks)
     // One query in flight between query_enqueue and query_collect.
     QueryFilter F{};
+    QueryFieldFilter FF{};   // by_fields: tbgpu_query_transfers' predicate instead
+    bool by_fields = false;
     u32 k = 0;
     bool reversed = false;
     u64 n = 0;
 };
+
+// tbgpu_query_accounts (k_query_filter.h): O(slots / 256 + histogram + k) device memory, made at
+// tbgpu_init and shared with nothing.
+struct AccountQueryBufs {
+    u64 nb = 0;               // tiles of QUERY_THREADS slots in the account table
+    u32* d_counts = nullptr;  // [nb] matches per tile
+    u64* d_mins = nullptr;    // [nb] their smallest timestamp
+    u64* d_maxs = nullptr;    // [nb] ... and largest
+    u64* d_state = nullptr;   // [QA_WORDS], then the select's histograms: u32 [QA_PASSES][QA_BINS]
+    u64* h_state = nullptr;   // pinned mirror of the QA_WORDS
+    u64* d_keys = nullptr;    // [BATCH_EVENTS_MAX][2] {value, slot} of the selected matches
+    u8* d_out = nullptr;      // [BATCH_EVENTS_MAX] the answer's records
+    u32 k = 0;                // one query in flight between account_query_enqueue and _collect
+    u64 last_scans = 0;       // select passes of the last query (tbgpu_bench_query_select_scans)
+};
+#define QA_STATE_BYTES ((u64)QA_WORDS * 8 + (u64)QA_PASSES * QA_BINS * 4)
 
 struct tbgpu {
     tbgpu_config cfg{};
@@ -325,6 +345,7 @@ struct tbgpu {
     u64* r_words = nullptr;
     u64* r_meta = nullptr;    // device [meta_cap + 1] offsets then [meta_cap] timestamps
     u64* h_rmeta = nullptr;   // pinned mirror
+    AccountQueryBufs qa;
 };
 
 // The write-back snapshot as a balance view (its two planes, like T.bal).
@@ -552,8 +573,10 @@ static int node_fetch(TbNode* N, bool accounts, const u64* ids, u32 n, u8* out, 
 static int node_api_accounts_in(TbNode* N, const void* records, u32 n, bool load);
 static int node_api_transfers_in(TbNode* N, const void* records, const u8* state, u32 n, bool load);
 static int node_api_set_commit_timestamp(TbNode* N, u64 timestamp);
-static int node_get_account_transfers(TbNode* N, const QueryFilter& F, bool valid, u32 k, bool reversed, u8* out,
-                                      tbgpu_query_result* result);
+template <typename F>
+static int node_query_transfers(TbNode* N, const F& flt, bool valid, u32 k, bool reversed, u8* out, tbgpu_query_result* result);
+static int node_query_accounts(TbNode* N, const QueryFieldFilter& F, bool valid, u32 k, bool reversed, u8* out,
+                               tbgpu_query_result* result);
 
 extern "C" int tbgpu_init(const tbgpu_config* config, tbgpu_t** out) {
     if (config && config->device_count > 1) return node_api_init(config, out);
@@ -844,6 +867,17 @@ extern "C" int tbgpu_init(const tbgpu_config* config, tbgpu_t** out) {
         E->event_pool.resize(PROF_EVENTS);
         for (auto& ev : E->event_pool) INIT_CK(tbEventCreate(&ev));
     }
+    {  // tbgpu_query_accounts: per-tile counts and bounds, the select's state and histograms, keys, the answer
+        AccountQueryBufs& A = E->qa;
+        A.nb = (E->account_cap + QUERY_THREADS - 1) / QUERY_THREADS;
+        INIT_CK(tbMalloc(&A.d_counts, A.nb * 4));
+        INIT_CK(tbMalloc(&A.d_mins, A.nb * 8));
+        INIT_CK(tbMalloc(&A.d_maxs, A.nb * 8));
+        INIT_CK(tbMalloc(&A.d_state, QA_STATE_BYTES));
+        INIT_CK(tbHostMalloc(&A.h_state, (u64)QA_WORDS * 8, hipHostMallocDefault));
+        INIT_CK(tbMalloc(&A.d_keys, (u64)BATCH_EVENTS_MAX * 16));
+        INIT_CK(tbMalloc(&A.d_out, (u64)BATCH_EVENTS_MAX * 128));
+    }
 #undef INIT_CK
     st = engine_clear(E);
     if (st == TBGPU_STATUS_OK && E->flow_ok) st = residency_probe(E, flow_grid(E));
@@ -873,6 +907,7 @@ extern "C" void tbgpu_deinit(tbgpu_t* E) {
                     E->wb.d_bc, E->wb.d_base, E->wb.d_out, E->wb.d_ids, E->wb.d_pv, E->wb.d_pairs, E->wb.d_hids,
                     E->wb.d_acc, E->wb.d_before, E->wb.d_slots, E->wb.d_cap, E->wb.d_cnt,
                     E->q.d_counts, E->q.d_mins, E->q.d_maxs, E->q.d_ordered, E->q.d_base, E->q.d_res, E->q.d_out, E->q.d_keys,
+                    E->qa.d_counts, E->qa.d_mins, E->qa.d_maxs, E->qa.d_state, E->qa.d_keys, E->qa.d_out,
                     E->r_block_counts, E->r_words, E->r_meta, E->resolve_slow, E->leg_w, E->leg_off, E->leg_tot,
                     E->F.f_pe, E->F.f_batch, E->F.f_len, E->F.need, E->F.nsucc, E->F.queue, E->F.uflags, E->F.nacct, E->F.rpos, E->F.succ,
                     E->F.run, E->F.keys[0], E->F.keys[1], E->F.vals[0], E->F.vals[1], E->F.hist, E->F.words, E->F.undo,
@@ -895,7 +930,7 @@ extern "C" void tbgpu_deinit(tbgpu_t* E) {
     if (E->h_rmeta) (void)hipHostFree(E->h_rmeta);
     if (E->h_kclock) (void)hipHostFree(E->h_kclock);
     if (E->h_pub) (void)hipHostFree(E->h_pub);
-    for (u64* p : {E->q.h_res, E->q.h_keys, E->q.h_base}) if (p) (void)hipHostFree(p);
+    for (u64* p : {E->q.h_res, E->q.h_keys, E->q.h_base, E->qa.h_state}) if (p) (void)hipHostFree(p);
     if (E->wb.h_cnt) (void)hipHostFree(E->wb.h_cnt);
     if (E->wb.stream) {
         (void)hipStreamSynchronize(E->wb.stream);
@@ -3325,14 +3360,19 @@ extern "C" int tbgpu_set_commit_timestamp(tbgpu_t* E, uint64_t timestamp) {
 // {total, ordered} word); query_collect waits, copies the answer's records, and runs the exact path
 // of a log out of timestamp order when the scan found one.  The stream is drained before (a pending
 // tbgpu_commit_device_async), so log_next is the log's end and nothing writes beside the scan.
-static int query_enqueue(tbgpu* E, const QueryFilter& F, u32 k, bool reversed) {
+static void query_keep_filter(QueryBufs& Q, const QueryFilter& F) { Q.F = F, Q.by_fields = false; }
+static void query_keep_filter(QueryBufs& Q, const QueryFieldFilter& F) { Q.FF = F, Q.by_fields = true; }
+
+template <typename FILTER>
+static int query_enqueue(tbgpu* E, const FILTER& F, u32 k, bool reversed) {
+    constexpr bool by_account = std::is_same<FILTER, QueryFilter>::value;
     QueryBufs& Q = E->q;
     HIPCK(hipSetDevice(E->device));
     if (E->pending) {
         int st = engine_sync(E);
         if (st) return st;
     }
-    Q.F = F;
+    query_keep_filter(Q, F);
     Q.k = k;
     Q.reversed = reversed;
     Q.n = E->log_next;
@@ -3340,17 +3380,22 @@ static int query_enqueue(tbgpu* E, const QueryFilter& F, u32 k, bool reversed) {
     const u64 nb = (Q.n + QUERY_THREADS - 1) / QUERY_THREADS;
     if (nb == 0) return TBGPU_STATUS_OK;
     if (nb > Q.nb_cap) return fail(TBGPU_STATUS_PANIC, "query: the log's end %llu is past its capacity", (unsigned long long)Q.n);
-    if (Q.coop) {
-        hipLaunchKernelGGL(tb_query_count<true>, dim3((unsigned)nb), dim3(QUERY_THREADS), 0, E->stream, E->T, F, Q.n,
-                           Q.d_counts, Q.d_mins, Q.d_maxs, Q.d_ordered);
+    if constexpr (by_account) {
+        if (Q.coop) {
+            hipLaunchKernelGGL((tb_query_count<true, QueryFilter>), dim3((unsigned)nb), dim3(QUERY_THREADS), 0, E->stream, E->T,
+                               F, Q.n, Q.d_counts, Q.d_mins, Q.d_maxs, Q.d_ordered);
+        } else {
+            hipLaunchKernelGGL((tb_query_count<false, QueryFilter>), dim3((unsigned)nb), dim3(QUERY_THREADS), 0, E->stream, E->T,
+                               F, Q.n, Q.d_counts, Q.d_mins, Q.d_maxs, Q.d_ordered);
+        }
     } else {
-        hipLaunchKernelGGL(tb_query_count<false>, dim3((unsigned)nb), dim3(QUERY_THREADS), 0, E->stream, E->T, F, Q.n,
+        hipLaunchKernelGGL((tb_query_count<false, FILTER>), dim3((unsigned)nb), dim3(QUERY_THREADS), 0, E->stream, E->T, F, Q.n,
                            Q.d_counts, Q.d_mins, Q.d_maxs, Q.d_ordered);
     }
     hipLaunchKernelGGL(tb_query_scan, dim3(1), dim3(1024), 0, E->stream, Q.d_counts, Q.d_mins, Q.d_maxs, Q.d_ordered, nb,
                        Q.d_base, Q.d_res);
-    hipLaunchKernelGGL(tb_query_scatter, dim3((unsigned)nb), dim3(QUERY_THREADS), 0, E->stream, E->T, F, Q.n, Q.d_counts,
-                       Q.d_base, Q.d_res, k, reversed ? 1u : 0u, Q.d_out);
+    hipLaunchKernelGGL(tb_query_scatter<FILTER>, dim3((unsigned)nb), dim3(QUERY_THREADS), 0, E->stream, E->T, F, Q.n,
+                       Q.d_counts, Q.d_base, Q.d_res, k, reversed ? 1u : 0u, Q.d_out);
     HIPCK(hipGetLastError());
     HIPCK(hipMemcpyAsync(Q.h_res, Q.d_res, 16, hipMemcpyDeviceToHost, E->stream));
     return TBGPU_STATUS_OK;
@@ -3393,8 +3438,13 @@ static int query_collect(tbgpu* E, u8* out, u32* count, u64* matched) {
             const u64 b1 = (u64)(std::upper_bound(Q.h_base + b0, Q.h_base + nb + 1, Q.h_base[b0] + Q.keys_max) - Q.h_base) - 1;
             const u64 keys = Q.h_base[b1] - Q.h_base[b0];
             if (b1 <= b0 || keys > Q.keys_max) return fail(TBGPU_STATUS_PANIC, "query: a round of %llu keys", (unsigned long long)keys);
-            hipLaunchKernelGGL(tb_query_keys, dim3((unsigned)(b1 - b0)), dim3(QUERY_THREADS), 0, E->stream, E->T, Q.F, Q.n, b0,
-                               Q.d_counts, Q.d_base, Q.d_keys, (u64)Q.keys_max);
+            if (Q.by_fields) {
+                hipLaunchKernelGGL(tb_query_keys<QueryFieldFilter>, dim3((unsigned)(b1 - b0)), dim3(QUERY_THREADS), 0, E->stream,
+                                   E->T, Q.FF, Q.n, b0, Q.d_counts, Q.d_base, Q.d_keys, (u64)Q.keys_max);
+            } else {
+                hipLaunchKernelGGL(tb_query_keys<QueryFilter>, dim3((unsigned)(b1 - b0)), dim3(QUERY_THREADS), 0, E->stream, E->T,
+                                   Q.F, Q.n, b0, Q.d_counts, Q.d_base, Q.d_keys, (u64)Q.keys_max);
+            }
             HIPCK(hipGetLastError());
             HIPCK(hipMemcpyAsync(Q.h_keys, Q.d_keys, keys * 16, hipMemcpyDeviceToHost, E->stream));
             HIPCK(hipStreamSynchronize(E->stream));
@@ -3447,7 +3497,7 @@ extern "C" int tbgpu_get_account_transfers(tbgpu_t* E, const tbgpu_account_filte
     const bool valid = query_filter_valid(filter);
     // One reply is one message body.
     const u32 k = std::min<u32>(std::min<u32>(filter->limit, out_cap_records), BATCH_EVENTS_MAX);
-    if (E->node) return node_get_account_transfers(E->node, F, valid, k, reversed, (u8*)out, result);
+    if (E->node) return node_query_transfers(E->node, F, valid, k, reversed, (u8*)out, result);
     result->complete = E->evicted_total == 0;
     if (!valid) return TBGPU_STATUS_OK;
     int st = query_enqueue(E, F, k, reversed);
@@ -3458,6 +3508,146 @@ extern "C" int tbgpu_get_account_transfers(tbgpu_t* E, const tbgpu_account_filte
     if (st) return st;
     result->count = count;
     result->matched = matched;
+    return TBGPU_STATUS_OK;
+}
+
+// ---- query_transfers / query_accounts (k_query.h, k_query_filter.h, include/tbgpu.h) --------------
+static bool query_fields_valid(const tbgpu_query_filter* f) {
+    if (f->timestamp_min == ~0ULL || f->timestamp_max == ~0ULL) return false;
+    if (f->timestamp_max != 0 && f->timestamp_max < f->timestamp_min) return false;
+    if (f->limit == 0) return false;
+    if (f->flags & ~TBGPU_QUERY_REVERSED) return false;
+    for (u8 b : f->reserved) if (b) return false;
+    return true;
+}
+
+static QueryFieldFilter query_fields_of(const tbgpu_query_filter* f) {
+    QueryFieldFilter F{};
+    F.u128_lo = f->user_data_128_lo;
+    F.u128_hi = f->user_data_128_hi;
+    F.u64v = f->user_data_64;
+    F.u32v = f->user_data_32;
+    F.ledger = f->ledger;
+    F.code = f->code;
+    F.ts_min = f->timestamp_min;
+    F.ts_max = f->timestamp_max ? f->timestamp_max : ~0ULL;
+    return F;
+}
+
+extern "C" int tbgpu_query_transfers(tbgpu_t* E, const tbgpu_query_filter* filter, void* out, uint32_t out_cap_records,
+                                     tbgpu_query_result* result) {
+    API_ENTER(E, false);  // a read, as tbgpu_get_account_transfers
+    if (!filter || !out || !result) return fail(TBGPU_STATUS_INVALID, "query_transfers: a NULL filter, out or result");
+    result->count = 0;
+    result->matched = 0;
+    result->complete = 0;
+    const QueryFieldFilter F = query_fields_of(filter);
+    const bool reversed = (filter->flags & TBGPU_QUERY_REVERSED) != 0;
+    const bool valid = query_fields_valid(filter);
+    const u32 k = std::min<u32>(std::min<u32>(filter->limit, out_cap_records), BATCH_EVENTS_MAX);
+    if (E->node) return node_query_transfers(E->node, F, valid, k, reversed, (u8*)out, result);
+    result->complete = E->evicted_total == 0;
+    if (!valid) return TBGPU_STATUS_OK;
+    int st = query_enqueue(E, F, k, reversed);
+    if (st) return st;
+    u32 count = 0;
+    u64 matched = 0;
+    st = query_collect(E, (u8*)out, &count, &matched);
+    if (st) return st;
+    result->count = count;
+    result->matched = matched;
+    return TBGPU_STATUS_OK;
+}
+
+// The account table in two halves, as the log scan: account_query_enqueue puts count -> scan -> the
+// select's passes -> collect -> emit on the engine stream, back to back (a pass that has nothing to
+// decide exits on the device); account_query_collect waits for the state words, then copies the
+// answer's records.  Nothing else crosses PCIe.  world != 0: a node shard answers for what it owns.
+static int account_query_enqueue(tbgpu* E, const QueryFieldFilter& F, u32 world, u32 self, u32 k, bool reversed) {
+    AccountQueryBufs& A = E->qa;
+    HIPCK(hipSetDevice(E->device));
+    if (E->pending) {
+        int st = engine_sync(E);
+        if (st) return st;
+    }
+    A.k = k;
+    QaPred P{};
+    P.f = F;
+    P.world = world;
+    P.self = self;
+    P.cold = F.wants_u128() || F.u64v || F.u32v;
+    const u64 cap = E->account_cap, nb = A.nb;
+    const u32 rev = reversed ? 1u : 0u;
+    const unsigned wide = (unsigned)((nb + QA_TILES - 1) / QA_TILES);
+    u32* hist = (u32*)(A.d_state + QA_WORDS);
+    HIPCK(hipMemsetAsync(A.d_state, 0, QA_STATE_BYTES, E->stream));
+    hipLaunchKernelGGL(tb_qa_count, dim3((unsigned)nb), dim3(QUERY_THREADS), 0, E->stream, E->T, P, cap, A.d_counts, A.d_mins,
+                       A.d_maxs);
+    hipLaunchKernelGGL(tb_qa_scan, dim3(1), dim3(1024), 0, E->stream, A.d_counts, A.d_mins, A.d_maxs, nb, k, A.d_state);
+    for (u32 pass = 0; pass < QA_PASSES; pass++) {
+        hipLaunchKernelGGL(tb_qa_hist, dim3(wide), dim3(QUERY_THREADS), 0, E->stream, E->T, P, cap, A.d_counts, nb, k, rev, pass,
+                           A.d_state, hist);
+        hipLaunchKernelGGL(tb_qa_pick, dim3(1), dim3(1024), 0, E->stream, k, pass, hist, A.d_state);
+    }
+    hipLaunchKernelGGL(tb_qa_collect, dim3(wide), dim3(QUERY_THREADS), 0, E->stream, E->T, P, cap, A.d_counts, nb, k, rev,
+                       A.d_state, A.d_keys);
+    hipLaunchKernelGGL(tb_qa_emit, dim3(std::max<u32>(1, (k + QA_EMIT_KEYS - 1) / QA_EMIT_KEYS)), dim3(QUERY_THREADS), 0,
+                       E->stream, E->T, cap, k, A.d_state, A.d_keys, A.d_out);
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpyAsync(A.h_state, A.d_state, (u64)QA_WORDS * 8, hipMemcpyDeviceToHost, E->stream));
+    return TBGPU_STATUS_OK;
+}
+
+static int account_query_collect(tbgpu* E, u8* out, u32* count, u64* matched) {
+    AccountQueryBufs& A = E->qa;
+    *count = 0;
+    *matched = 0;
+    HIPCK(hipSetDevice(E->device));
+    HIPCK(hipStreamSynchronize(E->stream));
+    const u64 total = A.h_state[QA_TOTAL];
+    const u32 m = (u32)std::min<u64>(A.k, total);
+    A.last_scans = A.h_state[QA_SCANS];
+    *matched = total;
+    if (m == 0) return TBGPU_STATUS_OK;
+    if (std::min<u64>(A.k, A.h_state[QA_NKEYS]) != m) {
+        return fail(TBGPU_STATUS_PANIC, "query_accounts: %llu keys selected for %u of %llu matches",
+                    (unsigned long long)A.h_state[QA_NKEYS], m, (unsigned long long)total);
+    }
+    HIPCK(hipMemcpyAsync(out, A.d_out, (u64)m * 128, hipMemcpyDeviceToHost, E->stream));
+    HIPCK(hipStreamSynchronize(E->stream));
+    *count = m;
+    return TBGPU_STATUS_OK;
+}
+
+extern "C" int tbgpu_query_accounts(tbgpu_t* E, const tbgpu_query_filter* filter, void* out, uint32_t out_cap_records,
+                                    tbgpu_query_result* result) {
+    API_ENTER(E, false);  // a read, as tbgpu_get_account_transfers
+    if (!filter || !out || !result) return fail(TBGPU_STATUS_INVALID, "query_accounts: a NULL filter, out or result");
+    result->count = 0;
+    result->matched = 0;
+    result->complete = 0;
+    const QueryFieldFilter F = query_fields_of(filter);
+    const bool reversed = (filter->flags & TBGPU_QUERY_REVERSED) != 0;
+    const bool valid = query_fields_valid(filter);
+    const u32 k = std::min<u32>(std::min<u32>(filter->limit, out_cap_records), BATCH_EVENTS_MAX);
+    if (E->node) return node_query_accounts(E->node, F, valid, k, reversed, (u8*)out, result);
+    result->complete = 1;  // accounts are never evicted
+    if (!valid) return TBGPU_STATUS_OK;
+    int st = account_query_enqueue(E, F, 0, 0, k, reversed);
+    if (st) return st;
+    u32 count = 0;
+    u64 matched = 0;
+    st = account_query_collect(E, (u8*)out, &count, &matched);
+    if (st) return st;
+    result->count = count;
+    result->matched = matched;
+    return TBGPU_STATUS_OK;
+}
+
+extern "C" int tbgpu_bench_query_select_scans(tbgpu_t* E, uint64_t* scans) {
+    API_ENTER(E, false);
+    if (E->node) E = node_engine(E->node, 0);
+    *scans = E->qa.last_scans;
     return TBGPU_STATUS_OK;
 }
 

@@ -19,27 +19,68 @@
 // the grid or by k.
 #pragma once
 
+#include <type_traits>
+
 #include "pass.h"
 
 #define QUERY_THREADS 256
 #define QUERY_WAVES (QUERY_THREADS / 64)
 
-struct QueryFilter {
+struct QueryFields {
+    u64 dlo, dhi, clo, chi, ts;
+};
+
+// The predicate is a template parameter of the scan (tb_query_fields, tb_query_hit and the kernels
+// that call them): a filter names the bytes it reads (Fields) and its test of them (pass); the
+// window, the liveness probe and everything after the test are shared.
+struct QueryFilter {  // get_account_transfers: one account on the wanted sides
+    typedef QueryFields Fields;
     u64 id_lo, id_hi;
     u64 ts_min, ts_max;  // inclusive; ts_max = ~0: no upper bound
     u32 debits, credits;
+    __device__ bool pass(const QueryFields& f) const {
+        return (debits && f.dlo == id_lo && f.dhi == id_hi) || (credits && f.clo == id_lo && f.chi == id_hi);
+    }
 };
 
-struct QueryFields {
-    u64 dlo, dhi, clo, chi, ts;
+struct QueryFieldVals {
+    u64 u128_lo, u128_hi, u64v, ts;
+    u32 u32v, ledger, code;
+};
+
+// query_transfers / query_accounts (k_query_filter.h): every non-zero field equals the stored one.
+struct QueryFieldFilter {
+    typedef QueryFieldVals Fields;
+    u64 u128_lo, u128_hi, u64v;
+    u64 ts_min, ts_max;  // as above
+    u32 u32v, ledger, code;
+    __host__ __device__ bool wants_u128() const { return (u128_lo | u128_hi) != 0; }
+    __device__ bool pass(const QueryFieldVals& f) const {
+        return (!wants_u128() || (f.u128_lo == u128_lo && f.u128_hi == u128_hi)) && (!u64v || f.u64v == u64v) &&
+               (!u32v || f.u32v == u32v) && (!ledger || f.ledger == ledger) && (!code || f.code == code);
+    }
 };
 
 // The 40 bytes the test needs of the record at `pos`: both account ids (bytes 16-47) and the
 // timestamp (byte 120).  COOP = false: the lane reads its own record (two 16-B loads and one 8-B
 // load, 128 B apart from its neighbours').  COOP = true: the wave reads chunks 1, 2 and 7 of its 64
 // records with neighbouring lanes on neighbouring chunks and hands them over through LDS.
-template <bool COOP>
-__device__ static inline QueryFields tb_query_fields(const Tables& T, u64 tile0, u64 n, u64* s_raw) {
+// The field filter reads chunks 5, 6 and 7 — user_data_128; user_data_64, user_data_32; ledger, code
+// and the timestamp, the last word of chunk 7 — three 16-B loads per lane, lane-per-record only.
+template <bool COOP, typename F>
+__device__ static inline typename F::Fields tb_query_fields(const Tables& T, u64 tile0, u64 n, u64* s_raw) {
+    if constexpr (std::is_same<F, QueryFieldFilter>::value) {
+        static_assert(!COOP, "the field filter has no cooperative load shape");
+        QueryFieldVals v{0, 0, 0, 0, 0, 0, 0};
+        const u64 pos = tile0 + threadIdx.x;
+        if (pos < n) {
+            const ulonglong2* c = (const ulonglong2*)&T.xlog[pos];
+            const ulonglong2 a = c[5], b = c[6], d = c[7];
+            v.u128_lo = a.x, v.u128_hi = a.y, v.u64v = b.x, v.u32v = (u32)b.y;
+            v.ledger = (u32)d.x, v.code = (u32)(d.x >> 32) & 0xFFFF, v.ts = d.y;
+        }
+        return v;
+    } else {
     QueryFields f{0, 0, 0, 0, 0};
     if (!COOP) {
         const u64 pos = tile0 + threadIdx.x;
@@ -65,32 +106,33 @@ __device__ static inline QueryFields tb_query_fields(const Tables& T, u64 tile0,
     const ulonglong2 d = s[lane * 3], cr = s[lane * 3 + 1], t = s[lane * 3 + 2];
     f.dlo = d.x, f.dhi = d.y, f.clo = cr.x, f.chi = cr.y, f.ts = t.y;
     return f;
+    }
 }
 
-// Whether the record at `pos` answers the filter: the account on a wanted side, the timestamp in the
-// window, and — only then — live: the id index holds its id at this position (tb_delta_live's test).
+// Whether the record at `pos` answers the filter: the filter's own test (the account on a wanted
+// side; the fields equal), the timestamp in the window, and — only then — live: the id index holds its id at this position (tb_delta_live's test).
 // A dead position (a failed event, a withdrawn speculative record, a rolled-back chain member) can
 // hold any bytes, so reserved ids never reach the probe.
-__device__ static inline bool tb_query_hit(const Tables& T, const QueryFilter& F, u64 pos, u64 n, const QueryFields& f) {
-    if (pos >= n || f.ts == 0 || f.ts < F.ts_min || f.ts > F.ts_max) return false;
-    const bool side = (F.debits && f.dlo == F.id_lo && f.dhi == F.id_hi) || (F.credits && f.clo == F.id_lo && f.chi == F.id_hi);
-    if (!side) return false;
+template <typename F>
+__device__ static inline bool tb_query_hit(const Tables& T, const F& flt, u64 pos, u64 n, const typename F::Fields& f) {
+    if (pos >= n || f.ts == 0 || f.ts < flt.ts_min || f.ts > flt.ts_max) return false;
+    if (!flt.pass(f)) return false;
     const u64* idw = (const u64*)&T.xlog[pos];
     const u64 lo = idw[0], hi = idw[1];
     if (tb_id_reserved(lo, hi)) return false;
     return tb_transfer_find(T, lo, hi) == (u32)pos;
 }
 
-template <bool COOP>
-__global__ __launch_bounds__(QUERY_THREADS) void tb_query_count(Tables T, QueryFilter F, u64 n, u32* counts, u64* mins,
+template <bool COOP, typename F>
+__global__ __launch_bounds__(QUERY_THREADS) void tb_query_count(Tables T, F flt, u64 n, u32* counts, u64* mins,
                                                                 u64* maxs, u32* ordered) {
     __shared__ __attribute__((aligned(16))) u64 s_chunks[COOP ? QUERY_WAVES * 192 * 2 : 2];
     __shared__ u64 s_max[QUERY_WAVES], s_min[QUERY_WAVES];
     __shared__ u32 s_cnt[QUERY_WAVES], s_bad[QUERY_WAVES];
     const u64 tile0 = (u64)blockIdx.x * QUERY_THREADS;
     const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const QueryFields f = tb_query_fields<COOP>(T, tile0, n, s_chunks);
-    const bool hit = tb_query_hit(T, F, tile0 + threadIdx.x, n, f);
+    const typename F::Fields f = tb_query_fields<COOP, F>(T, tile0, n, s_chunks);
+    const bool hit = tb_query_hit(T, flt, tile0 + threadIdx.x, n, f);
     // The largest matched timestamp at the lanes before this one: the wave's prefix maximum.
     u64 incl = hit ? f.ts : 0;
 #pragma unroll
@@ -191,7 +233,8 @@ __device__ static inline u32 tb_query_tile_rank(bool hit, u32* s_cnt) {
 
 // Ordered log: rank = position among the matches = position by timestamp.  The first k ranks (the
 // last k under `reversed`, newest first) write their whole record to out[0, k).
-__global__ __launch_bounds__(QUERY_THREADS) void tb_query_scatter(Tables T, QueryFilter F, u64 n, const u32* counts,
+template <typename F>
+__global__ __launch_bounds__(QUERY_THREADS) void tb_query_scatter(Tables T, F flt, u64 n, const u32* counts,
                                                                   const u64* base, const u64* res, u32 k, u32 reversed,
                                                                   u8* out) {
     __shared__ u32 s_cnt[QUERY_WAVES];
@@ -199,8 +242,8 @@ __global__ __launch_bounds__(QUERY_THREADS) void tb_query_scatter(Tables T, Quer
     const u64 kk = min((u64)k, total), lo = reversed ? total - kk : 0, hi = lo + kk;
     if (!res[1] || c == 0 || b0 >= hi || b0 + c <= lo) return;  // the whole workgroup alike
     const u64 pos = (u64)blockIdx.x * QUERY_THREADS + threadIdx.x;
-    const QueryFields f = tb_query_fields<false>(T, (u64)blockIdx.x * QUERY_THREADS, n, nullptr);
-    const bool hit = tb_query_hit(T, F, pos, n, f);
+    const typename F::Fields f = tb_query_fields<false, F>(T, (u64)blockIdx.x * QUERY_THREADS, n, nullptr);
+    const bool hit = tb_query_hit(T, flt, pos, n, f);
     const u64 rank = b0 + tb_query_tile_rank(hit, s_cnt);
     if (!hit || rank < lo || rank >= hi) return;
     const u64 dst = reversed ? total - 1 - rank : rank;
@@ -209,14 +252,15 @@ __global__ __launch_bounds__(QUERY_THREADS) void tb_query_scatter(Tables T, Quer
 
 // Unordered log, one round: the matches of tiles [wg0, wg0 + gridDim.x) as {timestamp, position}
 // keys, in log order from keys[0]; the host chose the range so that they fit keys_cap.
-__global__ __launch_bounds__(QUERY_THREADS) void tb_query_keys(Tables T, QueryFilter F, u64 n, u64 wg0, const u32* counts,
+template <typename F>
+__global__ __launch_bounds__(QUERY_THREADS) void tb_query_keys(Tables T, F flt, u64 n, u64 wg0, const u32* counts,
                                                                const u64* base, u64* keys, u64 keys_cap) {
     __shared__ u32 s_cnt[QUERY_WAVES];
     const u64 b = wg0 + blockIdx.x;
     if (counts[b] == 0) return;
     const u64 pos = b * QUERY_THREADS + threadIdx.x;
-    const QueryFields f = tb_query_fields<false>(T, b * QUERY_THREADS, n, nullptr);
-    const bool hit = tb_query_hit(T, F, pos, n, f);
+    const typename F::Fields f = tb_query_fields<false, F>(T, b * QUERY_THREADS, n, nullptr);
+    const bool hit = tb_query_hit(T, flt, pos, n, f);
     const u64 rank = base[b] - base[wg0] + tb_query_tile_rank(hit, s_cnt);
     if (hit && rank < keys_cap) {
         keys[2 * rank] = f.ts;

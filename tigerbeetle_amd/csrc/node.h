@@ -1705,28 +1705,20 @@ static int node_lookup(TbNode* N, bool accounts, const void* input, u32 input_le
     return TBGPU_STATUS_OK;
 }
 
-// get_account_transfers on a node (tbgpu.h): a transfer lives on its home shard only, so every shard
-// scans its own log on its own device and stream, side by side (engine.hip query_enqueue), and the
-// host merges the shards' answers — each its first k by timestamp, its last k under `reversed` —
-// under the limit, summing the matches.
-static int node_get_account_transfers(TbNode* N, const QueryFilter& F, bool valid, u32 k, bool reversed, u8* out,
-                                      tbgpu_query_result* result) {
-    result->complete = 1;
-    for (u32 d = 0; d < N->world; d++) {
-        if (N->D[d].E->evicted_total) result->complete = 0;
-    }
-    if (!valid) return TBGPU_STATUS_OK;
-    for (u32 d = 0; d < N->world; d++) {
-        const int st = query_enqueue(N->D[d].E, F, k, reversed);
-        if (st) return st;
-    }
+// The queries on a node (tbgpu.h).  A transfer lives on its home shard only and an account is answered
+// by its owner only, so every shard scans its own log or table on its own device and stream, side by
+// side (engine.hip query_enqueue / account_query_enqueue), and the host merges the shards' answers —
+// each its first k by timestamp, its last k under `reversed` — under the limit, summing the matches.
+// Both records carry their timestamp in their last word.
+static int node_query_finish(TbNode* N, bool accounts, u32 k, bool reversed, u8* out, tbgpu_query_result* result) {
     std::vector<std::vector<u8>> recs(N->world);
     std::vector<u32> cnt(N->world, 0), at(N->world, 0);
     int status = TBGPU_STATUS_OK;
     for (u32 d = 0; d < N->world; d++) {  // every shard is waited for, whatever an earlier one returned
         recs[d].resize((u64)std::max<u32>(k, 1) * 128);
         u64 m = 0;
-        const int st = query_collect(N->D[d].E, recs[d].data(), &cnt[d], &m);
+        const int st = accounts ? account_query_collect(N->D[d].E, recs[d].data(), &cnt[d], &m)
+                                : query_collect(N->D[d].E, recs[d].data(), &cnt[d], &m);
         if (st && status == TBGPU_STATUS_OK) status = st;
         result->matched += m;
     }
@@ -1749,6 +1741,34 @@ static int node_get_account_transfers(TbNode* N, const QueryFilter& F, bool vali
     }
     result->count = w;
     return TBGPU_STATUS_OK;
+}
+
+// get_account_transfers and query_transfers: the log scan under either predicate.
+template <typename F>
+static int node_query_transfers(TbNode* N, const F& flt, bool valid, u32 k, bool reversed, u8* out, tbgpu_query_result* result) {
+    result->complete = 1;
+    for (u32 d = 0; d < N->world; d++) {
+        if (N->D[d].E->evicted_total) result->complete = 0;
+    }
+    if (!valid) return TBGPU_STATUS_OK;
+    for (u32 d = 0; d < N->world; d++) {
+        const int st = query_enqueue(N->D[d].E, flt, k, reversed);
+        if (st) return st;
+    }
+    return node_query_finish(N, false, k, reversed, out, result);
+}
+
+// query_accounts: shard d answers for the accounts with tb_home(id, world) == d — a home's imported
+// copies of foreign accounts do not match, and the sequencer's engine (N->X) is not asked.
+static int node_query_accounts(TbNode* N, const QueryFieldFilter& F, bool valid, u32 k, bool reversed, u8* out,
+                               tbgpu_query_result* result) {
+    result->complete = 1;  // accounts are never evicted
+    if (!valid) return TBGPU_STATUS_OK;
+    for (u32 d = 0; d < N->world; d++) {
+        const int st = account_query_enqueue(N->D[d].E, F, N->world, d, k, reversed);
+        if (st) return st;
+    }
+    return node_query_finish(N, true, k, reversed, out, result);
 }
 
 // -- the tbgpu.h entry points of a node engine --------------------------------------------------------

@@ -287,6 +287,18 @@ tbgpu_query_result StateMachine::get_account_transfers(const tbgpu_account_filte
     return r;
 }
 
+tbgpu_query_result StateMachine::query_transfers(const tbgpu_query_filter& filter, void* out, uint32_t out_cap_records) {
+    tbgpu_query_result r{};
+    check(tbgpu_query_transfers(engine_, &filter, out, out_cap_records, &r), "query_transfers");
+    return r;
+}
+
+tbgpu_query_result StateMachine::query_accounts(const tbgpu_query_filter& filter, void* out, uint32_t out_cap_records) {
+    tbgpu_query_result r{};
+    check(tbgpu_query_accounts(engine_, &filter, out, out_cap_records, &r), "query_accounts");
+    return r;
+}
+
 void StateMachine::test_set_balances(u128 id, u128 dp, u128 dpost, u128 cp, u128 cpost) {
     const uint64_t b[8] = {(uint64_t)dp, (uint64_t)(dp >> 64), (uint64_t)dpost, (uint64_t)(dpost >> 64),
                            (uint64_t)cp, (uint64_t)(cp >> 64), (uint64_t)cpost, (uint64_t)(cpost >> 64)};

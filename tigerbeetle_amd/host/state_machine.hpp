@@ -234,6 +234,14 @@ public:
     // result.complete == 0: the engine has evicted transfers, and the caller merges with its forest.
     tbgpu_query_result get_account_transfers(const tbgpu_account_filter& filter, void* out, uint32_t out_cap_records);
 
+    // The field-filter queries (tbgpu_query_transfers / tbgpu_query_accounts; reads, not commits): the
+    // resident transfers, or the accounts, whose user_data_128 / user_data_64 / user_data_32 / ledger /
+    // code equal the filter's non-zero fields, by timestamp (newest first under TBGPU_QUERY_REVERSED),
+    // at most filter.limit and one message body.  Accounts carry their current balances and their
+    // result.complete is always 1; for transfers it is get_account_transfers' rule.
+    tbgpu_query_result query_transfers(const tbgpu_query_filter& filter, void* out, uint32_t out_cap_records);
+    tbgpu_query_result query_accounts(const tbgpu_query_filter& filter, void* out, uint32_t out_cap_records);
+
     // Test-only: the table harness `setup` action (state_machine.zig:1398-1407).
     void test_set_balances(u128 account_id, u128 debits_pending, u128 debits_posted, u128 credits_pending,
                            u128 credits_posted);

@@ -3,6 +3,7 @@
 //
 //   tb_table_runner <tests/golden/state_machine_tables.txt> [device]
 //   tb_table_runner --query <prepares.bin> <answer.bin> [device]     (run_query below)
+//   tb_table_runner --query-fields <transfers|accounts> <prepares.bin> <answer.bin> [device]
 //
 // The fixture holds the 18 check() tables of src/state_machine.zig:1531-2074 verbatim.  Row DSL:
 // src/testing/table.zig:8-100 (tokens, `_` defaults, letter labels, `-N` = maxInt - N); action
@@ -297,7 +298,11 @@ std::string run_table(tb::StateMachine& sm, const std::string& text) {
 // to compare with the Python mirror's answer.  <prepares.bin>: {u64 timestamp, u32 operation, u32
 // body bytes, body} per prepare, then {0, 0, 64, a tbgpu_account_filter}.  <answer.bin> receives the
 // 16-byte tbgpu_query_result and the records.
-int run_query(tb::StateMachine& sm, const char* in_path, const char* out_path) {
+// --query-fields (tests/test_gpu_query_filter_cpp.py): the same files, the prepares ending in a
+// tbgpu_query_filter for query_transfers or query_accounts.
+enum QueryKind { ACCOUNT_TRANSFERS, QUERY_TRANSFERS, QUERY_ACCOUNTS };
+
+int run_query(tb::StateMachine& sm, QueryKind kind, const char* in_path, const char* out_path) {
     std::ifstream in(in_path, std::ios::binary);
     if (!in) {
         fprintf(stderr, "cannot open %s\n", in_path);
@@ -319,13 +324,18 @@ int run_query(tb::StateMachine& sm, const char* in_path, const char* out_path) {
         sm.commit(0, ++op, ts, (tb::Operation)operation, body.data(), body.size(), reply.data());
     }
     tbgpu_account_filter f;
+    tbgpu_query_filter q;
+    static_assert(sizeof(f) == sizeof(q), "both filters are 64 bytes");
     if (body.size() != sizeof(f)) {
         fprintf(stderr, "%s: a filter is %zu bytes\n", in_path, sizeof(f));
         return 2;
     }
     memcpy(&f, body.data(), sizeof(f));
+    memcpy(&q, body.data(), sizeof(q));
     std::vector<uint8_t> out((size_t)TBGPU_BATCH_EVENTS_MAX * 128);
-    const tbgpu_query_result r = sm.get_account_transfers(f, out.data(), TBGPU_BATCH_EVENTS_MAX);
+    const tbgpu_query_result r = kind == ACCOUNT_TRANSFERS ? sm.get_account_transfers(f, out.data(), TBGPU_BATCH_EVENTS_MAX)
+                                 : kind == QUERY_TRANSFERS ? sm.query_transfers(q, out.data(), TBGPU_BATCH_EVENTS_MAX)
+                                                           : sm.query_accounts(q, out.data(), TBGPU_BATCH_EVENTS_MAX);
     std::ofstream o(out_path, std::ios::binary);
     o.write((const char*)&r, sizeof(r)).write((const char*)out.data(), (size_t)r.count * 128);
     printf("query: %u of %llu records, complete %u\n", r.count, (unsigned long long)r.matched, r.complete);
@@ -335,10 +345,21 @@ int run_query(tb::StateMachine& sm, const char* in_path, const char* out_path) {
 }  // namespace
 
 int main(int argc, char** argv) {
-    const bool query = argc > 1 && std::string(argv[1]) == "--query";
+    const bool fields = argc > 1 && std::string(argv[1]) == "--query-fields";
+    const bool query = fields || (argc > 1 && std::string(argv[1]) == "--query");
+    QueryKind kind = ACCOUNT_TRANSFERS;
+    const char* self = argv[0];
+    if (fields && argc > 2) {
+        const std::string which = argv[2];
+        kind = which == "transfers" ? QUERY_TRANSFERS : QUERY_ACCOUNTS;
+        if (which != "transfers" && which != "accounts") argc = 0;  // usage
+        argv++, argc--;  // the paths and the device now sit where --query has them
+    }
     if (argc < 2 || (query && argc < 4)) {
-        fprintf(stderr, "usage: %s <state_machine_tables.txt> [device]\n       %s --query <prepares.bin> <answer.bin> [device]\n",
-                argv[0], argv[0]);
+        fprintf(stderr,
+                "usage: %s <state_machine_tables.txt> [device]\n       %s --query <prepares.bin> <answer.bin> [device]\n"
+                "       %s --query-fields <transfers|accounts> <prepares.bin> <answer.bin> [device]\n",
+                self, self, self);
         return 2;
     }
     if (query) {
@@ -350,7 +371,7 @@ int main(int argc, char** argv) {
         o.device = argc > 4 ? atoi(argv[4]) : 0;
         try {
             tb::StateMachine sm(o);
-            return run_query(sm, argv[2], argv[3]);
+            return run_query(sm, kind, argv[2], argv[3]);
         } catch (const std::exception& e) {
             fprintf(stderr, "query failed: %s\n", e.what());
             return 255;

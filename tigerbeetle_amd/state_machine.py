@@ -23,7 +23,7 @@ import numpy as np
 
 from . import _lib
 from .types import (ACCOUNT_DTYPE, ACCOUNT_FILTER_DTYPE, BATCH_MAX, FILTER_CREDITS, FILTER_DEBITS, FILTER_REVERSED,
-                    TRANSFER_DTYPE, U64_MAX, Operation)
+                    QUERY_FILTER_DTYPE, QUERY_REVERSED, TRANSFER_DTYPE, U64_MAX, Operation)
 
 
 @dataclass
@@ -264,6 +264,55 @@ class Engine:
         src = ctypes.create_string_buffer(filter_bytes, len(filter_bytes))
         _lib.check(self.lib.tbgpu_get_account_transfers(self.h, src, out.ctypes.data, cap, ctypes.byref(res)))
         return out[:res.count], int(res.matched), bool(res.complete)
+
+    @staticmethod
+    def query_filter(user_data_128=0, user_data_64=0, user_data_32=0, ledger=0, code=0, *, reversed=False,
+                     timestamp_min=0, timestamp_max=0, limit=8190):
+        """The 64 bytes of a tbgpu_query_filter (QUERY_FILTER_DTYPE); a zero field is not filtered."""
+        f = np.zeros(1, dtype=QUERY_FILTER_DTYPE)
+        f["user_data_128_lo"], f["user_data_128_hi"] = user_data_128 & U64_MAX, user_data_128 >> 64
+        f["user_data_64"], f["user_data_32"], f["ledger"], f["code"] = user_data_64, user_data_32, ledger, code
+        f["timestamp_min"], f["timestamp_max"], f["limit"] = timestamp_min, timestamp_max, limit
+        f["flags"] = QUERY_REVERSED if reversed else 0
+        return f.tobytes()
+
+    def query_transfers(self, *, out_cap_records=None, **filter):
+        """The resident transfers whose user_data_128 / user_data_64 / user_data_32 / ledger / code
+        equal the non-zero keywords (tbgpu_query_transfers), by timestamp ascending, newest first
+        under `reversed`, at most `limit`.  Returns (records, matched, complete) as
+        get_account_transfers does."""
+        return self.query_transfers_raw(self.query_filter(**filter), out_cap_records)
+
+    def query_accounts(self, *, out_cap_records=None, **filter):
+        """The accounts that answer the same filter (tbgpu_query_accounts), with their current
+        balances; `complete` is always True."""
+        return self.query_accounts_raw(self.query_filter(**filter), out_cap_records)
+
+    def query_transfers_raw(self, filter_bytes, out_cap_records=None):
+        """query_transfers from the 64 bytes of a tbgpu_query_filter."""
+        return self._query_raw(self.lib.tbgpu_query_transfers, TRANSFER_DTYPE, filter_bytes, out_cap_records)
+
+    def query_accounts_raw(self, filter_bytes, out_cap_records=None):
+        """query_accounts from the 64 bytes of a tbgpu_query_filter."""
+        return self._query_raw(self.lib.tbgpu_query_accounts, ACCOUNT_DTYPE, filter_bytes, out_cap_records)
+
+    def _query_raw(self, fn, dtype, filter_bytes, out_cap_records):
+        filter_bytes = bytes(filter_bytes)
+        if len(filter_bytes) != QUERY_FILTER_DTYPE.itemsize:
+            raise ValueError("a query filter is %d bytes" % QUERY_FILTER_DTYPE.itemsize)
+        limit = int(np.frombuffer(filter_bytes, dtype=QUERY_FILTER_DTYPE)["limit"][0])
+        cap = min(limit, BATCH_MAX) if out_cap_records is None else int(out_cap_records)
+        out = np.zeros(max(cap, 1), dtype=dtype)
+        res = _lib.tbgpu_query_result()
+        src = ctypes.create_string_buffer(filter_bytes, len(filter_bytes))
+        _lib.check(fn(self.h, src, out.ctypes.data, cap, ctypes.byref(res)))
+        return out[:res.count], int(res.matched), bool(res.complete)
+
+    def query_select_scans(self):
+        """Table scans the last query_accounts' select made (tbgpu_bench_query_select_scans)."""
+        n = ctypes.c_uint64(0)
+        _lib.check(self.lib.tbgpu_bench_query_select_scans(self.h, ctypes.byref(n)))
+        return n.value
 
     def query_keys_max(self, keys):
         """Keys per round of a query over a log out of timestamp order (tbgpu_bench_query_keys_max)."""
@@ -571,6 +620,14 @@ class StateMachine:
         """The account-filter query (Engine.get_account_transfers): a read, no operation number in
         the reference's enum, so it does not go through commit."""
         return self.engine.get_account_transfers(account_id, **filter)
+
+    def query_transfers(self, **filter):
+        """The field-filter query over transfers (Engine.query_transfers): a read, not a commit."""
+        return self.engine.query_transfers(**filter)
+
+    def query_accounts(self, **filter):
+        """The field-filter query over accounts (Engine.query_accounts): a read, not a commit."""
+        return self.engine.query_accounts(**filter)
 
     def compact(self, callback, op):
         del op

@@ -108,6 +108,14 @@ ACCOUNT_FILTER_DTYPE = np.dtype(
 assert ACCOUNT_FILTER_DTYPE.itemsize == 64
 FILTER_DEBITS, FILTER_CREDITS, FILTER_REVERSED = 1, 2, 4
 
+# tbgpu_query_filter (include/tbgpu.h tbgpu_query_transfers / tbgpu_query_accounts): 64 bytes, no padding.
+QUERY_FILTER_DTYPE = np.dtype(
+    _u128("user_data_128") + [("user_data_64", "<u8"), ("user_data_32", "<u4"), ("ledger", "<u4"), ("code", "<u2"),
+                              ("reserved", "u1", (6,)), ("timestamp_min", "<u8"), ("timestamp_max", "<u8"),
+                              ("limit", "<u4"), ("flags", "<u4")])
+assert QUERY_FILTER_DTYPE.itemsize == 64
+QUERY_REVERSED = 1
+
 ACCOUNT_FIELDS = ("id", "debits_pending", "debits_posted", "credits_pending", "credits_posted",
                   "user_data_128", "user_data_64", "user_data_32", "reserved", "ledger", "code",
                   "flags", "timestamp")

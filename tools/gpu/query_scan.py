@@ -1,7 +1,7 @@
 """The account-filter scan (tbgpu_get_account_transfers, csrc/k_query.h) over a 16M-transfer log (2 GB)
 against a device-to-device copy of the same log range, in one process.
 
-usage: python tools/gpu/query_scan.py [transfers] [runs]
+usage: python tools/gpu/query_scan.py [transfers] [runs] [--only account|fields]
 
 The log is built by the device generator, committed in place (the way tools/gpu/device_pass.py builds
 a pass): once with uniform C2 ids, where the queried account is a cold one (a few dozen matches), and
@@ -9,6 +9,14 @@ once with the Zipf draw, where it is the hottest account.  Each query (limit 819
 newest first) is timed with the engine's markers, three warm-ups then the median of `runs`; so is the
 copy.  Both load shapes of tb_query_count are measured (TBGPU_QUERY_COOP, read at tbgpu_init).
 Prints one JSON line; the bar is query <= copy.
+
+The field-filter queries (tbgpu_query_transfers / tbgpu_query_accounts) are measured the
+same way on the uniform log and its 1M-account table: query_transfers with a selective filter (code and
+ledger) and a broad one (ledger only) against the copy of the log; query_accounts with an all-match
+filter (ledger only), a selective one with more matches than the limit, and one with fewer, against a
+device-to-device copy of 64 B x slots (the hot and cold entries the scan reads), with the number of
+table scans the select made.  `--only account` measures the account filter alone (an older library
+loaded through TBGPU_AB_LIB has nothing else), `--only fields` the field filters alone.
 """
 import json
 import os
@@ -20,10 +28,13 @@ import numpy as np  # noqa: E402
 
 from tests.harness.configs import KINDS, batches, timestamps  # noqa: E402
 from tigerbeetle_amd.state_machine import Engine, Options  # noqa: E402
-from tigerbeetle_amd.types import TRANSFER_DTYPE  # noqa: E402
+from tigerbeetle_amd.types import ACCOUNT_DTYPE, TRANSFER_DTYPE  # noqa: E402
 
-n_xfer = int(sys.argv[1]) if len(sys.argv) > 1 else 1 << 24
-runs = int(sys.argv[2]) if len(sys.argv) > 2 else 21
+argv = [a for a in sys.argv[1:] if not a.startswith("--")]
+only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else None
+argv = [a for a in argv if a != only]
+n_xfer = int(argv[0]) if len(argv) > 0 else 1 << 24
+runs = int(argv[1]) if len(argv) > 1 else 21
 n_acct, batch, pb = 1_000_000, 8190, 512
 WARMUPS = 3
 
@@ -91,9 +102,74 @@ def measure(coop):
     return out
 
 
-result = dict(transfers=n_xfer, log_bytes=n_xfer * 128, runs=runs, warmups=WARMUPS,
-              lane_per_record=measure(False), cooperative=measure(True))
-for shape in ("lane_per_record", "cooperative"):
-    r = result[shape]
-    r["bar_query_le_copy"] = all(v["ms"] <= r["copy_d2d"]["ms"] for k, v in r.items() if k != "copy_d2d")
+def row(med, lo_ms, hi_ms, **more):
+    return dict(ms=round(med, 4), min_ms=round(lo_ms, 4), max_ms=round(hi_ms, 4), **more)
+
+
+def measure_fields():
+    """query_transfers and query_accounts on the uniform log and its account table."""
+    os.environ["TBGPU_QUERY_COOP"] = "0"
+    e = Engine(Options(accounts_max=n_acct, transfers_max=n_xfer, pass_events_max=pb * batch, pass_batches_max=pb))
+    a_lens = batches(n_acct, batch)
+    a_ts, t = timestamps(a_lens, 1_000_000_000)
+    acct = e.alloc(n_acct * 128)
+    e.generate_accounts(acct, 0, n_acct, seed=42)
+    e.sync()
+    # The generator leaves user_data zero: every 50th account gets user_data_64 = 5 (more than one
+    # reply's worth), every 1000th user_data_64 = 7 (fewer).
+    host = e.to_host(acct, n_acct * 128).view(ACCOUNT_DTYPE)
+    host["user_data_64"][::50] = 5
+    host["user_data_64"][::1000] = 7
+    e.to_device(acct, host)
+    res = e.alloc(max(n_acct, n_xfer) * 8)
+    rb = e.alloc((n_xfer // batch + 2) * 4)
+    e.commit_device_async(128, a_ts, a_lens, acct, res, rb)
+    e.sync()
+    spare = e.alloc(n_xfer * 128)
+    log = e.log_window(n_xfer)
+    e.generate_transfers(log, 0, n_xfer, n_acct, seed=42, kind=KINDS["c2"])
+    e.sync()
+    x_lens = batches(n_xfer, batch)
+    x_ts, t = timestamps(x_lens, t + 10)
+    e.commit_device_async(129, x_ts, x_lens, log, res, rb)
+    e.sync()
+    sample = e.to_host(log + (n_xfer // 2) * 128, 128).view(TRANSFER_DTYPE)
+    out = {}
+    med, lo_ms, hi_ms = timed(e, lambda: e.copy_device_async(spare, log, n_xfer * 128))
+    out["copy_log_d2d"] = copy_log = row(med, lo_ms, hi_ms, bytes=n_xfer * 128)
+    for name, flt in (("selective_code_ledger", dict(code=int(sample["code"][0]), ledger=int(sample["ledger"][0]))),
+                      ("broad_ledger", dict(ledger=int(sample["ledger"][0])))):
+        for rev in (False, True):
+            recs, matched, complete = e.query_transfers(reversed=rev, limit=8190, **flt)
+            ts = recs["timestamp"].astype(np.int64)
+            assert complete and len(recs) == min(matched, 8190) and np.all(np.diff(ts) < 0 if rev else np.diff(ts) > 0)
+            med, lo_ms, hi_ms = timed(e, lambda: e.query_transfers(reversed=rev, limit=8190, **flt))
+            out["transfers_%s_%s" % (name, "reversed" if rev else "ascending")] = row(
+                med, lo_ms, hi_ms, matched=matched, count=len(recs), query_le_copy=med <= copy_log["ms"])
+    slots = e.stats()["account_table_bytes"] // 132  # hot 32 + balances 64 + cold 32 + mark 4 per slot
+    med, lo_ms, hi_ms = timed(e, lambda: e.copy_device_async(spare, log, slots * 64))
+    out["copy_table_d2d"] = copy_table = row(med, lo_ms, hi_ms, bytes=slots * 64, slots=slots)
+    for name, flt in (("all_match_ledger", dict(ledger=2)), ("selective_user_data_64", dict(user_data_64=5)),
+                      ("few_user_data_64", dict(user_data_64=7))):
+        for rev in (False, True):
+            recs, matched, complete = e.query_accounts(reversed=rev, limit=8190, **flt)
+            ts = recs["timestamp"].astype(np.int64)
+            assert complete and len(recs) == min(matched, 8190) and np.all(np.diff(ts) < 0 if rev else np.diff(ts) > 0)
+            scans = e.query_select_scans()
+            med, lo_ms, hi_ms = timed(e, lambda: e.query_accounts(reversed=rev, limit=8190, **flt))
+            out["accounts_%s_%s" % (name, "reversed" if rev else "ascending")] = row(
+                med, lo_ms, hi_ms, matched=matched, count=len(recs), select_scans=scans, table_scans=scans + 2,
+                ratio_to_copy=round(med / copy_table["ms"], 2))
+    e.close()
+    return out
+
+
+result = dict(transfers=n_xfer, log_bytes=n_xfer * 128, runs=runs, warmups=WARMUPS)
+if only != "fields":
+    result.update(lane_per_record=measure(False), cooperative=measure(True))
+    for shape in ("lane_per_record", "cooperative"):
+        r = result[shape]
+        r["bar_query_le_copy"] = all(v["ms"] <= r["copy_d2d"]["ms"] for k, v in r.items() if k != "copy_d2d")
+if only != "account":
+    result["field_filters"] = measure_fields()
 print(json.dumps(result))
