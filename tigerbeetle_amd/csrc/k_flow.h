@@ -242,8 +242,8 @@ __device__ static inline bool fl_pending_accounts(const PassArgs& P, u64 lo, u64
     const Tables& T = P.T;
     if (tb_id_reserved(lo, hi)) return true;
     const u64 fp = tb_fp32(lo, hi);
-    u64 pos = tb_hash_id(lo, hi) & T.xidx_mask;
-    for (u64 n = 0; n <= T.xidx_mask; n++) {
+    u64 pos = tb_xi_home(lo, hi, T.xidx_mask);
+    for (u64 n = 0; n < tb_xi_steps(T.xidx_mask); n++) {
         const u64 e = T.xidx[pos];
         if (e == 0) return true;
         if ((e >> 32) == fp) {
@@ -272,7 +272,7 @@ __device__ static inline bool fl_pending_accounts(const PassArgs& P, u64 lo, u64
             if (crs != TB_NOT_FOUND && fl_account_is_resource(T, crs, P.epoch, cert_global)) keys[nk++] = crs;
             if (nk > FLOW_RMAX - 2) return false;  // several matching records: keep it simple
         }
-        pos = (pos + 1) & T.xidx_mask;
+        pos = tb_xi_next(pos, T.xidx_mask);
     }
     return true;
 }

@@ -997,15 +997,15 @@ __global__ void tb_seq_xidx_list(Tables X, const u64* loaded, const u8* events, 
         }
         if (tb_id_reserved(lo, hi)) continue;  // no claim: the event failed before its id check
         const u64 fp = tb_fp32(lo, hi);
-        u64 p = tb_hash_id(lo, hi) & X.xidx_mask;
-        for (u64 k = 0; k <= X.xidx_mask; k++) {
+        u64 p = tb_xi_home(lo, hi, X.xidx_mask);
+        for (u64 k = 0; k < tb_xi_steps(X.xidx_mask); k++) {
             const u64 e = X.xidx[p];
             if (e == 0) break;
             if ((e >> 32) == fp && (e & XI_POS_MASK) == pos + 1) {
                 const u64 at = atomicAdd((unsigned long long*)&count[0], 1ULL);
                 if (at < cap) list[at] = (u32)p;
             }
-            p = (p + 1) & X.xidx_mask;
+            p = tb_xi_next(p, X.xidx_mask);
         }
     }
 }

@@ -152,8 +152,8 @@ __device__ static inline u32 rp_transfer_find(const Tables& T, u64 lo, u64 hi) {
     if (!FLOW) return tb_transfer_find(T, lo, hi);
     if (tb_id_reserved(lo, hi)) return TB_NOT_FOUND;
     const u64 fp = tb_fp32(lo, hi);
-    u64 pos = tb_hash_id(lo, hi) & T.xidx_mask;
-    for (u64 n = 0; n <= T.xidx_mask; n++) {
+    u64 pos = tb_xi_home(lo, hi, T.xidx_mask);
+    for (u64 n = 0; n < tb_xi_steps(T.xidx_mask); n++) {
         const u64 e = fl_ld64(&T.xidx[pos]);
         if (e == 0) return TB_NOT_FOUND;
         if ((e >> 32) == fp && !(e & XI_TOMB)) {
@@ -161,7 +161,7 @@ __device__ static inline u32 rp_transfer_find(const Tables& T, u64 lo, u64 hi) {
             const u64* idw = (const u64*)&T.xlog[lp];
             if (fl_ld64(idw) == lo && fl_ld64(idw + 1) == hi) return lp;
         }
-        pos = (pos + 1) & T.xidx_mask;
+        pos = tb_xi_next(pos, T.xidx_mask);
     }
     return TB_NOT_FOUND;
 }

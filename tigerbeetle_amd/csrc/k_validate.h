@@ -92,7 +92,7 @@ __device__ static inline u32 tb_claim_id(const PassArgs& P, const Transfer& t, u
     if (TB_ABL(P, ABL_SPEC)) return CLAIM_NEW;
     u32 entry = TB_NOT_FOUND;
     if (TB_ABL(P, ABL_CAS)) {  // timing only: no atomic claim
-        s.rs = (u32)(tb_hash_id(tb_lo(t.id), tb_hi(t.id)) & P.T.xidx_mask);
+        s.rs = (u32)tb_xi_home(tb_lo(t.id), tb_hi(t.id), P.T.xidx_mask);
         s.hz |= HZ_SPEC;
         return CLAIM_NEW;
     }
@@ -221,7 +221,7 @@ __device__ static inline u32 tb_validate_transfer(const PassArgs& P, const Trans
     const u64 clo = tb_lo(t.credit_account_id), chi = tb_hi(t.credit_account_id);
     const u64 dpos = tb_hash_id(dlo, dhi) & T.account_mask;
     const u64 cpos = tb_hash_id(clo, chi) & T.account_mask;
-    const u64 xpos = tb_hash_id(tb_lo(t.id), tb_hi(t.id)) & T.xidx_mask;
+    const u64 xpos = tb_xi_home(tb_lo(t.id), tb_hi(t.id), T.xidx_mask);
     const bool fake = TB_ABL(P, ABL_ACCTS);
     AccountHot d0 = {}, c0 = {};
     if (!fake) {

@@ -202,7 +202,9 @@ __global__ void tb_gen_transfers(u8* out, u64 count, WorkloadParams W) {
 // buffers sized like the engine's tables — what the hardware does for this pattern is the kernel's
 // practical bound.  STREAM: the 128-B event in, the 128-B record and 26 B of
 // per-event results out (info, flags, dr, cr, rs, amount low word); PROBE: two random 32-B rows of an account-table-sized array; CAS: one
-// random 8-B CAS into an index-sized array.
+// random 8-B CAS into an index-sized array.  The CAS stays random although the engine now clusters
+// consecutive ids (tb_device.h tb_xi_home): the mix prices the random-id pattern, which is the
+// engine's worst case, and the headline's reversed ids run below it.
 enum : u32 { MIX_STREAM = 1, MIX_PROBE = 2, MIX_CAS = 4 };
 struct MixArgs {
     const uint4* events;

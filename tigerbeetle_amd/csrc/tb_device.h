@@ -181,6 +181,17 @@ __device__ static inline u128 tb_sat_add(u128 a, u128 b) {
 // confirms a match against the log record's id.  A second event of the same pass with the same id
 // meets the claimed fingerprint on its probe path (or loses the CAS to it) — that is how same-pass
 // duplicate ids are detected, with no separate dedup set.
+//
+// Index layout: the index is cut into 64-byte SEGMENTS of XI_GROUP = 8 entries, the size of one
+// memory-side atomic request.  The 8 ids of a GROUP (id >> 3) share one segment, picked by the hash
+// of the group, and take 8 distinct slots in it: slot = (id.lo + rot) & 7, with `rot` from the same
+// hash so that ids which share their low bits (multiples of 8, shifted ids, ids that differ in the
+// high word only) still spread over all 8 slot classes.  A probe steps to the same slot of the next
+// segment (tb_xi_next), so a class is a cycle of xidx_cap / 8 entries and a group that collides with
+// another group moves on as a whole and stays clustered.  A wave that claims 64 consecutive ids
+// issues its 64 CASes into 8 or 9 segments instead of 64 lines; random ids scatter as before.
+// tb_xi_home and tb_xi_next are the only places that know the layout; every probe loop is bounded by
+// tb_xi_steps, the length of a class.
 // ------------------------------------------------------------------------------------------------
 #ifndef FL_BAR_GROUPS
 #define FL_BAR_GROUPS 8
@@ -496,12 +507,30 @@ __host__ __device__ static inline u64 tb_fingerprint(u64 lo, u64 hi) {
 __host__ __device__ static inline u64 tb_fp32(u64 lo, u64 hi) { return (tb_fingerprint(lo, hi) >> 32) | 1; }
 __device__ static inline u32 tb_xi_pos(u64 e) { return (u32)((e & XI_POS_MASK) - 1); }
 
+// The index layout (above): home entry of an id, the next entry of its probe path, and the length
+// of that path.  `mask` is xidx_mask (xidx_cap - 1, xidx_cap a power of two >= XI_GROUP).
+#define XI_GROUP_LOG2 3
+#define XI_GROUP (1ULL << XI_GROUP_LOG2)
+
+__host__ __device__ static inline u64 tb_xi_home(u64 lo, u64 hi, u64 mask) {
+    const u64 glo = (lo >> XI_GROUP_LOG2) | (hi << (64 - XI_GROUP_LOG2)), ghi = hi >> XI_GROUP_LOG2;
+    const u64 h = tb_hash_id(glo, ghi);
+    const u64 seg = h & (mask >> XI_GROUP_LOG2);
+    const u64 rot = h >> (64 - XI_GROUP_LOG2);
+    return (seg << XI_GROUP_LOG2) | ((lo + rot) & (XI_GROUP - 1));
+}
+
+__host__ __device__ static inline u64 tb_xi_next(u64 p, u64 mask) { return (p + XI_GROUP) & mask; }
+
+// Entries on a probe path (one slot class): a probe loop runs `n < tb_xi_steps(mask)`.
+__host__ __device__ static inline u64 tb_xi_steps(u64 mask) { return (mask >> XI_GROUP_LOG2) + 1; }
+
 // Find a live transfer; returns its log position or TB_NOT_FOUND.
 __device__ static inline u32 tb_transfer_find(const Tables& T, u64 lo, u64 hi) {
     if (tb_id_reserved(lo, hi)) return TB_NOT_FOUND;
     const u64 fp = tb_fp32(lo, hi);
-    u64 pos = tb_hash_id(lo, hi) & T.xidx_mask;
-    for (u64 n = 0; n <= T.xidx_mask; n++) {
+    u64 pos = tb_xi_home(lo, hi, T.xidx_mask);
+    for (u64 n = 0; n < tb_xi_steps(T.xidx_mask); n++) {
         const u64 e = T.xidx[pos];
         if (e == 0) return TB_NOT_FOUND;
         if ((e >> 32) == fp && !(e & XI_TOMB)) {
@@ -509,7 +538,7 @@ __device__ static inline u32 tb_transfer_find(const Tables& T, u64 lo, u64 hi) {
             const u64* idw = (const u64*)&T.xlog[lp];
             if (idw[0] == lo && idw[1] == hi) return lp;
         }
-        pos = (pos + 1) & T.xidx_mask;
+        pos = tb_xi_next(pos, T.xidx_mask);
     }
     return TB_NOT_FOUND;
 }
@@ -528,7 +557,8 @@ __device__ static inline u32 tb_transfer_claim(const Tables& T, u64 lo, u64 hi, 
     const u64 fp = tb_fp32(lo, hi);
     const u64 mine = (fp << 32) | ((u64)log_pos + 1);
     const u64 mask = T.xidx_mask;
-    u64 pos = tb_hash_id(lo, hi) & mask;
+    const u64 steps = tb_xi_steps(mask);
+    u64 pos = tb_xi_home(lo, hi, mask);
     // One entry: claim it if empty, else decide on its fingerprint.  Returns CLAIM_FULL to go on.
     auto step = [&](u64 p, u64 cur) -> u32 {
         if (cur == 0) {
@@ -560,20 +590,21 @@ __device__ static inline u32 tb_transfer_claim(const Tables& T, u64 lo, u64 hi, 
         }
         const u32 r = step(pos, first);
         if (r != CLAIM_FULL) return r;
-        pos = (pos + 1) & mask;
+        pos = tb_xi_next(pos, mask);
         n = 1;
     }
     // The chain, two entries per read round (entries never return to empty, so a value read before
-    // the first one's CAS is still a valid lower bound for the second).
-    for (; n <= mask; n += 2) {
-        const u64 q = (pos + 1) & mask;
+    // the first one's CAS is still a valid lower bound for the second).  A round that reaches past
+    // the end of the class revisits its first entries, which changes nothing: they were full.
+    for (; n < steps; n += 2) {
+        const u64 q = tb_xi_next(pos, mask);
         const u64 e0 = *(volatile u64*)&T.xidx[pos];
         const u64 e1 = *(volatile u64*)&T.xidx[q];
         u32 r = step(pos, e0);
         if (r != CLAIM_FULL) return r;
         r = step(q, e1);
         if (r != CLAIM_FULL) return r;
-        pos = (q + 1) & mask;
+        pos = tb_xi_next(q, mask);
     }
     tb_panic(T.g, PANIC_TABLE_FULL);
     return CLAIM_FULL;
@@ -591,11 +622,11 @@ __device__ static inline u64 tb_transfer_cas_home(const Tables& T, u64 lo, u64 h
 // Claim the first empty entry for an id known to be absent (the ordered replay).
 __device__ static inline u32 tb_transfer_claim_new(const Tables& T, u64 lo, u64 hi, u32 log_pos) {
     const u64 mine = (tb_fp32(lo, hi) << 32) | ((u64)log_pos + 1);
-    u64 pos = tb_hash_id(lo, hi) & T.xidx_mask;
-    for (u64 n = 0; n <= T.xidx_mask; n++) {
+    u64 pos = tb_xi_home(lo, hi, T.xidx_mask);
+    for (u64 n = 0; n < tb_xi_steps(T.xidx_mask); n++) {
         u64* e = &T.xidx[pos];
         if (*e == 0 && atomicCAS((unsigned long long*)e, 0ULL, (unsigned long long)mine) == 0ULL) return (u32)pos;
-        pos = (pos + 1) & T.xidx_mask;
+        pos = tb_xi_next(pos, T.xidx_mask);
     }
     tb_panic(T.g, PANIC_TABLE_FULL);
     return TB_NOT_FOUND;
@@ -606,12 +637,12 @@ __device__ static inline u32 tb_transfer_claim_new(const Tables& T, u64 lo, u64 
 __device__ static inline bool tb_transfer_claimed_in_pass(const Tables& T, u64 lo, u64 hi, u64 pass_base) {
     if (tb_id_reserved(lo, hi)) return false;
     const u64 fp = tb_fp32(lo, hi);
-    u64 pos = tb_hash_id(lo, hi) & T.xidx_mask;
-    for (u64 n = 0; n <= T.xidx_mask; n++) {
+    u64 pos = tb_xi_home(lo, hi, T.xidx_mask);
+    for (u64 n = 0; n < tb_xi_steps(T.xidx_mask); n++) {
         const u64 e = T.xidx[pos];
         if (e == 0) return false;
         if ((e >> 32) == fp && (u64)tb_xi_pos(e) >= pass_base) return true;
-        pos = (pos + 1) & T.xidx_mask;
+        pos = tb_xi_next(pos, T.xidx_mask);
     }
     return true;
 }

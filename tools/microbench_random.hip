@@ -3,7 +3,8 @@
 // Measures, for a table of `bytes` bytes, the rate of: random 16-B loads, random 32-B loads,
 // random 8-B CAS (returning), random 8-B atomicAdd (no return), random 128-B stores, and a
 // coalesced 16-B/lane stream read, so the commit engine's per-transfer random-op budget can be
-// priced.
+// priced. Two further columns price a clustered CAS into 8-B entries: cas8_c8 puts 8
+// consecutive lanes into one random 64-B segment, cas8_c16 puts 16 into one random 128-B line.
 //
 //   hipcc --offload-arch=gfx950 -O3 -o /tmp/mb tools/microbench_random.hip && /tmp/mb
 #include <hip/hip_runtime.h>
@@ -62,6 +63,10 @@ __global__ void k(u64* table, u64 mask16, u64 n_ops, u64* sink) {
             const uint4 v = *(const uint4*)(table + 2 * slot);
             const uint4 w = *(const uint4*)(table + 2 * s2);
             acc += v.x ^ w.y;
+        } else if (MODE == 7 || MODE == 8) {  // clustered CAS 8 B (returning): G lanes per segment
+            constexpr int LG = MODE == 7 ? 3 : 4;
+            const u64 seg = mix((i >> LG) * 0x9e3779b97f4a7c15ULL + 12345) & (mask16 >> (LG - 1));
+            acc += atomicCAS(table + ((seg << LG) | (i & ((1u << LG) - 1))), 0ULL, h | 1);
         }
     }
     if (acc == 0x123456789ULL) sink[0] = acc;
@@ -87,8 +92,8 @@ int main(int argc, char** argv) {
     const u64 n_ops = 1ULL << 27;
     u64* sink;
     CK(hipMalloc(&sink, 64));
-    printf("%10s %10s %10s %10s %10s %10s %10s %10s  (G ops/s)\n", "table_MB", "rd16", "rd32", "cas8", "add8_nr",
-           "st128", "stream16", "2xrd16");
+    printf("%10s %10s %10s %10s %10s %10s %10s %10s %10s %10s  (G ops/s)\n", "table_MB", "rd16", "rd32", "cas8",
+           "add8_nr", "st128", "stream16", "2xrd16", "cas8_c8", "cas8_c16");
     for (u64 mb : sizes_mb) {
         const u64 bytes = mb << 20;
         u64* table;
@@ -102,7 +107,13 @@ int main(int argc, char** argv) {
         const double r4 = run<4>(table, mask16, n_ops / 4, sink);
         const double r5 = run<5>(table, mask16, n_ops, sink);
         const double r6 = run<6>(table, mask16, n_ops, sink);
-        printf("%10llu %10.2f %10.2f %10.2f %10.2f %10.2f %10.2f %10.2f\n", mb, r0, r1, r2, r3, r4, r5, r6);
+        // the table is cleared again so each clustered CAS meets an empty entry, as cas8 mostly does
+        CK(hipMemset(table, 0, bytes));
+        const double r7 = run<7>(table, mask16, n_ops, sink);
+        CK(hipMemset(table, 0, bytes));
+        const double r8 = run<8>(table, mask16, n_ops, sink);
+        printf("%10llu %10.2f %10.2f %10.2f %10.2f %10.2f %10.2f %10.2f %10.2f %10.2f\n", mb, r0, r1, r2, r3, r4, r5, r6,
+               r7, r8);
         CK(hipFree(table));
     }
     return 0;
