@@ -19,6 +19,8 @@
  *     (:140-178; no reference operation reads them)          operation: specified below)
  *   both grooves' user_data / ledger / code / timestamp     tbgpu_query_transfers, tbgpu_query_accounts
  *     index trees (:103-169; likewise unread)                (likewise)
+ *   (later references: the account_balances groove)        tbgpu_get_account_balances (likewise;
+ *                                                             derived from the log, nothing stored)
  *   `setup` action of the table tests (:1398-1407)         tbgpu_test_set_balances (test only)
  *   StateMachine.commit_timestamp field (:251)             tbgpu_commit_timestamp
  *
@@ -321,6 +323,58 @@ typedef struct tbgpu_query_result {
 
 int tbgpu_get_account_transfers(tbgpu_t* engine, const tbgpu_account_filter* filter,
                                 void* out, uint32_t out_cap_records, tbgpu_query_result* result);
+
+/* get_account_balances: an account's four balances as they stood right after each of its transfers.
+ * Later references answer it from balance rows they store at every commit for accounts that opted in
+ * with a `history` flag.  This engine stores nothing and asks for no flag: the transfer log is in HBM
+ * and the account table holds the current balances, so the history is derived when asked, and the
+ * commit path is not touched.  An entry point of its own, as above; this comment is its specification.
+ *   Which rows: exactly the transfers tbgpu_get_account_transfers returns for the same filter and
+ *     out_cap_records, in the same order, one 128-byte row per transfer.  count, matched and every
+ *     invalid-filter rule are that call's: an invalid filter returns TBGPU_STATUS_OK with count =
+ *     matched = 0; a NULL filter, out or result is TBGPU_STATUS_INVALID.
+ *   What a row holds: the transfer's timestamp and the account's four balances right after that
+ *     transfer committed.  Let R be every live resident record that names the account on either side
+ *     (the DEBITS / CREDITS flags and the timestamp window choose rows, not what is summed).  A
+ *     record's effect on the account's side — debits_* where it is the debit account, credits_* where
+ *     it is the credit account — follows src/state_machine.zig:872-878 and :997-1007:
+ *       a pending record   *_pending += amount
+ *       a post             *_pending -= P, *_posted += amount
+ *       a void             *_pending -= P
+ *       any other          *_posted  += amount
+ *     where P is the amount of the resident record whose id is the record's pending_id (for a void, P
+ *     equals the void record's own amount).  Then
+ *       balance_after(r) = current balances - the sum of the effects of the records in R with a
+ *                          timestamp strictly above r's,
+ *     per column modulo 2^128; the true values are in range, so the modular result is exact.  The
+ *     anchor is the current balance, not zero, so the rows stay exact after the oldest transfers were
+ *     evicted, after a restart from checkpointed balances (tbgpu_load_accounts) and after
+ *     tbgpu_test_set_balances.
+ *   complete: 1 when no transfer was ever evicted (tbgpu_get_account_transfers' rule) and every post
+ *     record that entered a sum found its pending transfer resident; otherwise 0.  A post whose pending
+ *     transfer is not resident is summed with P = its own amount.  Rows of a complete = 0 answer are
+ *     still exact whenever every transfer of the account newer than the oldest returned row is
+ *     resident and none of them is such an orphan post — the common case, eviction of an old prefix.
+ *   The call contract of tbgpu_get_account_transfers: synchronous, drains a pending
+ *     tbgpu_commit_device_async first, changes nothing, works on an engine a device panic stopped,
+ *     allocates nothing (every buffer is made in tbgpu_init), legal beside an asynchronous write-back.
+ *     It scans the log once more than tbgpu_get_account_transfers does.
+ *   A node engine has the same contract: the rows are the merged answer; every home shard sums the
+ *     effects of its own log on its own device, reading a post's pending transfer on the home shard of
+ *     its pending_id; the host adds the shards' sums and takes the current balances from the account's
+ *     owner shard. */
+typedef struct tbgpu_account_balance {   /* 128 bytes, little-endian, no padding: the later
+                                            reference's AccountBalance */
+    uint64_t debits_pending_lo,  debits_pending_hi;
+    uint64_t debits_posted_lo,   debits_posted_hi;
+    uint64_t credits_pending_lo, credits_pending_hi;
+    uint64_t credits_posted_lo,  credits_posted_hi;
+    uint64_t timestamp;
+    uint8_t  reserved[56];               /* zero */
+} tbgpu_account_balance;
+
+int tbgpu_get_account_balances(tbgpu_t* engine, const tbgpu_account_filter* filter,
+                               void* out, uint32_t out_cap_records, tbgpu_query_result* result);
 
 /* query_transfers / query_accounts: which transfers, or accounts, carry these field values.  The
  * reference maintains the user_data_128 / user_data_64 / user_data_32 / ledger / code / timestamp

@@ -44,6 +44,14 @@ class tbgpu_account_filter(ctypes.Structure):
                 ("limit", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint8 * 24)]
 
 
+class tbgpu_account_balance(ctypes.Structure):
+    _fields_ = [("debits_pending_lo", ctypes.c_uint64), ("debits_pending_hi", ctypes.c_uint64),
+                ("debits_posted_lo", ctypes.c_uint64), ("debits_posted_hi", ctypes.c_uint64),
+                ("credits_pending_lo", ctypes.c_uint64), ("credits_pending_hi", ctypes.c_uint64),
+                ("credits_posted_lo", ctypes.c_uint64), ("credits_posted_hi", ctypes.c_uint64),
+                ("timestamp", ctypes.c_uint64), ("reserved", ctypes.c_uint8 * 56)]
+
+
 class tbgpu_query_filter(ctypes.Structure):
     _fields_ = [("user_data_128_lo", ctypes.c_uint64), ("user_data_128_hi", ctypes.c_uint64),
                 ("user_data_64", ctypes.c_uint64), ("user_data_32", ctypes.c_uint32), ("ledger", ctypes.c_uint32),
@@ -174,6 +182,7 @@ SIGNATURES = [
     ("tbgpu_export_transfers", ctypes.c_int, [_P, _P, _U64, ctypes.POINTER(_U64)]),
     ("tbgpu_export_posted", ctypes.c_int, [_P, _P, _U64, ctypes.POINTER(_U64)]),
     ("tbgpu_get_account_transfers", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
+    ("tbgpu_get_account_balances", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_query_transfers", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_query_accounts", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_bench_query_keys_max", ctypes.c_int, [_P, _U32]),

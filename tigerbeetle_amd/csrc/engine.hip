@@ -34,6 +34,7 @@
 #include "k_evict.h"
 #include "k_query.h"
 #include "k_query_filter.h"
+#include "k_balances.h"
 #include "checksum.h"
 
 static thread_local std::string g_err;
@@ -181,6 +182,15 @@ struct QueryBufs {
     u32 k = 0;
     bool reversed = false;
     u64 n = 0;
+};
+
+// tbgpu_get_account_balances (k_balances.h): the rows' timestamps and the bins, on the device and
+// pinned; made at tbgpu_init and shared with nothing.  The rows themselves are chosen through QueryBufs.
+struct BalanceBufs {
+    u64* d_ts = nullptr;    // [BATCH_EVENTS_MAX] the rows' timestamps, ascending
+    u64* h_ts = nullptr;    // pinned mirror (a node hands every shard the merged rows' here)
+    u64* d_bins = nullptr;  // [BALANCE_SLOTS(BATCH_EVENTS_MAX)][BALANCE_SLOT_WORDS]
+    u64* h_bins = nullptr;  // pinned mirror
 };
 
 // tbgpu_query_accounts (k_query_filter.h): O(slots / 256 + histogram + k) device memory, made at
@@ -346,6 +356,7 @@ struct tbgpu {
     u64* r_meta = nullptr;    // device [meta_cap + 1] offsets then [meta_cap] timestamps
     u64* h_rmeta = nullptr;   // pinned mirror
     AccountQueryBufs qa;
+    BalanceBufs qb;
 };
 
 // The write-back snapshot as a balance view (its two planes, like T.bal).
@@ -577,6 +588,8 @@ template <typename F>
 static int node_query_transfers(TbNode* N, const F& flt, bool valid, u32 k, bool reversed, u8* out, tbgpu_query_result* result);
 static int node_query_accounts(TbNode* N, const QueryFieldFilter& F, bool valid, u32 k, bool reversed, u8* out,
                                tbgpu_query_result* result);
+static int node_account_balances(TbNode* N, const QueryFilter& F, bool valid, u32 k, bool reversed, u8* out,
+                                 tbgpu_query_result* result);
 
 extern "C" int tbgpu_init(const tbgpu_config* config, tbgpu_t** out) {
     if (config && config->device_count > 1) return node_api_init(config, out);
@@ -867,6 +880,13 @@ extern "C" int tbgpu_init(const tbgpu_config* config, tbgpu_t** out) {
         E->event_pool.resize(PROF_EVENTS);
         for (auto& ev : E->event_pool) INIT_CK(tbEventCreate(&ev));
     }
+    {  // tbgpu_get_account_balances: the rows' timestamps and the bins
+        BalanceBufs& B = E->qb;
+        INIT_CK(tbMalloc(&B.d_ts, (u64)BATCH_EVENTS_MAX * 8));
+        INIT_CK(tbHostMalloc(&B.h_ts, (u64)BATCH_EVENTS_MAX * 8, hipHostMallocDefault));
+        INIT_CK(tbMalloc(&B.d_bins, BALANCE_SLOTS(BATCH_EVENTS_MAX) * BALANCE_SLOT_WORDS * 8));
+        INIT_CK(tbHostMalloc(&B.h_bins, BALANCE_SLOTS(BATCH_EVENTS_MAX) * BALANCE_SLOT_WORDS * 8, hipHostMallocDefault));
+    }
     {  // tbgpu_query_accounts: per-tile counts and bounds, the select's state and histograms, keys, the answer
         AccountQueryBufs& A = E->qa;
         A.nb = (E->account_cap + QUERY_THREADS - 1) / QUERY_THREADS;
@@ -907,7 +927,7 @@ extern "C" void tbgpu_deinit(tbgpu_t* E) {
                     E->wb.d_bc, E->wb.d_base, E->wb.d_out, E->wb.d_ids, E->wb.d_pv, E->wb.d_pairs, E->wb.d_hids,
                     E->wb.d_acc, E->wb.d_before, E->wb.d_slots, E->wb.d_cap, E->wb.d_cnt,
                     E->q.d_counts, E->q.d_mins, E->q.d_maxs, E->q.d_ordered, E->q.d_base, E->q.d_res, E->q.d_out, E->q.d_keys,
-                    E->qa.d_counts, E->qa.d_mins, E->qa.d_maxs, E->qa.d_state, E->qa.d_keys, E->qa.d_out,
+                    E->qa.d_counts, E->qa.d_mins, E->qa.d_maxs, E->qa.d_state, E->qa.d_keys, E->qa.d_out, E->qb.d_ts, E->qb.d_bins,
                     E->r_block_counts, E->r_words, E->r_meta, E->resolve_slow, E->leg_w, E->leg_off, E->leg_tot,
                     E->F.f_pe, E->F.f_batch, E->F.f_len, E->F.need, E->F.nsucc, E->F.queue, E->F.uflags, E->F.nacct, E->F.rpos, E->F.succ,
                     E->F.run, E->F.keys[0], E->F.keys[1], E->F.vals[0], E->F.vals[1], E->F.hist, E->F.words, E->F.undo,
@@ -930,7 +950,7 @@ extern "C" void tbgpu_deinit(tbgpu_t* E) {
     if (E->h_rmeta) (void)hipHostFree(E->h_rmeta);
     if (E->h_kclock) (void)hipHostFree(E->h_kclock);
     if (E->h_pub) (void)hipHostFree(E->h_pub);
-    for (u64* p : {E->q.h_res, E->q.h_keys, E->q.h_base, E->qa.h_state}) if (p) (void)hipHostFree(p);
+    for (u64* p : {E->q.h_res, E->q.h_keys, E->q.h_base, E->qa.h_state, E->qb.h_ts, E->qb.h_bins}) if (p) (void)hipHostFree(p);
     if (E->wb.h_cnt) (void)hipHostFree(E->wb.h_cnt);
     if (E->wb.stream) {
         (void)hipStreamSynchronize(E->wb.stream);
@@ -3479,6 +3499,17 @@ static bool query_filter_valid(const tbgpu_account_filter* f) {
     return true;
 }
 
+static QueryFilter query_account_filter_of(const tbgpu_account_filter* f) {
+    QueryFilter F{};
+    F.id_lo = f->account_id_lo;
+    F.id_hi = f->account_id_hi;
+    F.ts_min = f->timestamp_min;
+    F.ts_max = f->timestamp_max ? f->timestamp_max : ~0ULL;
+    F.debits = (f->flags & TBGPU_FILTER_DEBITS) != 0;
+    F.credits = (f->flags & TBGPU_FILTER_CREDITS) != 0;
+    return F;
+}
+
 extern "C" int tbgpu_get_account_transfers(tbgpu_t* E, const tbgpu_account_filter* filter, void* out,
                                            uint32_t out_cap_records, tbgpu_query_result* result) {
     API_ENTER(E, false);  // a read: legal on a stopped engine, like the exports
@@ -3486,13 +3517,7 @@ extern "C" int tbgpu_get_account_transfers(tbgpu_t* E, const tbgpu_account_filte
     result->count = 0;
     result->matched = 0;
     result->complete = 0;
-    QueryFilter F{};
-    F.id_lo = filter->account_id_lo;
-    F.id_hi = filter->account_id_hi;
-    F.ts_min = filter->timestamp_min;
-    F.ts_max = filter->timestamp_max ? filter->timestamp_max : ~0ULL;
-    F.debits = (filter->flags & TBGPU_FILTER_DEBITS) != 0;
-    F.credits = (filter->flags & TBGPU_FILTER_CREDITS) != 0;
+    const QueryFilter F = query_account_filter_of(filter);
     const bool reversed = (filter->flags & TBGPU_FILTER_REVERSED) != 0;
     const bool valid = query_filter_valid(filter);
     // One reply is one message body.
@@ -3508,6 +3533,103 @@ extern "C" int tbgpu_get_account_transfers(tbgpu_t* E, const tbgpu_account_filte
     if (st) return st;
     result->count = count;
     result->matched = matched;
+    return TBGPU_STATUS_OK;
+}
+
+// ---- get_account_balances (k_balances.h, include/tbgpu.h) -----------------------------------------
+// The rows are get_account_transfers' answer, left in `out`; the second scan runs in two halves like
+// the first, so that a node's shards scan side by side.  balance_enqueue: the rows' ascending
+// timestamps (in B.h_ts) go to the device, the bins are zeroed, tb_balance_effects runs over this
+// engine's log, and the k + 1 bins, the account's balances and the two flag words come back.
+// NT: every engine whose log may hold a post's pending transfer (a single engine: itself).
+static int balance_enqueue(tbgpu* E, const NodeTablesArgs& NT, u32 self, const QueryFilter& rows, u32 k) {
+    BalanceBufs& B = E->qb;
+    HIPCK(hipSetDevice(E->device));
+    QueryFilter F = rows;
+    F.debits = F.credits = 1;  // the flags and the window choose rows, not what is summed
+    F.ts_min = B.h_ts[0] + 1;
+    F.ts_max = ~0ULL;
+    const u64 n = E->log_next, per = (u64)QUERY_THREADS * BALANCE_TILES, nb = (n + per - 1) / per;
+    const u64 bytes = BALANCE_SLOTS(k) * BALANCE_SLOT_WORDS * 8;
+    HIPCK(hipMemcpyAsync(B.d_ts, B.h_ts, (u64)k * 8, hipMemcpyHostToDevice, E->stream));
+    HIPCK(hipMemsetAsync(B.d_bins, 0, bytes, E->stream));
+    // A shard without a record still answers for the account it may own: one workgroup.
+    hipLaunchKernelGGL(tb_balance_effects, dim3((unsigned)std::max<u64>(nb, 1)), dim3(QUERY_THREADS), 0, E->stream, NT, self, F,
+                       n, B.d_ts, k, B.d_bins);
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpyAsync(B.h_bins, B.d_bins, bytes, hipMemcpyDeviceToHost, E->stream));
+    return TBGPU_STATUS_OK;
+}
+
+static int balance_collect(tbgpu* E) {
+    HIPCK(hipSetDevice(E->device));
+    HIPCK(hipStreamSynchronize(E->stream));
+    return TBGPU_STATUS_OK;
+}
+
+// The k rows' ascending timestamps from the k records of an answer (their last word).
+static void balance_row_timestamps(const u8* out, u32 k, bool reversed, u64* ts) {
+    for (u32 i = 0; i < k; i++) memcpy(&ts[i], out + (u64)(reversed ? k - 1 - i : i) * 128 + 120, 8);
+}
+
+// bins: [k + 1][4] summed over every engine that scanned; cur: the account's current balances.  Row i
+// by timestamp holds cur minus the bins above i, per column modulo 2^128, and goes where record i was.
+static void balance_write_rows(u8* out, u32 k, bool reversed, const u64* ts, const u128* bins, const u128 cur[4]) {
+    u128 later[4] = {0, 0, 0, 0};
+    for (u32 i = k; i-- > 0;) {
+        tbgpu_account_balance row{};
+        u64* w = &row.debits_pending_lo;
+        for (u32 c = 0; c < 4; c++) {
+            later[c] += bins[((u64)i + 1) * 4 + c];
+            const u128 v = cur[c] - later[c];
+            w[2 * c] = (u64)v, w[2 * c + 1] = (u64)(v >> 64);
+        }
+        row.timestamp = ts[i];
+        memcpy(out + (u64)(reversed ? k - 1 - i : i) * 128, &row, 128);
+    }
+}
+
+static u128 balance_word(const u64* h_bins, u64 slot, u32 c) {
+    const u64* w = h_bins + slot * BALANCE_SLOT_WORDS + 2 * c;
+    return ((u128)w[1] << 64) | w[0];
+}
+
+extern "C" int tbgpu_get_account_balances(tbgpu_t* E, const tbgpu_account_filter* filter, void* out,
+                                          uint32_t out_cap_records, tbgpu_query_result* result) {
+    API_ENTER(E, false);  // a read, as tbgpu_get_account_transfers
+    if (!filter || !out || !result) return fail(TBGPU_STATUS_INVALID, "get_account_balances: a NULL filter, out or result");
+    result->count = 0;
+    result->matched = 0;
+    result->complete = 0;
+    const QueryFilter F = query_account_filter_of(filter);
+    const bool reversed = (filter->flags & TBGPU_FILTER_REVERSED) != 0;
+    const bool valid = query_filter_valid(filter);
+    const u32 k = std::min<u32>(std::min<u32>(filter->limit, out_cap_records), BATCH_EVENTS_MAX);
+    if (E->node) return node_account_balances(E->node, F, valid, k, reversed, (u8*)out, result);
+    result->complete = E->evicted_total == 0;
+    if (!valid) return TBGPU_STATUS_OK;
+    int st = query_enqueue(E, F, k, reversed);
+    if (st) return st;
+    u32 m = 0;
+    u64 matched = 0;
+    st = query_collect(E, (u8*)out, &m, &matched);
+    if (st) return st;
+    result->matched = matched;
+    if (m == 0) return TBGPU_STATUS_OK;
+    BalanceBufs& B = E->qb;
+    balance_row_timestamps((const u8*)out, m, reversed, B.h_ts);
+    NodeTablesArgs NT{};
+    NT.world = 1;
+    NT.T[0] = E->T;
+    if ((st = balance_enqueue(E, NT, 0, F, m)) || (st = balance_collect(E))) return st;
+    const u64* flags = B.h_bins + ((u64)m + 2) * BALANCE_SLOT_WORDS;
+    if (!flags[1]) return fail(TBGPU_STATUS_PANIC, "get_account_balances: transfers name an account the table lacks");
+    u128 cur[4];
+    for (u32 c = 0; c < 4; c++) cur[c] = balance_word(B.h_bins, (u64)m + 1, c);
+    // The bins in place as u128s: a slot is 4 x {lo, hi}, little-endian.
+    balance_write_rows((u8*)out, m, reversed, B.h_ts, (const u128*)B.h_bins, cur);
+    if (flags[0]) result->complete = 0;
+    result->count = m;
     return TBGPU_STATUS_OK;
 }
 

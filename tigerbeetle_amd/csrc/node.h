@@ -1758,6 +1758,56 @@ static int node_query_transfers(TbNode* N, const F& flt, bool valid, u32 k, bool
     return node_query_finish(N, false, k, reversed, out, result);
 }
 
+// get_account_balances: the rows are the merged get_account_transfers answer.  Every shard then gets
+// the merged rows' timestamps in its own pinned buffer and scans its own log on its own stream, side
+// by side; a post's pending transfer is read on home(pending_id) through the peers' tables, as
+// tb_node_import reads owners.  The host adds the shards' bins (modulo 2^128, like the device) and
+// anchors them at the balances the account's owner holds.  The sequencer's engine is not asked.
+static int node_account_balances(TbNode* N, const QueryFilter& F, bool valid, u32 k, bool reversed, u8* out,
+                                 tbgpu_query_result* result) {
+    int status = node_query_transfers(N, F, valid, k, reversed, out, result);
+    const u32 m = result->count;
+    result->count = 0;
+    if (status || m == 0) return status;
+    std::vector<u64> ts(m);
+    balance_row_timestamps(out, m, reversed, ts.data());
+    NodeTablesArgs NT{};
+    NT.world = N->world;
+    for (u32 d = 0; d < N->world; d++) NT.T[d] = N->D[d].E->T;
+    u32 issued = 0;
+    for (; issued < N->world && status == TBGPU_STATUS_OK; issued++) {
+        tbgpu* E = N->D[issued].E;
+        memcpy(E->qb.h_ts, ts.data(), (u64)m * 8);
+        status = balance_enqueue(E, NT, issued, F, m);
+    }
+    for (u32 d = 0; d < issued; d++) {  // every shard that launched is waited for
+        const int st = balance_collect(N->D[d].E);
+        if (st && status == TBGPU_STATUS_OK) status = st;
+    }
+    if (status) {
+        result->matched = 0;
+        return status;
+    }
+    std::vector<u128> bins(((u64)m + 1) * 4, 0);
+    bool orphan = false;
+    for (u32 d = 0; d < N->world; d++) {
+        const u64* h = N->D[d].E->qb.h_bins;
+        for (u64 i = 0; i < bins.size(); i++) bins[i] += ((u128)h[2 * i + 1] << 64) | h[2 * i];
+        orphan |= h[((u64)m + 2) * BALANCE_SLOT_WORDS] != 0;
+    }
+    const u64* owner = N->D[tb_home(F.id_lo, F.id_hi, N->world)].E->qb.h_bins;
+    if (!owner[((u64)m + 2) * BALANCE_SLOT_WORDS + 1]) {
+        result->matched = 0;
+        return fail(TBGPU_STATUS_PANIC, "get_account_balances: transfers name an account its owner lacks");
+    }
+    u128 cur[4];
+    for (u32 c = 0; c < 4; c++) cur[c] = balance_word(owner, (u64)m + 1, c);
+    balance_write_rows(out, m, reversed, ts.data(), bins.data(), cur);
+    if (orphan) result->complete = 0;
+    result->count = m;
+    return TBGPU_STATUS_OK;
+}
+
 // query_accounts: shard d answers for the accounts with tb_home(id, world) == d — a home's imported
 // copies of foreign accounts do not match, and the sequencer's engine (N->X) is not asked.
 static int node_query_accounts(TbNode* N, const QueryFieldFilter& F, bool valid, u32 k, bool reversed, u8* out,

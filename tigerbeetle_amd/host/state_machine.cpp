@@ -287,6 +287,13 @@ tbgpu_query_result StateMachine::get_account_transfers(const tbgpu_account_filte
     return r;
 }
 
+tbgpu_query_result StateMachine::get_account_balances(const tbgpu_account_filter& filter, void* out,
+                                                      uint32_t out_cap_records) {
+    tbgpu_query_result r{};
+    check(tbgpu_get_account_balances(engine_, &filter, out, out_cap_records, &r), "get_account_balances");
+    return r;
+}
+
 tbgpu_query_result StateMachine::query_transfers(const tbgpu_query_filter& filter, void* out, uint32_t out_cap_records) {
     tbgpu_query_result r{};
     check(tbgpu_query_transfers(engine_, &filter, out, out_cap_records, &r), "query_transfers");

@@ -234,6 +234,13 @@ public:
     // result.complete == 0: the engine has evicted transfers, and the caller merges with its forest.
     tbgpu_query_result get_account_transfers(const tbgpu_account_filter& filter, void* out, uint32_t out_cap_records);
 
+    // The balance history (tbgpu_get_account_balances; a read): one tbgpu_account_balance row per
+    // transfer get_account_transfers returns for the same filter, in the same order — the account's
+    // four balances right after that transfer, derived from the current balances and the resident
+    // log, whatever the account's flags.  result.complete == 0: transfers were evicted or a summed
+    // post had lost its pending transfer (tbgpu.h says when the rows are exact all the same).
+    tbgpu_query_result get_account_balances(const tbgpu_account_filter& filter, void* out, uint32_t out_cap_records);
+
     // The field-filter queries (tbgpu_query_transfers / tbgpu_query_accounts; reads, not commits): the
     // resident transfers, or the accounts, whose user_data_128 / user_data_64 / user_data_32 / ledger /
     // code equal the filter's non-zero fields, by timestamp (newest first under TBGPU_QUERY_REVERSED),

@@ -300,7 +300,9 @@ std::string run_table(tb::StateMachine& sm, const std::string& text) {
 // 16-byte tbgpu_query_result and the records.
 // --query-fields (tests/test_gpu_query_filter_cpp.py): the same files, the prepares ending in a
 // tbgpu_query_filter for query_transfers or query_accounts.
-enum QueryKind { ACCOUNT_TRANSFERS, QUERY_TRANSFERS, QUERY_ACCOUNTS };
+// --query-balances (tests/test_gpu_balances_cpp.py): --query's files, answered by get_account_balances
+// (the records are tbgpu_account_balance rows).
+enum QueryKind { ACCOUNT_TRANSFERS, ACCOUNT_BALANCES, QUERY_TRANSFERS, QUERY_ACCOUNTS };
 
 int run_query(tb::StateMachine& sm, QueryKind kind, const char* in_path, const char* out_path) {
     std::ifstream in(in_path, std::ios::binary);
@@ -334,6 +336,7 @@ int run_query(tb::StateMachine& sm, QueryKind kind, const char* in_path, const c
     memcpy(&q, body.data(), sizeof(q));
     std::vector<uint8_t> out((size_t)TBGPU_BATCH_EVENTS_MAX * 128);
     const tbgpu_query_result r = kind == ACCOUNT_TRANSFERS ? sm.get_account_transfers(f, out.data(), TBGPU_BATCH_EVENTS_MAX)
+                                 : kind == ACCOUNT_BALANCES ? sm.get_account_balances(f, out.data(), TBGPU_BATCH_EVENTS_MAX)
                                  : kind == QUERY_TRANSFERS ? sm.query_transfers(q, out.data(), TBGPU_BATCH_EVENTS_MAX)
                                                            : sm.query_accounts(q, out.data(), TBGPU_BATCH_EVENTS_MAX);
     std::ofstream o(out_path, std::ios::binary);
@@ -346,8 +349,9 @@ int run_query(tb::StateMachine& sm, QueryKind kind, const char* in_path, const c
 
 int main(int argc, char** argv) {
     const bool fields = argc > 1 && std::string(argv[1]) == "--query-fields";
-    const bool query = fields || (argc > 1 && std::string(argv[1]) == "--query");
-    QueryKind kind = ACCOUNT_TRANSFERS;
+    const bool balances = argc > 1 && std::string(argv[1]) == "--query-balances";
+    const bool query = fields || balances || (argc > 1 && std::string(argv[1]) == "--query");
+    QueryKind kind = balances ? ACCOUNT_BALANCES : ACCOUNT_TRANSFERS;
     const char* self = argv[0];
     if (fields && argc > 2) {
         const std::string which = argv[2];
@@ -358,8 +362,9 @@ int main(int argc, char** argv) {
     if (argc < 2 || (query && argc < 4)) {
         fprintf(stderr,
                 "usage: %s <state_machine_tables.txt> [device]\n       %s --query <prepares.bin> <answer.bin> [device]\n"
+                "       %s --query-balances <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-fields <transfers|accounts> <prepares.bin> <answer.bin> [device]\n",
-                self, self, self);
+                self, self, self, self);
         return 2;
     }
     if (query) {

@@ -22,7 +22,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from .types import (ACCOUNT_DTYPE, ACCOUNT_FILTER_DTYPE, BATCH_MAX, FILTER_CREDITS, FILTER_DEBITS, FILTER_REVERSED,
+from .types import (ACCOUNT_BALANCE_DTYPE, ACCOUNT_DTYPE, ACCOUNT_FILTER_DTYPE, BATCH_MAX, FILTER_CREDITS, FILTER_DEBITS, FILTER_REVERSED,
                     QUERY_FILTER_DTYPE, QUERY_REVERSED, TRANSFER_DTYPE, U64_MAX, Operation)
 
 
@@ -245,25 +245,51 @@ class Engine:
         Returns (records ndarray of TRANSFER_DTYPE, matched, complete): `matched` counts every match
         before the limit; `complete` is False once the engine has evicted transfers (the caller
         merges with its forest).  An invalid filter matches nothing."""
+        f = self.account_filter(account_id, debits, credits, reversed, timestamp_min, timestamp_max, limit)
+        return self.get_account_transfers_raw(f, out_cap_records)
+
+    @staticmethod
+    def account_filter(account_id, debits=True, credits=True, reversed=False, timestamp_min=0, timestamp_max=0,
+                       limit=8190):
+        """The 64 bytes of a tbgpu_account_filter (ACCOUNT_FILTER_DTYPE)."""
         f = np.zeros(1, dtype=ACCOUNT_FILTER_DTYPE)
         f["account_id_lo"], f["account_id_hi"] = account_id & U64_MAX, account_id >> 64
         f["timestamp_min"], f["timestamp_max"], f["limit"] = timestamp_min, timestamp_max, limit
         f["flags"] = ((FILTER_DEBITS if debits else 0) | (FILTER_CREDITS if credits else 0)
                       | (FILTER_REVERSED if reversed else 0))
-        return self.get_account_transfers_raw(f.tobytes(), out_cap_records)
+        return f.tobytes()
 
     def get_account_transfers_raw(self, filter_bytes, out_cap_records=None):
         """The same query from the 64 bytes of a tbgpu_account_filter (ACCOUNT_FILTER_DTYPE)."""
+        return self._account_filter_raw(self.lib.tbgpu_get_account_transfers, TRANSFER_DTYPE, filter_bytes, out_cap_records)
+
+    def _account_filter_raw(self, fn, dtype, filter_bytes, out_cap_records):
         filter_bytes = bytes(filter_bytes)
         if len(filter_bytes) != ACCOUNT_FILTER_DTYPE.itemsize:
             raise ValueError("an account filter is %d bytes" % ACCOUNT_FILTER_DTYPE.itemsize)
         limit = int(np.frombuffer(filter_bytes, dtype=ACCOUNT_FILTER_DTYPE)["limit"][0])
         cap = min(limit, BATCH_MAX) if out_cap_records is None else int(out_cap_records)
-        out = np.zeros(max(cap, 1), dtype=TRANSFER_DTYPE)
+        out = np.zeros(max(cap, 1), dtype=dtype)
         res = _lib.tbgpu_query_result()
         src = ctypes.create_string_buffer(filter_bytes, len(filter_bytes))
-        _lib.check(self.lib.tbgpu_get_account_transfers(self.h, src, out.ctypes.data, cap, ctypes.byref(res)))
+        _lib.check(fn(self.h, src, out.ctypes.data, cap, ctypes.byref(res)))
         return out[:res.count], int(res.matched), bool(res.complete)
+
+    def get_account_balances(self, account_id, *, debits=True, credits=True, reversed=False, timestamp_min=0,
+                             timestamp_max=0, limit=8190, out_cap_records=None):
+        """The balances of `account_id` right after each transfer get_account_transfers returns for
+        the same keywords (tbgpu_get_account_balances), in the same order: derived from the current
+        balances and the resident log, whatever the account's flags.  Returns (rows ndarray of
+        ACCOUNT_BALANCE_DTYPE, matched, complete); `complete` is False once the engine has evicted
+        transfers or a post in a sum had lost its pending transfer (tbgpu.h says when the rows are
+        exact all the same)."""
+        f = self.account_filter(account_id, debits, credits, reversed, timestamp_min, timestamp_max, limit)
+        return self.get_account_balances_raw(f, out_cap_records)
+
+    def get_account_balances_raw(self, filter_bytes, out_cap_records=None):
+        """get_account_balances from the 64 bytes of a tbgpu_account_filter."""
+        return self._account_filter_raw(self.lib.tbgpu_get_account_balances, ACCOUNT_BALANCE_DTYPE, filter_bytes,
+                                        out_cap_records)
 
     @staticmethod
     def query_filter(user_data_128=0, user_data_64=0, user_data_32=0, ledger=0, code=0, *, reversed=False,
@@ -620,6 +646,10 @@ class StateMachine:
         """The account-filter query (Engine.get_account_transfers): a read, no operation number in
         the reference's enum, so it does not go through commit."""
         return self.engine.get_account_transfers(account_id, **filter)
+
+    def get_account_balances(self, account_id, **filter):
+        """The balance history of one account (Engine.get_account_balances): a read, not a commit."""
+        return self.engine.get_account_balances(account_id, **filter)
 
     def query_transfers(self, **filter):
         """The field-filter query over transfers (Engine.query_transfers): a read, not a commit."""

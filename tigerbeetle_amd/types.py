@@ -108,6 +108,12 @@ ACCOUNT_FILTER_DTYPE = np.dtype(
 assert ACCOUNT_FILTER_DTYPE.itemsize == 64
 FILTER_DEBITS, FILTER_CREDITS, FILTER_REVERSED = 1, 2, 4
 
+# tbgpu_account_balance (include/tbgpu.h tbgpu_get_account_balances): 128 bytes, no padding.
+ACCOUNT_BALANCE_DTYPE = np.dtype(
+    _u128("debits_pending") + _u128("debits_posted") + _u128("credits_pending") + _u128("credits_posted")
+    + [("timestamp", "<u8"), ("reserved", "u1", (56,))])
+assert ACCOUNT_BALANCE_DTYPE.itemsize == 128
+
 # tbgpu_query_filter (include/tbgpu.h tbgpu_query_transfers / tbgpu_query_accounts): 64 bytes, no padding.
 QUERY_FILTER_DTYPE = np.dtype(
     _u128("user_data_128") + [("user_data_64", "<u8"), ("user_data_32", "<u4"), ("ledger", "<u4"), ("code", "<u2"),

@@ -1,7 +1,7 @@
 """The account-filter scan (tbgpu_get_account_transfers, csrc/k_query.h) over a 16M-transfer log (2 GB)
 against a device-to-device copy of the same log range, in one process.
 
-usage: python tools/gpu/query_scan.py [transfers] [runs] [--only account|fields]
+usage: python tools/gpu/query_scan.py [transfers] [runs] [--only account|fields|balances]
 
 The log is built by the device generator, committed in place (the way tools/gpu/device_pass.py builds
 a pass): once with uniform C2 ids, where the queried account is a cold one (a few dozen matches), and
@@ -17,6 +17,10 @@ filter (ledger only), a selective one with more matches than the limit, and one 
 device-to-device copy of 64 B x slots (the hot and cold entries the scan reads), with the number of
 table scans the select made.  `--only account` measures the account filter alone (an older library
 loaded through TBGPU_AB_LIB has nothing else), `--only fields` the field filters alone.
+
+`--only balances` (tbgpu_get_account_balances) times get_account_balances beside
+get_account_transfers with the same filter on both logs, both directions, limit 8190: it scans the log
+once more, so the bar is about twice the time (explain a cold-account ratio above 2.5).
 """
 import json
 import os
@@ -55,7 +59,7 @@ def rates(ms):
     return dict(ms=round(ms, 4), log_gbs=round(n_xfer * 128 / ms / 1e6, 1), needed_gbs=round(n_xfer * 40 / ms / 1e6, 1))
 
 
-def measure(coop):
+def measure(coop, balances=False):
     os.environ["TBGPU_QUERY_COOP"] = "1" if coop else "0"
     e = Engine(Options(accounts_max=n_acct, transfers_max=n_xfer, pass_events_max=pb * batch, pass_batches_max=pb))
     a_lens = batches(n_acct, batch)
@@ -95,6 +99,13 @@ def measure(coop):
             out["%s_%s" % (name, "reversed" if rev else "ascending")] = dict(rates(med), min_ms=round(lo_ms, 4),
                                                                              max_ms=round(hi_ms, 4), matched=matched,
                                                                              count=len(recs))
+            if balances:
+                rows, b_matched, b_complete = e.get_account_balances(account, reversed=rev, limit=8190)
+                assert b_complete and b_matched == matched and np.array_equal(rows["timestamp"], recs["timestamp"])
+                b_med, b_lo, b_hi = timed(e, lambda: e.get_account_balances(account, reversed=rev, limit=8190))
+                out["%s_%s" % (name, "reversed" if rev else "ascending")].update(
+                    balances_ms=round(b_med, 4), balances_min_ms=round(b_lo, 4), balances_max_ms=round(b_hi, 4),
+                    balances_over_transfers=round(b_med / med, 2))
         if name == "uniform_cold":
             med, lo_ms, hi_ms = timed(e, lambda: e.copy_device_async(spare, log, n_xfer * 128))
             out["copy_d2d"] = dict(rates(med), min_ms=round(lo_ms, 4), max_ms=round(hi_ms, 4))
@@ -165,11 +176,13 @@ def measure_fields():
 
 
 result = dict(transfers=n_xfer, log_bytes=n_xfer * 128, runs=runs, warmups=WARMUPS)
-if only != "fields":
+if only == "balances":
+    result["balances"] = measure(False, balances=True)
+elif only != "fields":
     result.update(lane_per_record=measure(False), cooperative=measure(True))
     for shape in ("lane_per_record", "cooperative"):
         r = result[shape]
         r["bar_query_le_copy"] = all(v["ms"] <= r["copy_d2d"]["ms"] for k, v in r.items() if k != "copy_d2d")
-if only != "account":
+if only not in ("account", "balances"):
     result["field_filters"] = measure_fields()
 print(json.dumps(result))
