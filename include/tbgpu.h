@@ -21,6 +21,7 @@
  *     index trees (:103-169; likewise unread)                (likewise)
  *   (later references: the account_balances groove)        tbgpu_get_account_balances (likewise;
  *                                                             derived from the log, nothing stored)
+ *   (later references: get_change_events)                  tbgpu_get_change_events (likewise)
  *   `setup` action of the table tests (:1398-1407)         tbgpu_test_set_balances (test only)
  *   StateMachine.commit_timestamp field (:251)             tbgpu_commit_timestamp
  *
@@ -425,6 +426,61 @@ int tbgpu_query_transfers(tbgpu_t* engine, const tbgpu_query_filter* filter, voi
                           tbgpu_query_result* result);
 int tbgpu_query_accounts(tbgpu_t* engine, const tbgpu_query_filter* filter, void* out, uint32_t out_cap_records,
                          tbgpu_query_result* result);
+
+/* get_change_events: the ledger's change stream — every committed transfer in a timestamp window, in
+ * timestamp order, with both of its accounts as they stood right after it.  Later references keep a
+ * groove for it; this engine stores nothing at commit and derives the account blocks from the log in
+ * HBM and the current balances, as tbgpu_get_account_balances does for one account.  An entry point
+ * of its own, as above; this comment is its specification.
+ *   Which events: exactly the transfers tbgpu_query_transfers returns for a filter whose fields are
+ *     all zero, with the same window, ascending by timestamp (there is no REVERSED), under
+ *     k = min(limit, out_cap_events, TBGPU_CHANGE_EVENTS_MAX).  `matched` and the liveness rules are
+ *     that call's.  Post and void records carry their pending transfer's account ids (the log stores
+ *     them so).  The event's kind is read from the transfer's flags; there is no expired kind, as this
+ *     reference never expires a pending transfer ("Timeouts").  A consumer pages with
+ *     timestamp_min = the last event's timestamp + 1.
+ *   The account blocks: an account's fields other than its four balances never change after it was
+ *     created, so a block is the account's current record with the four balances replaced by the
+ *     balances right after the event.  For event r and account a, per column modulo 2^128,
+ *       balance_after(r, a) = current(a) - the sum of the effects on a of every live resident record
+ *                             that names a and has a timestamp strictly above r's,
+ *     with the effect table and the P rule of tbgpu_get_account_balances (a post whose pending transfer
+ *     is not resident is summed with P = its own amount).  The anchor is the current balance: the
+ *     blocks stay exact after eviction of an old prefix, after tbgpu_load_accounts and after
+ *     tbgpu_test_set_balances; events older than such a step follow this definition, not the ledger's
+ *     past.  An account the table does not hold (transfers loaded without their accounts) yields an
+ *     all-zero block.
+ *   complete: 1 only when no transfer was ever evicted, every post that entered a sum found its
+ *     pending transfer resident, and every account named by a returned event was found.
+ *   Invalid filters are never a status: timestamp_min or timestamp_max 2^64-1, a non-zero
+ *     timestamp_max below timestamp_min, limit 0, a non-zero reserved byte — each returns
+ *     TBGPU_STATUS_OK with count = matched = 0.  A NULL filter, out or result is TBGPU_STATUS_INVALID.
+ *   The call contract of tbgpu_get_account_transfers: synchronous, drains a pending
+ *     tbgpu_commit_device_async first, changes nothing, works on an engine a device panic stopped,
+ *     allocates nothing (every buffer is made in tbgpu_init), legal beside an asynchronous write-back.
+ *     It scans the log once more than tbgpu_query_transfers does.
+ *   A node engine has the same contract: the events are the merged answer; every home shard sums the
+ *     effects of its own log on its own device and stream, reading a post's pending transfer on the
+ *     home shard of its pending_id; the host adds the shards' sums; each account's record comes from
+ *     its owner shard. */
+#define TBGPU_CHANGE_EVENTS_MAX 2730u   /* 384 B events in one message body: 2730*384 <= 8191*128 */
+
+typedef struct tbgpu_change_events_filter {   /* 64 bytes, little-endian, no padding */
+    uint64_t timestamp_min;   /* inclusive; 0 = open */
+    uint64_t timestamp_max;   /* inclusive; 0 = open */
+    uint32_t limit;
+    uint8_t  reserved[44];    /* must be zero */
+} tbgpu_change_events_filter;
+
+typedef struct tbgpu_change_event {           /* 384 bytes, no padding */
+    uint8_t transfer[128];        /* the bytes lookup_transfers returns for this id */
+    uint8_t debit_account[128];   /* the bytes lookup_accounts would have returned for the record's
+                                     debit account right after this transfer committed */
+    uint8_t credit_account[128];  /* likewise, its credit account */
+} tbgpu_change_event;
+
+int tbgpu_get_change_events(tbgpu_t* engine, const tbgpu_change_events_filter* filter, void* out,
+                            uint32_t out_cap_events, tbgpu_query_result* result);
 
 /* The replica writes StateMachine.commit_timestamp itself: the header timestamp after every commit
  * (src/vsr/replica.zig:3664-3665) and the checkpoint's value on open / state sync.  The wrapper

@@ -63,6 +63,19 @@ class tbgpu_query_result(ctypes.Structure):
     _fields_ = [("count", ctypes.c_uint32), ("complete", ctypes.c_uint32), ("matched", ctypes.c_uint64)]
 
 
+class tbgpu_change_events_filter(ctypes.Structure):
+    _fields_ = [("timestamp_min", ctypes.c_uint64), ("timestamp_max", ctypes.c_uint64), ("limit", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint8 * 44)]
+
+
+class tbgpu_change_event(ctypes.Structure):
+    _fields_ = [("transfer", ctypes.c_uint8 * 128), ("debit_account", ctypes.c_uint8 * 128),
+                ("credit_account", ctypes.c_uint8 * 128)]
+
+
+CHANGE_EVENTS_MAX = 2730  # TBGPU_CHANGE_EVENTS_MAX
+
+
 class tbgpu_stats(ctypes.Structure):
     _fields_ = [
         ("passes", ctypes.c_uint64),
@@ -183,6 +196,7 @@ SIGNATURES = [
     ("tbgpu_export_posted", ctypes.c_int, [_P, _P, _U64, ctypes.POINTER(_U64)]),
     ("tbgpu_get_account_transfers", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_get_account_balances", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
+    ("tbgpu_get_change_events", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_query_transfers", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_query_accounts", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_bench_query_keys_max", ctypes.c_int, [_P, _U32]),

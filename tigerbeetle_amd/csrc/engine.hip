@@ -35,6 +35,7 @@
 #include "k_query.h"
 #include "k_query_filter.h"
 #include "k_balances.h"
+#include "k_change_events.h"
 #include "checksum.h"
 
 static thread_local std::string g_err;
@@ -191,6 +192,30 @@ struct BalanceBufs {
     u64* h_ts = nullptr;    // pinned mirror (a node hands every shard the merged rows' here)
     u64* d_bins = nullptr;  // [BALANCE_SLOTS(BATCH_EVENTS_MAX)][BALANCE_SLOT_WORDS]
     u64* h_bins = nullptr;  // pinned mirror
+};
+
+// tbgpu_get_change_events (k_change_events.h): the page's account set, the bins, the accounts' records
+// and the post rows' pending amounts, on the device and pinned; made at tbgpu_init after every other
+// buffer and shared with nothing.  The rows themselves are chosen through QueryBufs.
+struct ChangeBufs {
+    u32* d_set = nullptr;     // [CHANGE_SET_SLOTS_MAX] the set's entries
+    u64* d_ids = nullptr;     // [CHANGE_ACCOUNTS_MAX][2] the accounts' ids by index
+    u64* d_pids = nullptr;    // [CHANGE_EVENTS_MAX][2] the post rows' pending ids
+    u64* d_bins = nullptr;    // [CHANGE_ACCOUNTS_MAX + 1][BALANCE_SLOT_WORDS] the bins, then the flag slot
+    u8* d_accounts = nullptr; // [CHANGE_ACCOUNTS_MAX] the accounts' records
+    u32* d_found = nullptr;   // [CHANGE_ACCOUNTS_MAX] ... and whether the owner holds them
+    u64* d_p = nullptr;       // [CHANGE_EVENTS_MAX][2] the post rows' pending amounts
+    u32* d_found_p = nullptr; // [CHANGE_EVENTS_MAX] ... and whether the pending transfer is resident
+    u32* h_set = nullptr;     // pinned mirrors (a node hands every shard the page's set here)
+    u64* h_ids = nullptr;
+    u64* h_pids = nullptr;
+    u64* h_bins = nullptr;
+    u8* h_accounts = nullptr;
+    u32* h_found = nullptr;
+    u64* h_p = nullptr;
+    u32* h_found_p = nullptr;
+    u8* h_rows = nullptr;     // pinned [CHANGE_EVENTS_MAX] the rows, before they are assembled into `out`
+    u32* h_row_idx = nullptr; // host [CHANGE_EVENTS_MAX][2] the rows' debit and credit account index
 };
 
 // tbgpu_query_accounts (k_query_filter.h): O(slots / 256 + histogram + k) device memory, made at
@@ -357,6 +382,7 @@ struct tbgpu {
     u64* h_rmeta = nullptr;   // pinned mirror
     AccountQueryBufs qa;
     BalanceBufs qb;
+    ChangeBufs qc;
 };
 
 // The write-back snapshot as a balance view (its two planes, like T.bal).
@@ -590,6 +616,7 @@ static int node_query_accounts(TbNode* N, const QueryFieldFilter& F, bool valid,
                                tbgpu_query_result* result);
 static int node_account_balances(TbNode* N, const QueryFilter& F, bool valid, u32 k, bool reversed, u8* out,
                                  tbgpu_query_result* result);
+static int node_change_events(TbNode* N, const QueryFieldFilter& F, bool valid, u32 k, u8* out, tbgpu_query_result* result);
 
 extern "C" int tbgpu_init(const tbgpu_config* config, tbgpu_t** out) {
     if (config && config->device_count > 1) return node_api_init(config, out);
@@ -898,6 +925,28 @@ extern "C" int tbgpu_init(const tbgpu_config* config, tbgpu_t** out) {
         INIT_CK(tbMalloc(&A.d_keys, (u64)BATCH_EVENTS_MAX * 16));
         INIT_CK(tbMalloc(&A.d_out, (u64)BATCH_EVENTS_MAX * 128));
     }
+    {  // tbgpu_get_change_events: the set, the bins, the accounts, the pending amounts, the rows
+        ChangeBufs& C = E->qc;
+        const u64 na = CHANGE_ACCOUNTS_MAX, nr = CHANGE_EVENTS_MAX;
+        INIT_CK(tbMalloc(&C.d_set, (u64)CHANGE_SET_SLOTS_MAX * 4));
+        INIT_CK(tbMalloc(&C.d_ids, na * 16));
+        INIT_CK(tbMalloc(&C.d_pids, nr * 16));
+        INIT_CK(tbMalloc(&C.d_bins, (na + 1) * BALANCE_SLOT_WORDS * 8));
+        INIT_CK(tbMalloc(&C.d_accounts, na * 128));
+        INIT_CK(tbMalloc(&C.d_found, na * 4));
+        INIT_CK(tbMalloc(&C.d_p, nr * 16));
+        INIT_CK(tbMalloc(&C.d_found_p, nr * 4));
+        INIT_CK(tbHostMalloc(&C.h_set, (u64)CHANGE_SET_SLOTS_MAX * 4, hipHostMallocDefault));
+        INIT_CK(tbHostMalloc(&C.h_ids, na * 16, hipHostMallocDefault));
+        INIT_CK(tbHostMalloc(&C.h_pids, nr * 16, hipHostMallocDefault));
+        INIT_CK(tbHostMalloc(&C.h_bins, (na + 1) * BALANCE_SLOT_WORDS * 8, hipHostMallocDefault));
+        INIT_CK(tbHostMalloc(&C.h_accounts, na * 128, hipHostMallocDefault));
+        INIT_CK(tbHostMalloc(&C.h_found, na * 4, hipHostMallocDefault));
+        INIT_CK(tbHostMalloc(&C.h_p, nr * 16, hipHostMallocDefault));
+        INIT_CK(tbHostMalloc(&C.h_found_p, nr * 4, hipHostMallocDefault));
+        INIT_CK(tbHostMalloc(&C.h_rows, nr * 128, hipHostMallocDefault));
+        INIT_CK(tbHostMalloc(&C.h_row_idx, nr * 8, hipHostMallocDefault));
+    }
 #undef INIT_CK
     st = engine_clear(E);
     if (st == TBGPU_STATUS_OK && E->flow_ok) st = residency_probe(E, flow_grid(E));
@@ -932,7 +981,8 @@ extern "C" void tbgpu_deinit(tbgpu_t* E) {
                     E->F.f_pe, E->F.f_batch, E->F.f_len, E->F.need, E->F.nsucc, E->F.queue, E->F.uflags, E->F.nacct, E->F.rpos, E->F.succ,
                     E->F.run, E->F.keys[0], E->F.keys[1], E->F.vals[0], E->F.vals[1], E->F.hist, E->F.words, E->F.undo,
                     E->F.b_st, E->F.b_vd, E->F.b_vc, E->F.b_amt, E->F.b_meta, E->F.b_blk,
-                    E->F.b_qd, E->F.b_qc, E->F.b_head, E->F.b_xy, E->F.b_ex, E->F.b_rec, E->F.b_vw};
+                    E->F.b_qd, E->F.b_qc, E->F.b_head, E->F.b_xy, E->F.b_ex, E->F.b_rec, E->F.b_vw,
+                    E->qc.d_set, E->qc.d_ids, E->qc.d_pids, E->qc.d_bins, E->qc.d_accounts, E->qc.d_found, E->qc.d_p, E->qc.d_found_p};
     for (void* p : bufs) if (p) (void)hipFree(p);
     for (int k = 0; k < PIPE_SLOTS; k++) {
         tbgpu::PipeSlot& S = E->pipe[k];
@@ -951,6 +1001,10 @@ extern "C" void tbgpu_deinit(tbgpu_t* E) {
     if (E->h_kclock) (void)hipHostFree(E->h_kclock);
     if (E->h_pub) (void)hipHostFree(E->h_pub);
     for (u64* p : {E->q.h_res, E->q.h_keys, E->q.h_base, E->qa.h_state, E->qb.h_ts, E->qb.h_bins}) if (p) (void)hipHostFree(p);
+    for (void* p : {(void*)E->qc.h_set, (void*)E->qc.h_ids, (void*)E->qc.h_pids, (void*)E->qc.h_bins, (void*)E->qc.h_accounts,
+                    (void*)E->qc.h_found, (void*)E->qc.h_p, (void*)E->qc.h_found_p, (void*)E->qc.h_rows, (void*)E->qc.h_row_idx}) {
+        if (p) (void)hipHostFree(p);
+    }
     if (E->wb.h_cnt) (void)hipHostFree(E->wb.h_cnt);
     if (E->wb.stream) {
         (void)hipStreamSynchronize(E->wb.stream);
@@ -3739,6 +3793,208 @@ static int account_query_collect(tbgpu* E, u8* out, u32* count, u64* matched) {
     HIPCK(hipStreamSynchronize(E->stream));
     *count = m;
     return TBGPU_STATUS_OK;
+}
+
+// ---- get_change_events (k_change_events.h, include/tbgpu.h) ---------------------------------------
+// The rows are query_transfers' answer for an all-zero field filter.  change_events_finish takes them
+// (m > 0, ascending by timestamp, on the host) with the engines whose logs hold the ledger — one, or a
+// node's shards — and writes the m events into `out`:
+//   the set      the rows' distinct accounts, an index each, in an open-addressing table the host
+//                builds in Es[0]'s pinned buffers (a node copies it into every shard's);
+//   the scans    every engine, on its own device and stream, side by side: set and ids up, bins zeroed,
+//                tb_change_effects over its own log for the records above the last row, bins back;
+//   the gather   Es[0]'s stream: each account's record from its owner, each post row's pending amount
+//                from home(pending_id), through the peers' tables as tb_balance_effects reads them;
+//   the walk     end(a) = current(a) - the engines' bins; the rows from the newest to the oldest, each
+//                written with its two accounts' balances and then taken out of them.
+static u32 change_set_insert(u32* set, u32 mask, u64* ids, u32* count, u64 lo, u64 hi) {
+    const u64 h = tb_change_hash(lo, hi);
+    const u32 tag = (u32)(h >> 48);
+    u32 s = (u32)h & mask;
+    for (;;) {  // the table is at most half full: an empty slot ends the probe
+        const u32 e = set[s];
+        if (e == 0) break;
+        if ((e >> 16) == tag) {
+            const u32 index = (e & 0xFFFFu) - 1;
+            if (ids[2 * (u64)index] == lo && ids[2 * (u64)index + 1] == hi) return index;
+        }
+        s = (s + 1) & mask;
+    }
+    const u32 index = (*count)++;
+    ids[2 * (u64)index] = lo, ids[2 * (u64)index + 1] = hi;
+    set[s] = tb_change_entry(h, index);
+    return index;
+}
+
+static u64 change_row_word(const u8* row, u32 word) {
+    u64 v;
+    memcpy(&v, row + 8 * word, 8);
+    return v;
+}
+
+static int change_events_finish(tbgpu* const* Es, u32 world, const u8* rows, u32 m, u8* out, tbgpu_query_result* result) {
+    ChangeBufs& C = Es[0]->qc;
+    u32 slots = tb_change_set_slots(2 * m), mask = slots - 1;  // for now: the accounts are at most 2m
+    memset(C.h_set, 0, (u64)slots * 4);
+    u32 na = 0;
+    for (u32 i = 0; i < m; i++) {
+        const u8* r = rows + (u64)i * 128;
+        for (u32 side = 0; side < 2; side++) {
+            C.h_row_idx[2 * i + side] =
+                change_set_insert(C.h_set, mask, C.h_ids, &na, change_row_word(r, 2 + 2 * side), change_row_word(r, 3 + 2 * side));
+        }
+        const u32 tf = (u32)(change_row_word(r, 14) >> 48);
+        const bool post = !(tf & TF_PENDING) && (tf & TF_POST);
+        C.h_pids[2 * (u64)i] = post ? change_row_word(r, 8) : 0;
+        C.h_pids[2 * (u64)i + 1] = post ? change_row_word(r, 9) : 0;
+    }
+    if (tb_change_set_slots(na) < slots) {  // fewer distinct accounts: the smaller table, the same indices
+        slots = tb_change_set_slots(na), mask = slots - 1;
+        memset(C.h_set, 0, (u64)slots * 4);
+        u32 again = 0;
+        for (u32 a = 0; a < na; a++) change_set_insert(C.h_set, mask, C.h_ids, &again, C.h_ids[2 * (u64)a], C.h_ids[2 * (u64)a + 1]);
+    }
+    const u32 lds_bins = tb_change_lds_bins(slots);
+    const u64 t_last = change_row_word(rows + (u64)(m - 1) * 128, 15);
+    const u64 bin_bytes = ((u64)na + 1) * BALANCE_SLOT_WORDS * 8;
+    NodeTablesArgs NT{};
+    NT.world = world;
+    for (u32 d = 0; d < world; d++) NT.T[d] = Es[d]->T;
+    int status = TBGPU_STATUS_OK;
+    u32 issued = 0;
+    auto enqueue = [&](u32 d) -> int {
+        tbgpu* E = Es[d];
+        ChangeBufs& D = E->qc;
+        HIPCK(hipSetDevice(E->device));
+        if (d) {
+            memcpy(D.h_set, C.h_set, (u64)slots * 4);
+            memcpy(D.h_ids, C.h_ids, (u64)na * 16);
+        }
+        HIPCK(hipMemcpyAsync(D.d_set, D.h_set, (u64)slots * 4, hipMemcpyHostToDevice, E->stream));
+        HIPCK(hipMemcpyAsync(D.d_ids, D.h_ids, (u64)na * 16, hipMemcpyHostToDevice, E->stream));
+        HIPCK(hipMemsetAsync(D.d_bins, 0, bin_bytes, E->stream));
+        const u64 n = E->log_next, per = (u64)CHANGE_THREADS * CHANGE_TILES, nb = (n + per - 1) / per;
+        if (nb) {
+            hipLaunchKernelGGL(tb_change_effects, dim3((unsigned)nb), dim3(CHANGE_THREADS),
+                               (size_t)slots * 4 + (size_t)lds_bins * BALANCE_SLOT_WORDS * 8, E->stream, NT, d, n, t_last,
+                               (const u32*)D.d_set, mask, (const u64*)D.d_ids, na, D.d_bins, lds_bins);
+            HIPCK(hipGetLastError());
+        }
+        HIPCK(hipMemcpyAsync(D.h_bins, D.d_bins, bin_bytes, hipMemcpyDeviceToHost, E->stream));
+        if (d == 0) {
+            HIPCK(hipMemcpyAsync(D.d_pids, D.h_pids, (u64)m * 16, hipMemcpyHostToDevice, E->stream));
+            hipLaunchKernelGGL(tb_change_gather, dim3((std::max(na, m) + QUERY_THREADS - 1) / QUERY_THREADS), dim3(QUERY_THREADS), 0,
+                               E->stream, NT, (const u64*)D.d_ids, na, D.d_accounts, D.d_found, (const u64*)D.d_pids, m, D.d_p,
+                               D.d_found_p);
+            HIPCK(hipGetLastError());
+            HIPCK(hipMemcpyAsync(D.h_accounts, D.d_accounts, (u64)na * 128, hipMemcpyDeviceToHost, E->stream));
+            HIPCK(hipMemcpyAsync(D.h_found, D.d_found, (u64)na * 4, hipMemcpyDeviceToHost, E->stream));
+            HIPCK(hipMemcpyAsync(D.h_p, D.d_p, (u64)m * 16, hipMemcpyDeviceToHost, E->stream));
+            HIPCK(hipMemcpyAsync(D.h_found_p, D.d_found_p, (u64)m * 4, hipMemcpyDeviceToHost, E->stream));
+        }
+        return TBGPU_STATUS_OK;
+    };
+    auto wait = [&](u32 d) -> int {
+        HIPCK(hipSetDevice(Es[d]->device));
+        HIPCK(hipStreamSynchronize(Es[d]->stream));
+        return TBGPU_STATUS_OK;
+    };
+    for (; issued < world && status == TBGPU_STATUS_OK; issued++) status = enqueue(issued);
+    for (u32 d = 0; d < issued; d++) {  // every engine that launched is waited for
+        const int st = wait(d);
+        if (st && status == TBGPU_STATUS_OK) status = st;
+    }
+    if (status) return status;
+    bool complete = result->complete != 0;
+    // end(a): into Es[0]'s bins in place, as u128s (a slot is 4 x {lo, hi}, little-endian).
+    u128* bal = (u128*)C.h_bins;
+    for (u32 d = 0; d < world; d++) complete &= Es[d]->qc.h_bins[(u64)na * BALANCE_SLOT_WORDS + CHANGE_FLAG_ORPHAN] == 0;
+    for (u32 a = 0; a < na; a++) {
+        const u8* rec = C.h_accounts + (u64)a * 128;
+        for (u32 c = 0; c < 4; c++) {
+            u128 sum = bal[(u64)a * 4 + c];
+            for (u32 d = 1; d < world; d++) sum += ((const u128*)Es[d]->qc.h_bins)[(u64)a * 4 + c];
+            const u128 cur = C.h_found[a] ? tb_u128(change_row_word(rec, 2 + 2 * c), change_row_word(rec, 3 + 2 * c)) : (u128)0;
+            bal[(u64)a * 4 + c] = cur - sum;
+        }
+        complete &= C.h_found[a] != 0;
+    }
+    for (u32 i = m; i-- > 0;) {
+        const u8* r = rows + (u64)i * 128;
+        u8* ev = out + (u64)i * 384;
+        memcpy(ev, r, 128);
+        for (u32 side = 0; side < 2; side++) {
+            const u32 a = C.h_row_idx[2 * i + side];
+            u8* block = ev + 128 + 128 * side;
+            if (!C.h_found[a]) {
+                memset(block, 0, 128);
+                continue;
+            }
+            memcpy(block, C.h_accounts + (u64)a * 128, 128);
+            memcpy(block + 16, &bal[(u64)a * 4], 64);
+        }
+        // The row's own effect leaves its two accounts: the balances of the next older row.
+        const u128 amount = tb_u128(change_row_word(r, 6), change_row_word(r, 7));
+        const u32 tf = (u32)(change_row_word(r, 14) >> 48);
+        u128 pend = 0, post = 0;
+        if (tf & TF_PENDING) {
+            pend = amount;
+        } else if (tf & TF_POST) {
+            u128 p = amount;
+            if (C.h_found_p[i]) p = tb_u128(C.h_p[2 * (u64)i], C.h_p[2 * (u64)i + 1]);
+            else complete = false;
+            pend = (u128)0 - p;
+            post = amount;
+        } else if (tf & TF_VOID) {
+            pend = (u128)0 - amount;
+        } else {
+            post = amount;
+        }
+        for (u32 side = 0; side < 2; side++) {
+            u128* b = &bal[(u64)C.h_row_idx[2 * i + side] * 4 + 2 * side];
+            b[0] -= pend, b[1] -= post;
+        }
+    }
+    result->complete = complete ? 1 : 0;
+    result->count = m;
+    return TBGPU_STATUS_OK;
+}
+
+static bool change_filter_valid(const tbgpu_change_events_filter* f) {
+    if (f->timestamp_min == ~0ULL || f->timestamp_max == ~0ULL) return false;
+    if (f->timestamp_max != 0 && f->timestamp_max < f->timestamp_min) return false;
+    if (f->limit == 0) return false;
+    for (u8 b : f->reserved) if (b) return false;
+    return true;
+}
+
+extern "C" int tbgpu_get_change_events(tbgpu_t* E, const tbgpu_change_events_filter* filter, void* out,
+                                       uint32_t out_cap_events, tbgpu_query_result* result) {
+    API_ENTER(E, false);  // a read, as tbgpu_get_account_transfers
+    if (!filter || !out || !result) return fail(TBGPU_STATUS_INVALID, "get_change_events: a NULL filter, out or result");
+    result->count = 0;
+    result->matched = 0;
+    result->complete = 0;
+    QueryFieldFilter F{};
+    F.ts_min = filter->timestamp_min;
+    F.ts_max = filter->timestamp_max ? filter->timestamp_max : ~0ULL;
+    const bool valid = change_filter_valid(filter);
+    const u32 k = std::min<u32>(std::min<u32>(filter->limit, out_cap_events), CHANGE_EVENTS_MAX);
+    if (E->node) return node_change_events(E->node, F, valid, k, (u8*)out, result);
+    result->complete = E->evicted_total == 0;
+    if (!valid) return TBGPU_STATUS_OK;
+    int st = query_enqueue(E, F, k, false);
+    if (st) return st;
+    u32 m = 0;
+    u64 matched = 0;
+    st = query_collect(E, E->qc.h_rows, &m, &matched);
+    if (st) return st;
+    result->matched = matched;
+    if (m == 0) return TBGPU_STATUS_OK;
+    tbgpu* Es[1] = {E};
+    st = change_events_finish(Es, 1, E->qc.h_rows, m, (u8*)out, result);
+    if (st) result->matched = 0;
+    return st;
 }
 
 extern "C" int tbgpu_query_accounts(tbgpu_t* E, const tbgpu_query_filter* filter, void* out, uint32_t out_cap_records,

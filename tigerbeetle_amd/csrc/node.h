@@ -1808,6 +1808,23 @@ static int node_account_balances(TbNode* N, const QueryFilter& F, bool valid, u3
     return TBGPU_STATUS_OK;
 }
 
+// get_change_events: the rows are the merged query_transfers answer for the all-zero field filter.
+// change_events_finish (engine.hip) then has every shard sum the effects of its own log on its own
+// device and stream, reads each account from its owner and each post row's pending transfer on its
+// home, and adds the shards' sums on the host.  The sequencer's engine is not asked.
+static int node_change_events(TbNode* N, const QueryFieldFilter& F, bool valid, u32 k, u8* out, tbgpu_query_result* result) {
+    std::vector<u8> rows((u64)std::max<u32>(k, 1) * 128);
+    int status = node_query_transfers(N, F, valid, k, false, rows.data(), result);
+    const u32 m = result->count;
+    result->count = 0;
+    if (status || m == 0) return status;
+    std::vector<tbgpu*> Es(N->world);
+    for (u32 d = 0; d < N->world; d++) Es[d] = N->D[d].E;
+    status = change_events_finish(Es.data(), N->world, rows.data(), m, out, result);
+    if (status) result->matched = 0;
+    return status;
+}
+
 // query_accounts: shard d answers for the accounts with tb_home(id, world) == d — a home's imported
 // copies of foreign accounts do not match, and the sequencer's engine (N->X) is not asked.
 static int node_query_accounts(TbNode* N, const QueryFieldFilter& F, bool valid, u32 k, bool reversed, u8* out,

@@ -294,6 +294,13 @@ tbgpu_query_result StateMachine::get_account_balances(const tbgpu_account_filter
     return r;
 }
 
+tbgpu_query_result StateMachine::get_change_events(const tbgpu_change_events_filter& filter, void* out,
+                                                   uint32_t out_cap_events) {
+    tbgpu_query_result r{};
+    check(tbgpu_get_change_events(engine_, &filter, out, out_cap_events, &r), "get_change_events");
+    return r;
+}
+
 tbgpu_query_result StateMachine::query_transfers(const tbgpu_query_filter& filter, void* out, uint32_t out_cap_records) {
     tbgpu_query_result r{};
     check(tbgpu_query_transfers(engine_, &filter, out, out_cap_records, &r), "query_transfers");

@@ -241,6 +241,13 @@ public:
     // post had lost its pending transfer (tbgpu.h says when the rows are exact all the same).
     tbgpu_query_result get_account_balances(const tbgpu_account_filter& filter, void* out, uint32_t out_cap_records);
 
+    // The change stream (tbgpu_get_change_events; a read): every resident transfer of the filter's
+    // window by timestamp ascending, at most filter.limit and TBGPU_CHANGE_EVENTS_MAX, one 384-byte
+    // tbgpu_change_event each — the transfer and its two accounts right after it.  result.complete ==
+    // 0: transfers were evicted, a summed post had lost its pending transfer, or an event names an
+    // account the table lacks (its block is zero).
+    tbgpu_query_result get_change_events(const tbgpu_change_events_filter& filter, void* out, uint32_t out_cap_events);
+
     // The field-filter queries (tbgpu_query_transfers / tbgpu_query_accounts; reads, not commits): the
     // resident transfers, or the accounts, whose user_data_128 / user_data_64 / user_data_32 / ledger /
     // code equal the filter's non-zero fields, by timestamp (newest first under TBGPU_QUERY_REVERSED),

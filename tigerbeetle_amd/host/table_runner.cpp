@@ -302,7 +302,9 @@ std::string run_table(tb::StateMachine& sm, const std::string& text) {
 // tbgpu_query_filter for query_transfers or query_accounts.
 // --query-balances (tests/test_gpu_balances_cpp.py): --query's files, answered by get_account_balances
 // (the records are tbgpu_account_balance rows).
-enum QueryKind { ACCOUNT_TRANSFERS, ACCOUNT_BALANCES, QUERY_TRANSFERS, QUERY_ACCOUNTS };
+// --query-change-events (tests/test_gpu_change_events_cpp.py): the prepares ending in a
+// tbgpu_change_events_filter, answered by get_change_events (the records are 384-byte events).
+enum QueryKind { ACCOUNT_TRANSFERS, ACCOUNT_BALANCES, QUERY_TRANSFERS, QUERY_ACCOUNTS, CHANGE_EVENTS };
 
 int run_query(tb::StateMachine& sm, QueryKind kind, const char* in_path, const char* out_path) {
     std::ifstream in(in_path, std::ios::binary);
@@ -327,20 +329,24 @@ int run_query(tb::StateMachine& sm, QueryKind kind, const char* in_path, const c
     }
     tbgpu_account_filter f;
     tbgpu_query_filter q;
-    static_assert(sizeof(f) == sizeof(q), "both filters are 64 bytes");
+    tbgpu_change_events_filter c;
+    static_assert(sizeof(f) == sizeof(q) && sizeof(f) == sizeof(c), "every filter is 64 bytes");
     if (body.size() != sizeof(f)) {
         fprintf(stderr, "%s: a filter is %zu bytes\n", in_path, sizeof(f));
         return 2;
     }
     memcpy(&f, body.data(), sizeof(f));
     memcpy(&q, body.data(), sizeof(q));
+    memcpy(&c, body.data(), sizeof(c));
     std::vector<uint8_t> out((size_t)TBGPU_BATCH_EVENTS_MAX * 128);
-    const tbgpu_query_result r = kind == ACCOUNT_TRANSFERS ? sm.get_account_transfers(f, out.data(), TBGPU_BATCH_EVENTS_MAX)
+    const size_t record = kind == CHANGE_EVENTS ? sizeof(tbgpu_change_event) : 128;
+    const tbgpu_query_result r = kind == CHANGE_EVENTS ? sm.get_change_events(c, out.data(), TBGPU_CHANGE_EVENTS_MAX)
+                                 : kind == ACCOUNT_TRANSFERS ? sm.get_account_transfers(f, out.data(), TBGPU_BATCH_EVENTS_MAX)
                                  : kind == ACCOUNT_BALANCES ? sm.get_account_balances(f, out.data(), TBGPU_BATCH_EVENTS_MAX)
                                  : kind == QUERY_TRANSFERS ? sm.query_transfers(q, out.data(), TBGPU_BATCH_EVENTS_MAX)
                                                            : sm.query_accounts(q, out.data(), TBGPU_BATCH_EVENTS_MAX);
     std::ofstream o(out_path, std::ios::binary);
-    o.write((const char*)&r, sizeof(r)).write((const char*)out.data(), (size_t)r.count * 128);
+    o.write((const char*)&r, sizeof(r)).write((const char*)out.data(), (size_t)r.count * record);
     printf("query: %u of %llu records, complete %u\n", r.count, (unsigned long long)r.matched, r.complete);
     return o ? 0 : 2;
 }
@@ -350,8 +356,9 @@ int run_query(tb::StateMachine& sm, QueryKind kind, const char* in_path, const c
 int main(int argc, char** argv) {
     const bool fields = argc > 1 && std::string(argv[1]) == "--query-fields";
     const bool balances = argc > 1 && std::string(argv[1]) == "--query-balances";
-    const bool query = fields || balances || (argc > 1 && std::string(argv[1]) == "--query");
-    QueryKind kind = balances ? ACCOUNT_BALANCES : ACCOUNT_TRANSFERS;
+    const bool changes = argc > 1 && std::string(argv[1]) == "--query-change-events";
+    const bool query = fields || balances || changes || (argc > 1 && std::string(argv[1]) == "--query");
+    QueryKind kind = balances ? ACCOUNT_BALANCES : changes ? CHANGE_EVENTS : ACCOUNT_TRANSFERS;
     const char* self = argv[0];
     if (fields && argc > 2) {
         const std::string which = argv[2];
@@ -363,8 +370,9 @@ int main(int argc, char** argv) {
         fprintf(stderr,
                 "usage: %s <state_machine_tables.txt> [device]\n       %s --query <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-balances <prepares.bin> <answer.bin> [device]\n"
+                "       %s --query-change-events <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-fields <transfers|accounts> <prepares.bin> <answer.bin> [device]\n",
-                self, self, self, self);
+                self, self, self, self, self);
         return 2;
     }
     if (query) {

@@ -22,8 +22,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from .types import (ACCOUNT_BALANCE_DTYPE, ACCOUNT_DTYPE, ACCOUNT_FILTER_DTYPE, BATCH_MAX, FILTER_CREDITS, FILTER_DEBITS, FILTER_REVERSED,
-                    QUERY_FILTER_DTYPE, QUERY_REVERSED, TRANSFER_DTYPE, U64_MAX, Operation)
+from .types import (ACCOUNT_BALANCE_DTYPE, ACCOUNT_DTYPE, ACCOUNT_FILTER_DTYPE, BATCH_MAX, CHANGE_EVENT_DTYPE, CHANGE_EVENTS_FILTER_DTYPE,
+                    CHANGE_EVENTS_MAX, FILTER_CREDITS, FILTER_DEBITS, FILTER_REVERSED, pack_change_events_filter, QUERY_FILTER_DTYPE, QUERY_REVERSED, TRANSFER_DTYPE, U64_MAX, Operation)
 
 
 @dataclass
@@ -290,6 +290,28 @@ class Engine:
         """get_account_balances from the 64 bytes of a tbgpu_account_filter."""
         return self._account_filter_raw(self.lib.tbgpu_get_account_balances, ACCOUNT_BALANCE_DTYPE, filter_bytes,
                                         out_cap_records)
+
+    def get_change_events(self, timestamp_min=0, timestamp_max=0, limit=CHANGE_EVENTS_MAX, out_cap_events=None):
+        """The change stream (tbgpu_get_change_events): every resident transfer of the window by
+        timestamp ascending, at most `limit` (and one message body), each with its debit and its
+        credit account as they stood right after it.  Returns (events ndarray of CHANGE_EVENT_DTYPE,
+        matched, complete); `complete` is False once the engine has evicted transfers, a post in a sum
+        had lost its pending transfer, or an event names an account the table lacks (its block is
+        zero).  Page with timestamp_min = the last event's timestamp + 1."""
+        return self.get_change_events_raw(pack_change_events_filter(timestamp_min, timestamp_max, limit), out_cap_events)
+
+    def get_change_events_raw(self, filter_bytes, out_cap_events=None):
+        """get_change_events from the 64 bytes of a tbgpu_change_events_filter."""
+        filter_bytes = bytes(filter_bytes)
+        if len(filter_bytes) != CHANGE_EVENTS_FILTER_DTYPE.itemsize:
+            raise ValueError("a change-events filter is %d bytes" % CHANGE_EVENTS_FILTER_DTYPE.itemsize)
+        limit = int(np.frombuffer(filter_bytes, dtype=CHANGE_EVENTS_FILTER_DTYPE)["limit"][0])
+        cap = min(limit, CHANGE_EVENTS_MAX) if out_cap_events is None else int(out_cap_events)
+        out = np.zeros(max(cap, 1), dtype=CHANGE_EVENT_DTYPE)
+        res = _lib.tbgpu_query_result()
+        src = ctypes.create_string_buffer(filter_bytes, len(filter_bytes))
+        _lib.check(self.lib.tbgpu_get_change_events(self.h, src, out.ctypes.data, cap, ctypes.byref(res)))
+        return out[:res.count], int(res.matched), bool(res.complete)
 
     @staticmethod
     def query_filter(user_data_128=0, user_data_64=0, user_data_32=0, ledger=0, code=0, *, reversed=False,
@@ -650,6 +672,10 @@ class StateMachine:
     def get_account_balances(self, account_id, **filter):
         """The balance history of one account (Engine.get_account_balances): a read, not a commit."""
         return self.engine.get_account_balances(account_id, **filter)
+
+    def get_change_events(self, **filter):
+        """The change stream (Engine.get_change_events): a read, not a commit."""
+        return self.engine.get_change_events(**filter)
 
     def query_transfers(self, **filter):
         """The field-filter query over transfers (Engine.query_transfers): a read, not a commit."""

@@ -122,6 +122,23 @@ QUERY_FILTER_DTYPE = np.dtype(
 assert QUERY_FILTER_DTYPE.itemsize == 64
 QUERY_REVERSED = 1
 
+# tbgpu_change_events_filter and tbgpu_change_event (include/tbgpu.h tbgpu_get_change_events): 64 and
+# 384 bytes, no padding; an event is the transfer and its two accounts right after it.
+CHANGE_EVENTS_FILTER_DTYPE = np.dtype(
+    [("timestamp_min", "<u8"), ("timestamp_max", "<u8"), ("limit", "<u4"), ("reserved", "u1", (44,))])
+CHANGE_EVENT_DTYPE = np.dtype(
+    [("transfer", TRANSFER_DTYPE), ("debit_account", ACCOUNT_DTYPE), ("credit_account", ACCOUNT_DTYPE)])
+assert CHANGE_EVENTS_FILTER_DTYPE.itemsize == 64 and CHANGE_EVENT_DTYPE.itemsize == 384
+CHANGE_EVENTS_MAX = 2730
+
+
+def pack_change_events_filter(timestamp_min=0, timestamp_max=0, limit=CHANGE_EVENTS_MAX):
+    """The 64 bytes of a tbgpu_change_events_filter."""
+    f = np.zeros(1, dtype=CHANGE_EVENTS_FILTER_DTYPE)
+    f["timestamp_min"], f["timestamp_max"], f["limit"] = timestamp_min, timestamp_max, limit
+    return f.tobytes()
+
+
 ACCOUNT_FIELDS = ("id", "debits_pending", "debits_posted", "credits_pending", "credits_posted",
                   "user_data_128", "user_data_64", "user_data_32", "reserved", "ledger", "code",
                   "flags", "timestamp")

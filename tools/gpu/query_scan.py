@@ -1,7 +1,7 @@
 """The account-filter scan (tbgpu_get_account_transfers, csrc/k_query.h) over a 16M-transfer log (2 GB)
 against a device-to-device copy of the same log range, in one process.
 
-usage: python tools/gpu/query_scan.py [transfers] [runs] [--only account|fields|balances]
+usage: python tools/gpu/query_scan.py [transfers] [runs] [--only account|fields|balances|change_events]
 
 The log is built by the device generator, committed in place (the way tools/gpu/device_pass.py builds
 a pass): once with uniform C2 ids, where the queried account is a cold one (a few dozen matches), and
@@ -21,6 +21,11 @@ loaded through TBGPU_AB_LIB has nothing else), `--only fields` the field filters
 `--only balances` (tbgpu_get_account_balances) times get_account_balances beside
 get_account_transfers with the same filter on both logs, both directions, limit 8190: it scans the log
 once more, so the bar is about twice the time (explain a cold-account ratio above 2.5).
+
+`--only change_events` (tbgpu_get_change_events) times a page of limit 2730 beside
+query_transfers with the same window and limit and beside the copy of the log: the newest page of the
+uniform log (nothing is newer: the second scan reads timestamps only), its oldest page (the whole log
+is newer) and the oldest page of the Zipf log, whose set holds the hottest account.
 """
 import json
 import os
@@ -175,14 +180,63 @@ def measure_fields():
     return out
 
 
+def measure_change_events():
+    """get_change_events on both logs, beside query_transfers with the same window and the log's copy."""
+    os.environ["TBGPU_QUERY_COOP"] = "0"
+    e = Engine(Options(accounts_max=n_acct, transfers_max=n_xfer, pass_events_max=pb * batch, pass_batches_max=pb))
+    a_lens = batches(n_acct, batch)
+    a_ts, t = timestamps(a_lens, 1_000_000_000)
+    acct = e.alloc(n_acct * 128)
+    e.generate_accounts(acct, 0, n_acct, seed=42)
+    res = e.alloc(max(n_acct, n_xfer) * 8)
+    rb = e.alloc((n_xfer // batch + 2) * 4)
+    e.commit_device_async(128, a_ts, a_lens, acct, res, rb)
+    e.sync()
+    spare = e.alloc(n_xfer * 128)
+    out = {}
+    for name, kind in (("uniform", "c2"), ("zipf", "c3")):
+        if name != "uniform":
+            e.reset_transfers()
+        log = e.log_window(n_xfer)
+        e.generate_transfers(log, 0, n_xfer, n_acct, seed=42, kind=KINDS[kind])
+        e.sync()
+        x_lens = batches(n_xfer, batch)
+        x_ts, t = timestamps(x_lens, t + 10)
+        e.commit_device_async(129, x_ts, x_lens, log, res, rb)
+        e.sync()
+        if name == "uniform":
+            med, lo_ms, hi_ms = timed(e, lambda: e.copy_device_async(spare, log, n_xfer * 128))
+            out["copy_log_d2d"] = copy_log = row(med, lo_ms, hi_ms, bytes=n_xfer * 128)
+        newest, _, _ = e.query_transfers(reversed=True, limit=2730)
+        pages = [("oldest_page", 0)] + ([("newest_page", int(newest["timestamp"][-1]))] if name == "uniform" else [])
+        for page, ts_min in pages:
+            recs, matched, complete = e.query_transfers(timestamp_min=ts_min, limit=2730)
+            events, c_matched, c_complete = e.get_change_events(timestamp_min=ts_min, limit=2730)
+            assert complete and c_complete and c_matched == matched and len(events) == len(recs) == 2730
+            assert events["transfer"].tobytes() == recs.tobytes()
+            ids = set(zip(recs["debit_account_id_lo"].tolist(), recs["debit_account_id_hi"].tolist()))
+            ids |= set(zip(recs["credit_account_id_lo"].tolist(), recs["credit_account_id_hi"].tolist()))
+            q_med, q_lo, q_hi = timed(e, lambda: e.query_transfers(timestamp_min=ts_min, limit=2730))
+            med, lo_ms, hi_ms = timed(e, lambda: e.get_change_events(timestamp_min=ts_min, limit=2730))
+            out["%s_%s" % (name, page)] = row(
+                med, lo_ms, hi_ms, matched=matched, distinct_accounts=len(ids),
+                query_transfers_ms=round(q_med, 4), query_transfers_min_ms=round(q_lo, 4),
+                query_transfers_max_ms=round(q_hi, 4), over_query_transfers=round(med / q_med, 2),
+                over_copy=round(med / copy_log["ms"], 2), le_copy=med <= copy_log["ms"])
+    e.close()
+    return out
+
+
 result = dict(transfers=n_xfer, log_bytes=n_xfer * 128, runs=runs, warmups=WARMUPS)
 if only == "balances":
     result["balances"] = measure(False, balances=True)
+elif only == "change_events":
+    result["change_events"] = measure_change_events()
 elif only != "fields":
     result.update(lane_per_record=measure(False), cooperative=measure(True))
     for shape in ("lane_per_record", "cooperative"):
         r = result[shape]
         r["bar_query_le_copy"] = all(v["ms"] <= r["copy_d2d"]["ms"] for k, v in r.items() if k != "copy_d2d")
-if only not in ("account", "balances"):
+if only not in ("account", "balances", "change_events"):
     result["field_filters"] = measure_fields()
 print(json.dumps(result))
