@@ -120,6 +120,12 @@ double tbgpu_marker_elapsed_ms(tbgpu_t* engine, uint32_t a, uint32_t b);
  * tbgpu_init". */
 uint64_t tbgpu_debug_allocations(void);
 
+/* Device address of a single-device engine's event staging buffer (pass_events_max x 128 B): where a
+ * host commit's events are copied, or written through by kernel 1 when it reads them from registered
+ * memory.  Read-only for the engine's purposes: a test plants a sentinel behind a call's events and
+ * reads it back (tbgpu_copy_to_device / tbgpu_copy_to_host) to hold "nothing written past them". */
+int tbgpu_debug_staging(tbgpu_t* engine, void** staging);
+
 #ifdef __cplusplus
 }
 #endif

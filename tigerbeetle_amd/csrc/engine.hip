@@ -1720,6 +1720,14 @@ extern "C" int tbgpu_log_window(tbgpu_t* E, uint64_t events, void** window) {
     return TBGPU_STATUS_OK;
 }
 
+extern "C" int tbgpu_debug_staging(tbgpu_t* E, void** staging) {
+    API_ENTER(E, false);
+    *staging = nullptr;
+    if (E->node) return fail(TBGPU_STATUS_INVALID, "the staging buffer is a single-device engine's");
+    *staging = E->staging;
+    return TBGPU_STATUS_OK;
+}
+
 extern "C" int tbgpu_sync(tbgpu_t* E) {
     API_ENTER(E, false);
     if (E->node) return node_sync(E->node);

@@ -305,16 +305,19 @@ __global__ __launch_bounds__(VALIDATE_THREADS) void tb_transfers_validate(PassAr
 
     const u32 tile0 = blockIdx.x * VALIDATE_THREADS;
     const u32 count = min((u32)VALIDATE_THREADS, P.n - tile0);
-    tb_stage_tile<SRC>(P, tile0, count, stage, TB_ABL(P, EXP_NT));
-
     const u32 pe = tile0 + threadIdx.x;  // pass-relative event
     const u64 e = P.e0 + pe;
-    const u32 b = tb_wave_batch(P.batch_off, P.b0, P.b1, P.e0 + tile0, count, e);
+    // The tile's loads are issued first; the batch lookup runs while they are in flight.
+    u32x4 tile[STAGE_CHUNKS];
+    tb_stage_tile_issue<SRC>(P, tile0, count, tile, TB_ABL(P, EXP_NT));
+    const LaneBatch B = tb_lane_batch(P, tile0, count, e, true);
+    tb_stage_tile_commit<SRC>(P, tile0, count, tile, stage);
+
     TransferScratch s;
     if (threadIdx.x < count) {
         Transfer t = tb_read_staged<Transfer>(stage);
-        const u32 L = (u32)(P.batch_off[b + 1] - P.batch_off[b]);
-        const u32 j = (u32)(e - P.batch_off[b]);
+        const u32 L = (u32)(B.end - B.off);
+        const u32 j = (u32)(e - B.off);
         u32 code;
         u64 routed_ts = 0;
         if (P.routed) {
@@ -329,7 +332,7 @@ __global__ __launch_bounds__(VALIDATE_THREADS) void tb_transfers_validate(PassAr
         } else if (t.timestamp != 0) {
             code = R_TIMESTAMP_MUST_BE_ZERO;  // :643
         } else {
-            const u64 ts = P.routed ? routed_ts : P.ev_ts ? P.ev_ts[e] : P.batch_ts[b] - L + j + 1;  // :645
+            const u64 ts = P.routed ? routed_ts : P.ev_ts ? P.ev_ts[e] : B.ts - L + j + 1;  // :645
             code = tb_validate_transfer(P, t, ts, pe, s);
         }
         if (tb_hi(s.amount)) s.hz |= HZ_AMT_HI;
@@ -427,15 +430,17 @@ __global__ __launch_bounds__(VALIDATE_THREADS) void tb_accounts_validate(PassArg
     __shared__ __attribute__((aligned(16))) u8 stage[VALIDATE_THREADS * STAGE_STRIDE];
     const u32 tile0 = blockIdx.x * VALIDATE_THREADS;
     const u32 count = min((u32)VALIDATE_THREADS, P.n - tile0);
-    tb_stage_tile<SRC>(P, tile0, count, stage);
     const u32 pe = tile0 + threadIdx.x;
     const u64 e = P.e0 + pe;
-    const u32 b = tb_wave_batch(P.batch_off, P.b0, P.b1, P.e0 + tile0, count, e);
+    u32x4 tile[STAGE_CHUNKS];
+    tb_stage_tile_issue<SRC>(P, tile0, count, tile);
+    const LaneBatch B = tb_lane_batch(P, tile0, count, e, false);
+    tb_stage_tile_commit<SRC>(P, tile0, count, tile, stage);
     if (threadIdx.x >= count) return;
 
     const Account a = tb_read_staged<Account>(stage);
-    const u32 L = (u32)(P.batch_off[b + 1] - P.batch_off[b]);
-    const u32 j = (u32)(e - P.batch_off[b]);
+    const u32 L = (u32)(B.end - B.off);
+    const u32 j = (u32)(e - B.off);
     u32 code, hz = 0;
     u64 kid = 0;
     if ((a.flags & AF_LINKED) && j == L - 1) {

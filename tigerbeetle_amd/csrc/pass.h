@@ -234,29 +234,76 @@ __device__ static inline u32 tb_wave_batch(const u64* off, u32 lo, u32 hi, u64 t
 #define STAGE_STRIDE 128
 __device__ static inline u32 tb_stage_off(u32 row, u32 chunk) { return row * STAGE_STRIDE + ((chunk ^ (row & 7)) << 4); }
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-__device__ static inline void tb_stage_events(const u8* src, u32 count, u8* lds, bool nt = false, u8* copy = nullptr) {
-    const u32 t = threadIdx.x;
+
+// The stage has two phases, so that a tile costs one memory round trip and not eight.  Issue: the
+// thread's eight 16-B loads into registers, with no branch between them (a load behind its own
+// `if (ev < count)` gets its own basic block, and hipcc then waits for each load before it issues
+// the next).  A chunk index past the tile's last valid chunk is clamped to it, so every address is
+// inside the source and a partial tile needs no branch either; the clamped lanes' values are never
+// written.  Commit: the eight LDS writes (and the write-through copy), predicated on ev < count, then
+// the barrier.  Whatever the caller puts between the two phases runs under the tile's loads.
+#define STAGE_CHUNKS 8  // 16-B chunks per thread: VALIDATE_THREADS threads x 8 x 16 B = 256 events
+__device__ static inline void tb_stage_issue(const u8* src, u32 count, u32x4 (&v)[STAGE_CHUNKS], bool nt = false) {
+    const u32 last = count * 8 - 1;  // count >= 1: the grid has no empty tile
 #pragma unroll
-    for (u32 r = 0; r < 8; r++) {
-        const u32 c = t + r * VALIDATE_THREADS;  // 16-byte chunk index within the tile
+    for (u32 r = 0; r < STAGE_CHUNKS; r++) {
+        const u32 c = min(threadIdx.x + r * VALIDATE_THREADS, last);  // 16-byte chunk index within the tile
+        const u32x4* g = (const u32x4*)(src + (u64)c * 16);
+        v[r] = nt ? __builtin_nontemporal_load(g) : *g;
+    }
+}
+__device__ static inline void tb_stage_commit(const u32x4 (&v)[STAGE_CHUNKS], u32 count, u8* lds, u8* copy = nullptr) {
+#pragma unroll
+    for (u32 r = 0; r < STAGE_CHUNKS; r++) {
+        const u32 c = threadIdx.x + r * VALIDATE_THREADS;
         const u32 ev = c >> 3, part = c & 7;
-        if (ev < count) {
-            const u32x4* g = (const u32x4*)(src + (u64)c * 16);
-            const u32x4 v = nt ? __builtin_nontemporal_load(g) : *g;
-            *(u32x4*)(lds + tb_stage_off(ev, part)) = v;
-            if (copy) *(u32x4*)(copy + (u64)c * 16) = v;
+        if (ev < count) {  // nothing is written past the tile's events, in LDS or in `copy`
+            *(u32x4*)(lds + tb_stage_off(ev, part)) = v[r];
+            if (copy) *(u32x4*)(copy + (u64)c * 16) = v[r];
         }
     }
     __syncthreads();
 }
+__device__ static inline void tb_stage_events(const u8* src, u32 count, u8* lds) {
+    u32x4 v[STAGE_CHUNKS];
+    tb_stage_issue(src, count, v);
+    tb_stage_commit(v, count, lds);
+}
 
 // Kernel 1's tile: from the call's events, or (SRC, a separate instantiation so the HBM path's
-// code is untouched) read through from registered host memory.
+// code is untouched) read through from registered host memory and written through to the call's
+// events.
 template <bool SRC>
-__device__ static inline void tb_stage_tile(const PassArgs& P, u32 tile0, u32 count, u8* lds, bool nt = false) {
+__device__ static inline void tb_stage_tile_issue(const PassArgs& P, u32 tile0, u32 count, u32x4 (&v)[STAGE_CHUNKS],
+                                                  bool nt = false) {
     const u64 off = (P.e0 + tile0) * 128;
-    if (SRC) tb_stage_events(P.events_src + off, count, lds, false, const_cast<u8*>(P.events) + off);
-    else tb_stage_events(P.events + off, count, lds, nt);
+    if (SRC) tb_stage_issue(P.events_src + off, count, v);
+    else tb_stage_issue(P.events + off, count, v, nt);
+}
+template <bool SRC>
+__device__ static inline void tb_stage_tile_commit(const PassArgs& P, u32 tile0, u32 count, const u32x4 (&v)[STAGE_CHUNKS],
+                                                   u8* lds) {
+    tb_stage_commit(v, count, lds, SRC ? const_cast<u8*>(P.events) + (P.e0 + tile0) * 128 : nullptr);
+}
+
+// The batch of a validate lane's event, with the words of that batch every lane needs: looked up
+// between the two phases of the stage, so the scalar searches and these small loads run under the
+// tile's loads instead of after its barrier.  Every lane loads them, a lane past the tile's events
+// and a lane whose event fails before its timestamp matters included (a branch here would be a
+// wait): tb_wave_batch gives such a lane a batch of the pass too (b0 <= b < b1; b0 for a wave with
+// no event), so the loads rely on batch_off holding b1 + 1 words and on batch_ts being non-null
+// whenever the timestamps are not carried, as every caller of the pass provides.
+struct LaneBatch {
+    u64 off, end;  // batch_off[b], batch_off[b + 1]
+    u64 ts;        // batch_ts[b] (0 when the timestamps are carried: tb_ts_carried)
+};
+__device__ static inline LaneBatch tb_lane_batch(const PassArgs& P, u32 tile0, u32 count, u64 e, bool want_ts) {
+    const u32 b = tb_wave_batch(P.batch_off, P.b0, P.b1, P.e0 + tile0, count, e);
+    LaneBatch B;
+    B.off = P.batch_off[b];
+    B.end = P.batch_off[b + 1];
+    B.ts = want_ts && !tb_ts_carried(P) ? P.batch_ts[b] : 0;
+    return B;
 }
 
 template <typename R>
