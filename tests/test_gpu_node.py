@@ -45,7 +45,7 @@ def test_node_reproduces_reference_table(name, text, node_factory):
 
 
 @pytest.mark.parametrize("config", ["mixed", "chains", "two_phase", "limits", "hot_ids", "clean", "overflow",
-                                    "big_batches"])
+                                    "huge_amounts", "big_batches"])
 @pytest.mark.parametrize("many", [False, True], ids=["commit", "commit_many"])
 def test_node_differential(config, many, node_factory):
     sc = make_scenario(5003 + sum(map(ord, config)), **CONFIGS[config])
