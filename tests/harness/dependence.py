@@ -16,6 +16,15 @@ import numpy as np
 
 LIMITS = int(AF.debits_must_not_exceed_credits) | int(AF.credits_must_not_exceed_debits)
 PADDING = 0xFFC0  # TransferFlags bits 6..15
+# Plain ints: an IntFlag operand makes every `&` below build an enum member (most of the model's time).
+LINKED, PENDING = int(TF.linked), int(TF.pending)
+POST, VOID = int(TF.post_pending_transfer), int(TF.void_pending_transfer)
+BAL_DEBIT, BAL_CREDIT = int(TF.balancing_debit), int(TF.balancing_credit)
+
+
+_COLUMNS = ("id_lo", "id_hi", "debit_account_id_lo", "debit_account_id_hi", "credit_account_id_lo",
+            "credit_account_id_hi", "amount_lo", "amount_hi", "pending_id_lo", "pending_id_hi", "timeout", "ledger", "code",
+            "flags", "timestamp")
 
 
 def _u128(lo, hi):
@@ -31,29 +40,30 @@ def dependent_count(prepares, accounts, existing_ids=frozenset()):
     for p, body in enumerate(prepares):
         rec = np.frombuffer(body, dtype=TRANSFER_DTYPE)
         L = len(rec)
+        # Columns as Python ints at once (a pass of half a million events: field reads per record
+        # took ten seconds).
+        c = {name: rec[name].tolist() for name in _COLUMNS}
         for j in range(L):
-            r = rec[j]
-            evs.append(dict(p=p, j=j, L=L, id=_u128(r["id_lo"], r["id_hi"]),
-                            dr=_u128(r["debit_account_id_lo"], r["debit_account_id_hi"]),
-                            cr=_u128(r["credit_account_id_lo"], r["credit_account_id_hi"]),
-                            amount=_u128(r["amount_lo"], r["amount_hi"]),
-                            pid=_u128(r["pending_id_lo"], r["pending_id_hi"]), timeout=int(r["timeout"]),
-                            ledger=int(r["ledger"]), code=int(r["code"]), flags=int(r["flags"]),
-                            ts=int(r["timestamp"])))
+            evs.append(dict(p=p, j=j, L=L, id=_u128(c["id_lo"][j], c["id_hi"][j]),
+                            dr=_u128(c["debit_account_id_lo"][j], c["debit_account_id_hi"][j]),
+                            cr=_u128(c["credit_account_id_lo"][j], c["credit_account_id_hi"][j]),
+                            amount=_u128(c["amount_lo"][j], c["amount_hi"][j]),
+                            pid=_u128(c["pending_id_lo"][j], c["pending_id_hi"][j]), timeout=c["timeout"][j],
+                            ledger=c["ledger"][j], code=c["code"][j], flags=c["flags"][j], ts=c["timestamp"][j]))
     # -- kernel 1 (k_validate.h): who claims its id, pv keys, hazard bits ---------------------------
     for e in evs:
         f = e["flags"]
         e.update(claims=False, pv_key=False, accts=False, limit=False, bal=False, ok=False, selfdep=False)
-        if (f & TF.linked) and e["j"] == e["L"] - 1:
+        if (f & LINKED) and e["j"] == e["L"] - 1:
             continue  # linked_event_chain_open
         if e["ts"] != 0:
             continue  # timestamp_must_be_zero
         if f & PADDING or e["id"] in (0, U128_MAX):
             continue
-        if f & (TF.post_pending_transfer | TF.void_pending_transfer):
-            if (f & TF.post_pending_transfer) and (f & TF.void_pending_transfer):
+        if f & (POST | VOID):
+            if (f & POST) and (f & VOID):
                 continue
-            if f & (TF.pending | TF.balancing_debit | TF.balancing_credit):
+            if f & (PENDING | BAL_DEBIT | BAL_CREDIT):
                 continue
             if e["pid"] in (0, U128_MAX) or e["pid"] == e["id"] or e["timeout"] != 0:
                 continue
@@ -63,9 +73,9 @@ def dependent_count(prepares, accounts, existing_ids=frozenset()):
             continue
         if e["dr"] in (0, U128_MAX) or e["cr"] in (0, U128_MAX) or e["dr"] == e["cr"] or e["pid"] != 0:
             continue
-        if not (f & TF.pending) and e["timeout"] != 0:
+        if not (f & PENDING) and e["timeout"] != 0:
             continue
-        if not (f & (TF.balancing_debit | TF.balancing_credit)) and e["amount"] == 0:
+        if not (f & (BAL_DEBIT | BAL_CREDIT)) and e["amount"] == 0:
             continue
         if e["ledger"] == 0 or e["code"] == 0:
             continue
@@ -75,7 +85,7 @@ def dependent_count(prepares, accounts, existing_ids=frozenset()):
             continue
         e["accts"] = True
         e["limit"] = bool((da[0] | ca[0]) & LIMITS)
-        e["bal"] = bool(f & (TF.balancing_debit | TF.balancing_credit))
+        e["bal"] = bool(f & (BAL_DEBIT | BAL_CREDIT))
     # Claims: an id claimed by two or more events of the pass, and stored before by none, collides.
     claimers = {}
     for e in evs:
@@ -99,9 +109,9 @@ def dependent_count(prepares, accounts, existing_ids=frozenset()):
         if not e["accts"]:
             continue
         if e["bal"]:  # marks before the id check (k_validate.h: balancing accounts marked up front)
-            if e["flags"] & TF.balancing_debit:
+            if e["flags"] & BAL_DEBIT:
                 marked.add(e["dr"])
-            if e["flags"] & TF.balancing_credit:
+            if e["flags"] & BAL_CREDIT:
                 marked.add(e["cr"])
         exists = e["id"] in existing_ids
         e["selfdep"] = e["id"] in collided
@@ -131,10 +141,10 @@ def dependent_count(prepares, accounts, existing_ids=frozenset()):
     i = 0
     while i < len(evs):
         j = i
-        while j + 1 < len(evs) and evs[j + 1]["p"] == evs[i]["p"] and (evs[j]["flags"] & TF.linked):
+        while j + 1 < len(evs) and evs[j + 1]["p"] == evs[i]["p"] and (evs[j]["flags"] & LINKED):
             j += 1
         members = evs[i:j + 1]
-        if evs[i]["flags"] & TF.linked and len(members) >= 1:
+        if evs[i]["flags"] & LINKED and len(members) >= 1:
             if any(m["dep"] for m in members):
                 total += len(members)
         else:

@@ -2449,15 +2449,26 @@ __global__ __launch_bounds__(FLOW_THREADS) void tb_flow(PassArgs P, FlowArgs F, 
     const u32 NT = FLOW_THREADS, tid = threadIdx.x;
     const u32 nb = P.b1 - P.b0;
     // tb_apply_events' work first, when this launch replaces it (one launch a pass fewer): the
-    // independent ok transfers that are not legs touch no constrained account, id or pending transfer
-    // a dependent unit reads, so their balance adds commute with everything below.
-    if (P.late_in_flow) tb_apply_late(P);
-    if (__hip_atomic_load(&g->dependent_total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
-        if (blockIdx.x == 0) fl_finish(P, s_code, s_wave, s_list, 0, false);  // (before any admission)
+    // balance adds of the independent ok transfers that are not legs.  Which path a workgroup takes
+    // rests on a pass word tb_resolve left (PW_DEP), not on dependent_total, which the closing
+    // workgroup resets: a workgroup that starts after the close decides as every other did.
+    //   No dependent event: nothing in this launch reads a balance, so every workgroup of the launch
+    // adds its blockIdx share whenever it starts, and workgroup 0 closes the pass (once).
+    //   Dependent events: the adds commute with each other and with the atomic deltas free accounts
+    // take on the parallel path, but not with what reads or stores a balance whole — a limit check,
+    // the bounds' sums, and every account the sequential replay touches (rp_balance_update stores all
+    // four words, a chain's rollback stores the before-image).  So only the admitted workgroups add,
+    // their share by FL_B of FL_G, and the first grid barrier below (every storing wave drained
+    // before it) orders all of them before the first unit, the bounds and the sequential replay.  A
+    // workgroup that is not admitted touches no balance; nothing waits for it.
+    if (P.pass_words[PW_DEP] == 0) {
+        if (P.late_in_flow) tb_apply_late(P, blockIdx.x, gridDim.x);
+        if (blockIdx.x == 0) fl_finish(P, s_code, s_wave, s_list, 0, false);  // (no admission)
         return;
     }
     if (!fl_admit(g, F)) return;  // started after admission closed: the admitted workgroups cover the pass
     const u32 G = FL_G;
+    if (P.late_in_flow) tb_apply_late(P, FL_B, G);
     u128 S;
     bool cert_global, cert64;
     tb_pass_cert(P, S, cert_global, cert64);

@@ -540,6 +540,7 @@ __global__ __launch_bounds__(RESOLVE_THREADS) void tb_resolve(PassArgs P) {
         }
         P.dep_count[blockIdx.x] = ndep;
         if (ndep) atomicAdd((unsigned long long*)&T.g->dependent_total, (unsigned long long)ndep);
+        if (ndep) P.pass_words[PW_DEP] = 1;
     }
     if (use_legs) tb_emit_legs(P, pbase, legmask, pendmask, r_dr, r_cr, r_amt, s_hist, (u64*)s_key, s_wave);  // s_key is dead here
     if (ndep == 0) tb_write_replies(P, b, L, s_code, s_wave, s_failed);

@@ -359,13 +359,16 @@ __device__ static inline u128 tb_wave_sum_u128(u128 v) {
 // Pass words after the shards: HUGE (S >= 2^100 somewhere), DUP (an id or pending-id collision
 // happened), BAL (a tentatively-ok balancing event exists), PV (a post/void event registered its
 // pending id), LATE (an independent ok transfer of a legs pass is not a leg: tb_apply_events applies
-// it).  Written with idempotent stores.
+// it), DEP (tb_resolve left a dependent event to the ordered path: unlike Globals.dependent_total,
+// which the closing workgroup resets, no kernel after tb_resolve writes it, so every workgroup of
+// tb_flow reads the same answer whenever it starts).  Written with idempotent stores.
 #define PW_HUGE (2 * SUM_SHARDS)
 #define PW_DUP (2 * SUM_SHARDS + 1)
 #define PW_BAL (2 * SUM_SHARDS + 2)
 #define PW_PV (2 * SUM_SHARDS + 3)
 #define PW_LATE (2 * SUM_SHARDS + 4)
-#define SUM_WORDS (2 * SUM_SHARDS + 5)
+#define PW_DEP (2 * SUM_SHARDS + 5)
+#define SUM_WORDS (2 * SUM_SHARDS + 6)
 __device__ static inline void tb_sum_publish(const PassArgs& P, u128 block_sum) {
     if (block_sum == 0) return;
     if (tb_hi(block_sum) >> 36) {
