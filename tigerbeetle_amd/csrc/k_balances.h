@@ -9,9 +9,10 @@
 //   tb_balance_effects  k_query.h's tile shape and liveness probe, the account on either side, every
 //                       timestamp above the oldest row's: each hit adds its effect on the account's
 //                       four columns into bins[number of rows older than the record],
-// leaves the host a suffix sum over k + 1 bins of 64 B.  Whatever order the log is in: a record finds
-// its bin by binary search, never by position.  Plain launches: no grid barrier, no spin, no wait on
-// another workgroup; every loop is bounded by the workgroup's tiles or the distinct bins of a wave.
+// leaves the host (query.h balances_finish) a suffix sum over k + 1 bins of 64 B.  Whatever order the
+// log is in: a record finds its bin by binary search, never by position.  Plain launches: no grid
+// barrier, no spin, no wait on another workgroup; every loop is bounded by the workgroup's tiles or the
+// distinct bins of a wave.
 #pragma once
 
 #include "k_node.h"
@@ -73,6 +74,40 @@ __device__ static inline void tb_balance_flush(u64* bins, u32 bin, const u128 v[
     for (u32 c = 0; c < 4; c++) tb_atomic_add128(dst + 2 * c, v[c]);
 }
 
+// The balance-effect rule: how one log record moves the four balances of the accounts it names, as
+// {pend, post} added to *_pending and *_posted of its debit and its credit side, modulo 2^128.  Both
+// the balance history and the change stream are "current minus the effects of newer records", so this
+// is the definition of their answers, on the device and in the host's walk (query.h) alike.
+//   pending   +pending(amount)
+//   post      -pending(p), +posted(amount): p is the pending transfer's amount (tb_pending_amount),
+//             the post's own amount where the pending transfer is not resident (the caller's orphan flag)
+//   void      -pending(amount): a void record stores its pending transfer's amount
+//   plain     +posted(amount)
+// The post case is tested first, by the predicate the callers guard the lookup with, so that lookup
+// and case share one branch on the device.
+struct BalanceEffect {
+    u128 pend, post;
+};
+__host__ __device__ static inline bool tb_effect_is_post(u32 flags) { return !(flags & TF_PENDING) && (flags & TF_POST); }
+__host__ __device__ static inline BalanceEffect tb_balance_effect(u32 flags, u128 amount, u128 p) {
+    if (tb_effect_is_post(flags)) return {(u128)0 - p, amount};
+    if (flags & TF_PENDING) return {amount, 0};
+    if (flags & TF_VOID) return {(u128)0 - amount, 0};
+    return {0, amount};
+}
+
+// The amount of the pending transfer (lo, hi) into *p, read on its home's table (a single engine:
+// world = 1, every id's home is 0); false, and *p as it was: not resident (evicted, or never there).
+__device__ static inline bool tb_pending_amount(const NodeTablesArgs& N, u64 lo, u64 hi, u128* p) {
+    if (tb_id_reserved(lo, hi)) return false;
+    const Tables& H = N.T[tb_home(lo, hi, N.world)];
+    const u32 pp = tb_transfer_find(H, lo, hi);
+    if (pp == TB_NOT_FOUND) return false;
+    const u64* pw = (const u64*)&H.xlog[pp];
+    *p = tb_u128(pw[6], pw[7]);
+    return true;
+}
+
 // flt: the account on both sides, ts_min = the oldest row's timestamp + 1, no upper bound.
 // N.T[self] is the scanned engine; a post's pending transfer is read from N.T[home(pending_id)]
 // (a single engine: world = 1, every id's home is 0).  Workgroup b scans tiles [b, b + 1) *
@@ -110,29 +145,12 @@ __global__ __launch_bounds__(QUERY_THREADS) void tb_balance_effects(NodeTablesAr
             const u64* w = (const u64*)&T.xlog[pos];
             const u128 amount = tb_u128(w[6], w[7]);
             const u32 flags = (u32)(w[14] >> 48);
-            if (flags & TF_PENDING) {
-                pend = amount;
-            } else if (flags & TF_POST) {
-                const u64 plo = w[8], phi = w[9];
-                u128 p = amount;
-                bool resident = false;
-                if (!tb_id_reserved(plo, phi)) {
-                    const Tables& H = N.T[tb_home(plo, phi, N.world)];
-                    const u32 pp = tb_transfer_find(H, plo, phi);
-                    if (pp != TB_NOT_FOUND) {
-                        const u64* pw = (const u64*)&H.xlog[pp];
-                        p = tb_u128(pw[6], pw[7]);
-                        resident = true;
-                    }
-                }
-                if (!resident) atomicOr((unsigned long long*)(tail + BALANCE_SLOT_WORDS), 1ULL);
-                pend = (u128)0 - p;
-                post = amount;
-            } else if (flags & TF_VOID) {
-                pend = (u128)0 - amount;  // a void record stores its pending transfer's amount
-            } else {
-                post = amount;
+            u128 p = amount;
+            if (tb_effect_is_post(flags) && !tb_pending_amount(N, w[8], w[9], &p)) {
+                atomicOr((unsigned long long*)(tail + BALANCE_SLOT_WORDS), 1ULL);
             }
+            const BalanceEffect e = tb_balance_effect(flags, amount, p);
+            pend = e.pend, post = e.post;
             deb = f.dlo == flt.id_lo && f.dhi == flt.id_hi;
             cred = f.clo == flt.id_lo && f.chi == flt.id_hi;
             bin = tb_balance_bin(row_ts, k, f.ts);

@@ -6,8 +6,9 @@
 // after a row are its current balances minus the effects of every newer resident record that names it
 // (k_balances.h's definition, per column modulo 2^128).  The filter has no field predicate, so the
 // page is *every* live record between its first and its last timestamp: the host walks the k rows
-// themselves backward, and the device only sums what is newer than the last row, t_last — one bin
-// per distinct account of the page (at most 2k), whatever the record's distance from the page:
+// themselves backward (query.h change_walk), and the device only sums what is newer than the last
+// row, t_last — one bin per distinct account of the page (at most 2k), whatever the record's distance
+// from the page:
 //   tb_change_gather   a lane per distinct account: its 128-B record from its owner's table, or a
 //                      not-found mark; a lane per post row: its pending transfer's amount from
 //                      home(pending_id), or the orphan flag and the row's own amount;
@@ -97,19 +98,9 @@ __global__ __launch_bounds__(QUERY_THREADS) void tb_change_gather(NodeTablesArgs
         if (slot != TB_NOT_FOUND) *(Account*)(accounts + (u64)i * 128) = tb_account_load(O, slot);
     }
     if (i < n_rows) {
-        const u64 lo = pids[2 * (u64)i], hi = pids[2 * (u64)i + 1];
-        u64 plo = 0, phi = 0;
-        u32 ok = 0;
-        if (!tb_id_reserved(lo, hi)) {
-            const Tables& H = N.T[tb_home(lo, hi, N.world)];
-            const u32 pp = tb_transfer_find(H, lo, hi);
-            if (pp != TB_NOT_FOUND) {
-                const u64* pw = (const u64*)&H.xlog[pp];
-                plo = pw[6], phi = pw[7], ok = 1;
-            }
-        }
-        P[2 * (u64)i] = plo, P[2 * (u64)i + 1] = phi;
-        found_p[i] = ok;
+        u128 p = 0;
+        found_p[i] = tb_pending_amount(N, pids[2 * (u64)i], pids[2 * (u64)i + 1], &p);
+        P[2 * (u64)i] = tb_lo(p), P[2 * (u64)i + 1] = tb_hi(p);
     }
 }
 
@@ -154,29 +145,12 @@ __global__ __launch_bounds__(CHANGE_THREADS) void tb_change_effects(NodeTablesAr
             } else {
                 const u128 amount = tb_u128(w[6], w[7]);
                 const u32 tf = (u32)(w[14] >> 48);
-                if (tf & TF_PENDING) {
-                    pend = amount;
-                } else if (tf & TF_POST) {
-                    const u64 plo = w[8], phi = w[9];
-                    u128 p = amount;
-                    bool resident = false;
-                    if (!tb_id_reserved(plo, phi)) {
-                        const Tables& H = N.T[tb_home(plo, phi, N.world)];
-                        const u32 pp = tb_transfer_find(H, plo, phi);
-                        if (pp != TB_NOT_FOUND) {
-                            const u64* pw = (const u64*)&H.xlog[pp];
-                            p = tb_u128(pw[6], pw[7]);
-                            resident = true;
-                        }
-                    }
-                    if (!resident) atomicOr((unsigned long long*)(flags + CHANGE_FLAG_ORPHAN), 1ULL);
-                    pend = (u128)0 - p;
-                    post = amount;
-                } else if (tf & TF_VOID) {
-                    pend = (u128)0 - amount;  // a void record stores its pending transfer's amount
-                } else {
-                    post = amount;
+                u128 p = amount;
+                if (tb_effect_is_post(tf) && !tb_pending_amount(N, w[8], w[9], &p)) {
+                    atomicOr((unsigned long long*)(flags + CHANGE_FLAG_ORPHAN), 1ULL);
                 }
+                const BalanceEffect e = tb_balance_effect(tf, amount, p);
+                pend = e.pend, post = e.post;
             }
         }
         // The adds, a side at a time (side 0: the debit columns 0-1, side 1: the credit columns 2-3).

@@ -1705,138 +1705,9 @@ static int node_lookup(TbNode* N, bool accounts, const void* input, u32 input_le
     return TBGPU_STATUS_OK;
 }
 
-// The queries on a node (tbgpu.h).  A transfer lives on its home shard only and an account is answered
-// by its owner only, so every shard scans its own log or table on its own device and stream, side by
-// side (engine.hip query_enqueue / account_query_enqueue), and the host merges the shards' answers —
-// each its first k by timestamp, its last k under `reversed` — under the limit, summing the matches.
-// Both records carry their timestamp in their last word.
-static int node_query_finish(TbNode* N, bool accounts, u32 k, bool reversed, u8* out, tbgpu_query_result* result) {
-    std::vector<std::vector<u8>> recs(N->world);
-    std::vector<u32> cnt(N->world, 0), at(N->world, 0);
-    int status = TBGPU_STATUS_OK;
-    for (u32 d = 0; d < N->world; d++) {  // every shard is waited for, whatever an earlier one returned
-        recs[d].resize((u64)std::max<u32>(k, 1) * 128);
-        u64 m = 0;
-        const int st = accounts ? account_query_collect(N->D[d].E, recs[d].data(), &cnt[d], &m)
-                                : query_collect(N->D[d].E, recs[d].data(), &cnt[d], &m);
-        if (st && status == TBGPU_STATUS_OK) status = st;
-        result->matched += m;
-    }
-    if (status) {
-        result->matched = 0;
-        return status;
-    }
-    u32 w = 0;
-    for (; w < k; w++) {
-        u32 pick = N->world;
-        u64 best = 0;
-        for (u32 d = 0; d < N->world; d++) {
-            if (at[d] == cnt[d]) continue;
-            const u64 ts = *(const u64*)&recs[d][(u64)at[d] * 128 + 120];
-            if (pick == N->world || (reversed ? ts > best : ts < best)) pick = d, best = ts;
-        }
-        if (pick == N->world) break;
-        memcpy(out + (u64)w * 128, &recs[pick][(u64)at[pick] * 128], 128);
-        at[pick]++;
-    }
-    result->count = w;
-    return TBGPU_STATUS_OK;
-}
-
-// get_account_transfers and query_transfers: the log scan under either predicate.
-template <typename F>
-static int node_query_transfers(TbNode* N, const F& flt, bool valid, u32 k, bool reversed, u8* out, tbgpu_query_result* result) {
-    result->complete = 1;
-    for (u32 d = 0; d < N->world; d++) {
-        if (N->D[d].E->evicted_total) result->complete = 0;
-    }
-    if (!valid) return TBGPU_STATUS_OK;
-    for (u32 d = 0; d < N->world; d++) {
-        const int st = query_enqueue(N->D[d].E, flt, k, reversed);
-        if (st) return st;
-    }
-    return node_query_finish(N, false, k, reversed, out, result);
-}
-
-// get_account_balances: the rows are the merged get_account_transfers answer.  Every shard then gets
-// the merged rows' timestamps in its own pinned buffer and scans its own log on its own stream, side
-// by side; a post's pending transfer is read on home(pending_id) through the peers' tables, as
-// tb_node_import reads owners.  The host adds the shards' bins (modulo 2^128, like the device) and
-// anchors them at the balances the account's owner holds.  The sequencer's engine is not asked.
-static int node_account_balances(TbNode* N, const QueryFilter& F, bool valid, u32 k, bool reversed, u8* out,
-                                 tbgpu_query_result* result) {
-    int status = node_query_transfers(N, F, valid, k, reversed, out, result);
-    const u32 m = result->count;
-    result->count = 0;
-    if (status || m == 0) return status;
-    std::vector<u64> ts(m);
-    balance_row_timestamps(out, m, reversed, ts.data());
-    NodeTablesArgs NT{};
-    NT.world = N->world;
-    for (u32 d = 0; d < N->world; d++) NT.T[d] = N->D[d].E->T;
-    u32 issued = 0;
-    for (; issued < N->world && status == TBGPU_STATUS_OK; issued++) {
-        tbgpu* E = N->D[issued].E;
-        memcpy(E->qb.h_ts, ts.data(), (u64)m * 8);
-        status = balance_enqueue(E, NT, issued, F, m);
-    }
-    for (u32 d = 0; d < issued; d++) {  // every shard that launched is waited for
-        const int st = balance_collect(N->D[d].E);
-        if (st && status == TBGPU_STATUS_OK) status = st;
-    }
-    if (status) {
-        result->matched = 0;
-        return status;
-    }
-    std::vector<u128> bins(((u64)m + 1) * 4, 0);
-    bool orphan = false;
-    for (u32 d = 0; d < N->world; d++) {
-        const u64* h = N->D[d].E->qb.h_bins;
-        for (u64 i = 0; i < bins.size(); i++) bins[i] += ((u128)h[2 * i + 1] << 64) | h[2 * i];
-        orphan |= h[((u64)m + 2) * BALANCE_SLOT_WORDS] != 0;
-    }
-    const u64* owner = N->D[tb_home(F.id_lo, F.id_hi, N->world)].E->qb.h_bins;
-    if (!owner[((u64)m + 2) * BALANCE_SLOT_WORDS + 1]) {
-        result->matched = 0;
-        return fail(TBGPU_STATUS_PANIC, "get_account_balances: transfers name an account its owner lacks");
-    }
-    u128 cur[4];
-    for (u32 c = 0; c < 4; c++) cur[c] = balance_word(owner, (u64)m + 1, c);
-    balance_write_rows(out, m, reversed, ts.data(), bins.data(), cur);
-    if (orphan) result->complete = 0;
-    result->count = m;
-    return TBGPU_STATUS_OK;
-}
-
-// get_change_events: the rows are the merged query_transfers answer for the all-zero field filter.
-// change_events_finish (engine.hip) then has every shard sum the effects of its own log on its own
-// device and stream, reads each account from its owner and each post row's pending transfer on its
-// home, and adds the shards' sums on the host.  The sequencer's engine is not asked.
-static int node_change_events(TbNode* N, const QueryFieldFilter& F, bool valid, u32 k, u8* out, tbgpu_query_result* result) {
-    std::vector<u8> rows((u64)std::max<u32>(k, 1) * 128);
-    int status = node_query_transfers(N, F, valid, k, false, rows.data(), result);
-    const u32 m = result->count;
-    result->count = 0;
-    if (status || m == 0) return status;
-    std::vector<tbgpu*> Es(N->world);
-    for (u32 d = 0; d < N->world; d++) Es[d] = N->D[d].E;
-    status = change_events_finish(Es.data(), N->world, rows.data(), m, out, result);
-    if (status) result->matched = 0;
-    return status;
-}
-
-// query_accounts: shard d answers for the accounts with tb_home(id, world) == d — a home's imported
-// copies of foreign accounts do not match, and the sequencer's engine (N->X) is not asked.
-static int node_query_accounts(TbNode* N, const QueryFieldFilter& F, bool valid, u32 k, bool reversed, u8* out,
-                               tbgpu_query_result* result) {
-    result->complete = 1;  // accounts are never evicted
-    if (!valid) return TBGPU_STATUS_OK;
-    for (u32 d = 0; d < N->world; d++) {
-        const int st = account_query_enqueue(N->D[d].E, F, N->world, d, k, reversed);
-        if (st) return st;
-    }
-    return node_query_finish(N, true, k, reversed, out, result);
-}
+// The queries on a node (tbgpu.h) are query.h's: its entry points list the shards through node_world /
+// node_engine and run the same code over them as over one engine.  The sequencer's engine (N->X) is
+// not asked.
 
 // -- the tbgpu.h entry points of a node engine --------------------------------------------------------
 

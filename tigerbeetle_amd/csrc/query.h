@@ -1,0 +1,848 @@
+// query.h — the host side of the queries (include/tbgpu.h): get_account_transfers, get_account_balances,
+// query_transfers, query_accounts and get_change_events; their buffers, made at tbgpu_init, and their
+// entry points.  Included by engine.hip after the engine's own helpers and before node.h.
+//
+// Every query is written once, over a list of engines (QueryCall): the one engine, or a node's shards.
+// A transfer lives on its home shard only and an account is answered by its owner only, so every
+// engine scans its own log or table on its own device and stream, side by side, and the host merges
+// the engines' answers — each its first k by timestamp, its last k under `reversed` — under the
+// limit, summing the matches.  One engine's answer goes straight into the caller's buffer.  The
+// sequencer's engine of a node is never asked.
+#pragma once
+
+// tbgpu_get_account_transfers and tbgpu_query_transfers (k_query.h; one scan, two predicates): every
+// buffer made at tbgpu_init, none shared with the write-back or the lookups (a write-back may be in
+// flight beside a query).
+#define QUERY_KEYS_CAP (1u << 16)  // {timestamp, position} keys of one round of the unordered path
+struct QueryBufs {
+    u64 nb_cap = 0;            // tiles of QUERY_THREADS log positions in the whole log
+    u32* d_counts = nullptr;   // [nb_cap] matches per tile
+    u64* d_mins = nullptr;     // [nb_cap] their smallest timestamp
+    u64* d_maxs = nullptr;     // [nb_cap] ... and largest
+    u32* d_ordered = nullptr;  // [nb_cap] 1: the tile's matches rise with position
+    u64* d_base = nullptr;     // [nb_cap] exclusive prefix of d_counts
+    u64* d_res = nullptr;      // {total, ordered}
+    u64* h_res = nullptr;      // pinned mirror
+    u8* d_out = nullptr;       // [BATCH_EVENTS_MAX] the answer's records
+    u64* d_keys = nullptr;     // [QUERY_KEYS_CAP][2] unordered path: a round's keys; then the chosen positions
+    u64* h_keys = nullptr;     // pinned mirror
+    u64* h_base = nullptr;     // pinned [nb_cap + 1]: the bases, read back on the unordered path only
+    u32 keys_max = QUERY_KEYS_CAP;  // tbgpu_bench_query_keys_max
+    bool coop = false;         // tb_query_count's load shape (TBGPU_QUERY_COOP=1: cooperative 16-B chunks)
+    // One query in flight between query_enqueue and query_collect.
+    QueryFilter F{};
+    QueryFieldFilter FF{};   // by_fields: tbgpu_query_transfers' predicate instead
+    bool by_fields = false;
+    u32 k = 0;
+    bool reversed = false;
+    u64 n = 0;
+};
+
+// tbgpu_get_account_balances (k_balances.h): the rows' timestamps and the bins, on the device and
+// pinned; made at tbgpu_init and shared with nothing.  The rows themselves are chosen through QueryBufs.
+struct BalanceBufs {
+    u64* d_ts = nullptr;    // [BATCH_EVENTS_MAX] the rows' timestamps, ascending
+    u64* h_ts = nullptr;    // pinned mirror (a node hands every shard the merged rows' here)
+    u64* d_bins = nullptr;  // [BALANCE_SLOTS(BATCH_EVENTS_MAX)][BALANCE_SLOT_WORDS]
+    u64* h_bins = nullptr;  // pinned mirror
+};
+
+// tbgpu_query_accounts (k_query_filter.h): O(slots / 256 + histogram + k) device memory, made at
+// tbgpu_init and shared with nothing.
+struct AccountQueryBufs {
+    u64 nb = 0;               // tiles of QUERY_THREADS slots in the account table
+    u32* d_counts = nullptr;  // [nb] matches per tile
+    u64* d_mins = nullptr;    // [nb] their smallest timestamp
+    u64* d_maxs = nullptr;    // [nb] ... and largest
+    u64* d_state = nullptr;   // [QA_WORDS], then the select's histograms: u32 [QA_PASSES][QA_BINS]
+    u64* h_state = nullptr;   // pinned mirror of the QA_WORDS
+    u64* d_keys = nullptr;    // [BATCH_EVENTS_MAX][2] {value, slot} of the selected matches
+    u8* d_out = nullptr;      // [BATCH_EVENTS_MAX] the answer's records
+    u32 k = 0;                // one query in flight between account_query_enqueue and _collect
+    u64 last_scans = 0;       // select passes of the last query (tbgpu_bench_query_select_scans)
+};
+#define QA_STATE_BYTES ((u64)QA_WORDS * 8 + (u64)QA_PASSES * QA_BINS * 4)
+
+// tbgpu_get_change_events (k_change_events.h): the page's account set, the bins, the accounts' records
+// and the post rows' pending amounts, on the device and pinned; made at tbgpu_init after every other
+// buffer and shared with nothing.  The rows themselves are chosen through QueryBufs.
+struct ChangeBufs {
+    u32* d_set = nullptr;     // [CHANGE_SET_SLOTS_MAX] the set's entries
+    u64* d_ids = nullptr;     // [CHANGE_ACCOUNTS_MAX][2] the accounts' ids by index
+    u64* d_pids = nullptr;    // [CHANGE_EVENTS_MAX][2] the post rows' pending ids
+    u64* d_bins = nullptr;    // [CHANGE_ACCOUNTS_MAX + 1][BALANCE_SLOT_WORDS] the bins, then the flag slot
+    u8* d_accounts = nullptr; // [CHANGE_ACCOUNTS_MAX] the accounts' records
+    u32* d_found = nullptr;   // [CHANGE_ACCOUNTS_MAX] ... and whether the owner holds them
+    u64* d_p = nullptr;       // [CHANGE_EVENTS_MAX][2] the post rows' pending amounts
+    u32* d_found_p = nullptr; // [CHANGE_EVENTS_MAX] ... and whether the pending transfer is resident
+    u32* h_set = nullptr;     // pinned mirrors (a node hands every shard the page's set here)
+    u64* h_ids = nullptr;
+    u64* h_pids = nullptr;
+    u64* h_bins = nullptr;
+    u8* h_accounts = nullptr;
+    u32* h_found = nullptr;
+    u64* h_p = nullptr;
+    u32* h_found_p = nullptr;
+    u8* h_rows = nullptr;     // pinned [CHANGE_EVENTS_MAX] the rows, before they are assembled into `out`
+    u32* h_row_idx = nullptr; // host [CHANGE_EVENTS_MAX][2] the rows' debit and credit account index
+};
+
+// One engine's query buffers (tbgpu::qs), in the order query_init makes them.
+struct QueryState {
+    QueryBufs q;
+    BalanceBufs qb;
+    AccountQueryBufs qa;
+    ChangeBufs qc;
+};
+
+// Called by tbgpu_init on the engine's device, after every other buffer; tbgpu_deinit calls query_free
+// whether or not query_init finished.
+static int query_init(tbgpu* E) {
+#define QINIT_CK(x)                                                                      \
+    do {                                                                                 \
+        const hipError_t e_ = (x);                                                       \
+        if (e_ != hipSuccess) return fail(TBGPU_STATUS_DEVICE, "%s: %s", #x, hipGetErrorString(e_)); \
+    } while (0)
+    E->qs = new QueryState();
+    {  // the log scan: per-tile counts and bounds, the answer, the unordered path's keys
+        QueryBufs& Q = E->qs->q;
+        Q.nb_cap = (E->xlog_cap + QUERY_THREADS - 1) / QUERY_THREADS;
+        QINIT_CK(tbMalloc(&Q.d_counts, Q.nb_cap * 4));
+        QINIT_CK(tbMalloc(&Q.d_mins, Q.nb_cap * 8));
+        QINIT_CK(tbMalloc(&Q.d_maxs, Q.nb_cap * 8));
+        QINIT_CK(tbMalloc(&Q.d_ordered, Q.nb_cap * 4));
+        QINIT_CK(tbMalloc(&Q.d_base, Q.nb_cap * 8));
+        QINIT_CK(tbMalloc(&Q.d_res, 16));
+        QINIT_CK(tbHostMalloc(&Q.h_res, 16, hipHostMallocDefault));
+        QINIT_CK(tbMalloc(&Q.d_out, (u64)BATCH_EVENTS_MAX * 128));
+        QINIT_CK(tbMalloc(&Q.d_keys, (u64)QUERY_KEYS_CAP * 16));
+        QINIT_CK(tbHostMalloc(&Q.h_keys, (u64)QUERY_KEYS_CAP * 16, hipHostMallocDefault));
+        QINIT_CK(tbHostMalloc(&Q.h_base, (Q.nb_cap + 1) * 8, hipHostMallocDefault));
+        if (const char* v = getenv("TBGPU_QUERY_COOP")) Q.coop = atoi(v) != 0;  // the load-shape measurement
+    }
+    {  // tbgpu_get_account_balances: the rows' timestamps and the bins
+        BalanceBufs& B = E->qs->qb;
+        QINIT_CK(tbMalloc(&B.d_ts, (u64)BATCH_EVENTS_MAX * 8));
+        QINIT_CK(tbHostMalloc(&B.h_ts, (u64)BATCH_EVENTS_MAX * 8, hipHostMallocDefault));
+        QINIT_CK(tbMalloc(&B.d_bins, BALANCE_SLOTS(BATCH_EVENTS_MAX) * BALANCE_SLOT_WORDS * 8));
+        QINIT_CK(tbHostMalloc(&B.h_bins, BALANCE_SLOTS(BATCH_EVENTS_MAX) * BALANCE_SLOT_WORDS * 8, hipHostMallocDefault));
+    }
+    {  // tbgpu_query_accounts: per-tile counts and bounds, the select's state and histograms, keys, the answer
+        AccountQueryBufs& A = E->qs->qa;
+        A.nb = (E->account_cap + QUERY_THREADS - 1) / QUERY_THREADS;
+        QINIT_CK(tbMalloc(&A.d_counts, A.nb * 4));
+        QINIT_CK(tbMalloc(&A.d_mins, A.nb * 8));
+        QINIT_CK(tbMalloc(&A.d_maxs, A.nb * 8));
+        QINIT_CK(tbMalloc(&A.d_state, QA_STATE_BYTES));
+        QINIT_CK(tbHostMalloc(&A.h_state, (u64)QA_WORDS * 8, hipHostMallocDefault));
+        QINIT_CK(tbMalloc(&A.d_keys, (u64)BATCH_EVENTS_MAX * 16));
+        QINIT_CK(tbMalloc(&A.d_out, (u64)BATCH_EVENTS_MAX * 128));
+    }
+    {  // tbgpu_get_change_events: the set, the bins, the accounts, the pending amounts, the rows
+        ChangeBufs& C = E->qs->qc;
+        const u64 na = CHANGE_ACCOUNTS_MAX, nr = CHANGE_EVENTS_MAX;
+        QINIT_CK(tbMalloc(&C.d_set, (u64)CHANGE_SET_SLOTS_MAX * 4));
+        QINIT_CK(tbMalloc(&C.d_ids, na * 16));
+        QINIT_CK(tbMalloc(&C.d_pids, nr * 16));
+        QINIT_CK(tbMalloc(&C.d_bins, (na + 1) * BALANCE_SLOT_WORDS * 8));
+        QINIT_CK(tbMalloc(&C.d_accounts, na * 128));
+        QINIT_CK(tbMalloc(&C.d_found, na * 4));
+        QINIT_CK(tbMalloc(&C.d_p, nr * 16));
+        QINIT_CK(tbMalloc(&C.d_found_p, nr * 4));
+        QINIT_CK(tbHostMalloc(&C.h_set, (u64)CHANGE_SET_SLOTS_MAX * 4, hipHostMallocDefault));
+        QINIT_CK(tbHostMalloc(&C.h_ids, na * 16, hipHostMallocDefault));
+        QINIT_CK(tbHostMalloc(&C.h_pids, nr * 16, hipHostMallocDefault));
+        QINIT_CK(tbHostMalloc(&C.h_bins, (na + 1) * BALANCE_SLOT_WORDS * 8, hipHostMallocDefault));
+        QINIT_CK(tbHostMalloc(&C.h_accounts, na * 128, hipHostMallocDefault));
+        QINIT_CK(tbHostMalloc(&C.h_found, na * 4, hipHostMallocDefault));
+        QINIT_CK(tbHostMalloc(&C.h_p, nr * 16, hipHostMallocDefault));
+        QINIT_CK(tbHostMalloc(&C.h_found_p, nr * 4, hipHostMallocDefault));
+        QINIT_CK(tbHostMalloc(&C.h_rows, nr * 128, hipHostMallocDefault));
+        QINIT_CK(tbHostMalloc(&C.h_row_idx, nr * 8, hipHostMallocDefault));
+    }
+#undef QINIT_CK
+    return TBGPU_STATUS_OK;
+}
+
+static void query_free(tbgpu* E) {
+    if (!E->qs) return;
+    const QueryBufs& Q = E->qs->q;
+    const BalanceBufs& B = E->qs->qb;
+    const AccountQueryBufs& A = E->qs->qa;
+    const ChangeBufs& C = E->qs->qc;
+    for (void* p : {(void*)Q.d_counts, (void*)Q.d_mins, (void*)Q.d_maxs, (void*)Q.d_ordered, (void*)Q.d_base, (void*)Q.d_res,
+                    (void*)Q.d_out, (void*)Q.d_keys, (void*)B.d_ts, (void*)B.d_bins, (void*)A.d_counts, (void*)A.d_mins,
+                    (void*)A.d_maxs, (void*)A.d_state, (void*)A.d_keys, (void*)A.d_out, (void*)C.d_set, (void*)C.d_ids,
+                    (void*)C.d_pids, (void*)C.d_bins, (void*)C.d_accounts, (void*)C.d_found, (void*)C.d_p, (void*)C.d_found_p}) {
+        if (p) (void)hipFree(p);
+    }
+    for (void* p : {(void*)Q.h_res, (void*)Q.h_keys, (void*)Q.h_base, (void*)B.h_ts, (void*)B.h_bins, (void*)A.h_state,
+                    (void*)C.h_set, (void*)C.h_ids, (void*)C.h_pids, (void*)C.h_bins, (void*)C.h_accounts, (void*)C.h_found,
+                    (void*)C.h_p, (void*)C.h_found_p, (void*)C.h_rows, (void*)C.h_row_idx}) {
+        if (p) (void)hipHostFree(p);
+    }
+    delete E->qs;
+    E->qs = nullptr;
+}
+
+// ---- the engine list and what every entry point does first and last --------------------------------
+struct QueryCall {
+    tbgpu* Es[NODE_WORLD_MAX];  // the engine itself, or a node's shards
+    u32 world = 0;
+    u32 k = 0;                  // records asked for: the filter's limit under the caller's room and k_max
+};
+
+// A read: legal on a stopped engine, like the exports.  Zeroes `result`, lists the engines and sets
+// `complete`: of a log query (`evictable`), 1 while no listed engine has evicted a transfer; of the
+// account table, always 1 (accounts are never evicted).
+template <typename FILTER>
+static int query_begin(tbgpu* E, const char* name, const FILTER* filter, const void* out, u32 out_cap, u32 k_max,
+                       bool evictable, tbgpu_query_result* result, QueryCall* c) {
+    API_ENTER(E, false);
+    if (!filter || !out || !result) return fail(TBGPU_STATUS_INVALID, "%s: a NULL filter, out or result", name);
+    result->count = 0;
+    result->matched = 0;
+    result->complete = 1;
+    c->world = E->node ? node_world(E->node) : 1;
+    for (u32 d = 0; d < c->world; d++) {
+        c->Es[d] = E->node ? node_engine(E->node, d) : E;
+        if (evictable && c->Es[d]->evicted_total) result->complete = 0;
+    }
+    c->k = std::min<u32>(std::min<u32>(filter->limit, out_cap), k_max);  // one reply is one message body
+    return TBGPU_STATUS_OK;
+}
+
+// After any failing status the result names no records.
+static int query_end(tbgpu_query_result* result, int status) {
+    if (status) result->count = 0, result->matched = 0;
+    return status;
+}
+
+// The first k records of `world` answers by their last word, the timestamp (the last k, newest first,
+// under `reversed`): answer d is cnt[d] records of 128 B at recs + d * stride, in that order itself.
+static u32 query_merge(const u8* recs, u64 stride, const u32* cnt, u32 world, u32 k, bool reversed, u8* out) {
+    u32 at[NODE_WORLD_MAX] = {};
+    u32 w = 0;
+    for (; w < k; w++) {
+        u32 pick = world;
+        u64 best = 0;
+        for (u32 d = 0; d < world; d++) {
+            if (at[d] == cnt[d]) continue;
+            u64 ts;
+            memcpy(&ts, recs + d * stride + (u64)at[d] * 128 + 120, 8);
+            if (pick == world || (reversed ? ts > best : ts < best)) pick = d, best = ts;
+        }
+        if (pick == world) break;
+        memcpy(out + (u64)w * 128, recs + pick * stride + (u64)at[pick] * 128, 128);
+        at[pick]++;
+    }
+    return w;
+}
+
+// The answers of the engines' enqueued scans into `out` (room for c.k records): one engine's as it
+// is, a node's merged.  Every engine is waited for, whatever an earlier one returned.
+template <typename COLLECT>
+static int query_collect_all(const QueryCall& c, bool reversed, u8* out, tbgpu_query_result* result, COLLECT collect) {
+    u32 cnt[NODE_WORLD_MAX] = {};
+    u64 matched = 0;
+    if (c.world == 1) {
+        const int st = collect(c.Es[0], out, &cnt[0], &matched);
+        if (st) return st;
+        result->count = cnt[0];
+        result->matched = matched;
+        return TBGPU_STATUS_OK;
+    }
+    const u64 stride = (u64)std::max<u32>(c.k, 1) * 128;
+    std::vector<u8> recs(c.world * stride);
+    int status = TBGPU_STATUS_OK;
+    for (u32 d = 0; d < c.world; d++) {
+        u64 m = 0;
+        const int st = collect(c.Es[d], recs.data() + d * stride, &cnt[d], &m);
+        if (st && status == TBGPU_STATUS_OK) status = st;
+        matched += m;
+    }
+    if (status) return status;
+    result->count = query_merge(recs.data(), stride, cnt, c.world, c.k, reversed, out);
+    result->matched = matched;
+    return TBGPU_STATUS_OK;
+}
+
+// ---- get_account_transfers (k_query.h, include/tbgpu.h) -------------------------------------------
+// The scan of one engine's log in two halves, so that a node runs its shards' scans side by side:
+// query_enqueue puts count -> scan -> scatter on the engine stream (nothing crosses PCIe but the
+// {total, ordered} word); query_collect waits, copies the answer's records, and runs the exact path
+// of a log out of timestamp order when the scan found one.  The stream is drained before (a pending
+// tbgpu_commit_device_async), so log_next is the log's end and nothing writes beside the scan.
+static void query_keep_filter(QueryBufs& Q, const QueryFilter& F) { Q.F = F, Q.by_fields = false; }
+static void query_keep_filter(QueryBufs& Q, const QueryFieldFilter& F) { Q.FF = F, Q.by_fields = true; }
+
+template <typename FILTER>
+static int query_enqueue(tbgpu* E, const FILTER& F, u32 k, bool reversed) {
+    constexpr bool by_account = std::is_same<FILTER, QueryFilter>::value;
+    QueryBufs& Q = E->qs->q;
+    HIPCK(hipSetDevice(E->device));
+    if (E->pending) {
+        int st = engine_sync(E);
+        if (st) return st;
+    }
+    query_keep_filter(Q, F);
+    Q.k = k;
+    Q.reversed = reversed;
+    Q.n = E->log_next;
+    Q.h_res[0] = Q.h_res[1] = 0;
+    const u64 nb = (Q.n + QUERY_THREADS - 1) / QUERY_THREADS;
+    if (nb == 0) return TBGPU_STATUS_OK;
+    if (nb > Q.nb_cap) return fail(TBGPU_STATUS_PANIC, "query: the log's end %llu is past its capacity", (unsigned long long)Q.n);
+    if constexpr (by_account) {
+        if (Q.coop) {
+            hipLaunchKernelGGL((tb_query_count<true, QueryFilter>), dim3((unsigned)nb), dim3(QUERY_THREADS), 0, E->stream, E->T,
+                               F, Q.n, Q.d_counts, Q.d_mins, Q.d_maxs, Q.d_ordered);
+        } else {
+            hipLaunchKernelGGL((tb_query_count<false, QueryFilter>), dim3((unsigned)nb), dim3(QUERY_THREADS), 0, E->stream, E->T,
+                               F, Q.n, Q.d_counts, Q.d_mins, Q.d_maxs, Q.d_ordered);
+        }
+    } else {
+        hipLaunchKernelGGL((tb_query_count<false, FILTER>), dim3((unsigned)nb), dim3(QUERY_THREADS), 0, E->stream, E->T, F, Q.n,
+                           Q.d_counts, Q.d_mins, Q.d_maxs, Q.d_ordered);
+    }
+    hipLaunchKernelGGL(tb_query_scan, dim3(1), dim3(1024), 0, E->stream, Q.d_counts, Q.d_mins, Q.d_maxs, Q.d_ordered, nb,
+                       Q.d_base, Q.d_res);
+    hipLaunchKernelGGL(tb_query_scatter<FILTER>, dim3((unsigned)nb), dim3(QUERY_THREADS), 0, E->stream, E->T, F, Q.n,
+                       Q.d_counts, Q.d_base, Q.d_res, k, reversed ? 1u : 0u, Q.d_out);
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpyAsync(Q.h_res, Q.d_res, 16, hipMemcpyDeviceToHost, E->stream));
+    return TBGPU_STATUS_OK;
+}
+
+// out: room for the enqueued k records.  *count = records written, *matched = every match.
+static int query_collect(tbgpu* E, u8* out, u32* count, u64* matched) {
+    QueryBufs& Q = E->qs->q;
+    *count = 0;
+    *matched = 0;
+    const u64 nb = (Q.n + QUERY_THREADS - 1) / QUERY_THREADS;
+    if (nb == 0) return TBGPU_STATUS_OK;
+    HIPCK(hipSetDevice(E->device));
+    HIPCK(hipStreamSynchronize(E->stream));
+    const u64 total = Q.h_res[0];
+    const bool ordered = Q.h_res[1] != 0;
+    const u32 m = (u32)std::min<u64>(Q.k, total);
+    *matched = total;
+    if (m == 0) return TBGPU_STATUS_OK;
+    if (!ordered) {
+        // Exact with bounded memory: rounds over ranges of tiles whose matches fit the key buffer (the
+        // bases say which), the best m keys kept across rounds, then one gather of their records.
+        HIPCK(hipMemcpyAsync(Q.h_base, Q.d_base, nb * 8, hipMemcpyDeviceToHost, E->stream));
+        HIPCK(hipStreamSynchronize(E->stream));
+        Q.h_base[nb] = total;
+        typedef std::pair<u64, u64> Key;  // {timestamp, position}
+        std::vector<Key> best;
+        const bool rev = Q.reversed;
+        auto before = [rev](const Key& a, const Key& b) { return rev ? a > b : a < b; };
+        auto cut = [&]() {
+            if (best.size() <= m) return;
+            std::nth_element(best.begin(), best.begin() + m, best.end(), before);
+            best.resize(m);
+        };
+        u64 b0 = 0;
+        while (b0 < nb && Q.h_base[b0] < total) {
+            // Skip tiles without a match, then take tiles while their matches fit (a tile holds at most
+            // QUERY_THREADS <= keys_max, so every round advances).
+            b0 = (u64)(std::upper_bound(Q.h_base + b0, Q.h_base + nb + 1, Q.h_base[b0]) - Q.h_base) - 1;
+            const u64 b1 = (u64)(std::upper_bound(Q.h_base + b0, Q.h_base + nb + 1, Q.h_base[b0] + Q.keys_max) - Q.h_base) - 1;
+            const u64 keys = Q.h_base[b1] - Q.h_base[b0];
+            if (b1 <= b0 || keys > Q.keys_max) return fail(TBGPU_STATUS_PANIC, "query: a round of %llu keys", (unsigned long long)keys);
+            if (Q.by_fields) {
+                hipLaunchKernelGGL(tb_query_keys<QueryFieldFilter>, dim3((unsigned)(b1 - b0)), dim3(QUERY_THREADS), 0, E->stream,
+                                   E->T, Q.FF, Q.n, b0, Q.d_counts, Q.d_base, Q.d_keys, (u64)Q.keys_max);
+            } else {
+                hipLaunchKernelGGL(tb_query_keys<QueryFilter>, dim3((unsigned)(b1 - b0)), dim3(QUERY_THREADS), 0, E->stream, E->T,
+                                   Q.F, Q.n, b0, Q.d_counts, Q.d_base, Q.d_keys, (u64)Q.keys_max);
+            }
+            HIPCK(hipGetLastError());
+            HIPCK(hipMemcpyAsync(Q.h_keys, Q.d_keys, keys * 16, hipMemcpyDeviceToHost, E->stream));
+            HIPCK(hipStreamSynchronize(E->stream));
+            for (u64 i = 0; i < keys; i++) best.push_back(Key(Q.h_keys[2 * i], Q.h_keys[2 * i + 1]));
+            if (best.size() > 2 * (size_t)m + Q.keys_max) cut();
+            b0 = b1;
+        }
+        cut();
+        std::sort(best.begin(), best.end(), before);
+        if (best.size() != m) return fail(TBGPU_STATUS_PANIC, "query: %zu keys for %u matches", best.size(), m);
+        for (u32 i = 0; i < m; i++) Q.h_keys[i] = best[i].second;
+        HIPCK(hipMemcpyAsync(Q.d_keys, Q.h_keys, (u64)m * 8, hipMemcpyHostToDevice, E->stream));
+        hipLaunchKernelGGL(tb_query_gather, dim3((m + QUERY_THREADS - 1) / QUERY_THREADS), dim3(QUERY_THREADS), 0, E->stream,
+                           E->T, Q.d_keys, m, Q.n, Q.d_out);
+        HIPCK(hipGetLastError());
+    }
+    HIPCK(hipMemcpyAsync(out, Q.d_out, (u64)m * 128, hipMemcpyDeviceToHost, E->stream));
+    HIPCK(hipStreamSynchronize(E->stream));
+    *count = m;
+    return TBGPU_STATUS_OK;
+}
+
+// The log scan under either predicate on every listed engine: result->count rows in `out`.
+template <typename FILTER>
+static int query_log_rows(const QueryCall& c, const FILTER& F, bool reversed, u8* out, tbgpu_query_result* result) {
+    for (u32 d = 0; d < c.world; d++) {
+        const int st = query_enqueue(c.Es[d], F, c.k, reversed);
+        if (st) return st;
+    }
+    return query_collect_all(c, reversed, out, result, query_collect);
+}
+
+// The filter's rules (tbgpu.h): an invalid filter answers nothing, it is never a status.
+static bool query_filter_valid(const tbgpu_account_filter* f) {
+    if (tb_id_reserved(f->account_id_lo, f->account_id_hi)) return false;
+    if (f->timestamp_min == ~0ULL || f->timestamp_max == ~0ULL) return false;
+    if (f->timestamp_max != 0 && f->timestamp_max < f->timestamp_min) return false;
+    if (f->limit == 0) return false;
+    if (!(f->flags & (TBGPU_FILTER_DEBITS | TBGPU_FILTER_CREDITS))) return false;
+    if (f->flags & ~(TBGPU_FILTER_DEBITS | TBGPU_FILTER_CREDITS | TBGPU_FILTER_REVERSED)) return false;
+    for (u8 b : f->reserved) if (b) return false;
+    return true;
+}
+
+static QueryFilter query_account_filter_of(const tbgpu_account_filter* f) {
+    QueryFilter F{};
+    F.id_lo = f->account_id_lo;
+    F.id_hi = f->account_id_hi;
+    F.ts_min = f->timestamp_min;
+    F.ts_max = f->timestamp_max ? f->timestamp_max : ~0ULL;
+    F.debits = (f->flags & TBGPU_FILTER_DEBITS) != 0;
+    F.credits = (f->flags & TBGPU_FILTER_CREDITS) != 0;
+    return F;
+}
+
+extern "C" int tbgpu_get_account_transfers(tbgpu_t* E, const tbgpu_account_filter* filter, void* out,
+                                           uint32_t out_cap_records, tbgpu_query_result* result) {
+    QueryCall c;
+    if (const int st = query_begin(E, "get_account_transfers", filter, out, out_cap_records, BATCH_EVENTS_MAX, true, result, &c)) {
+        return st;
+    }
+    if (!query_filter_valid(filter)) return TBGPU_STATUS_OK;
+    const bool reversed = (filter->flags & TBGPU_FILTER_REVERSED) != 0;
+    return query_end(result, query_log_rows(c, query_account_filter_of(filter), reversed, (u8*)out, result));
+}
+
+// ---- get_account_balances (k_balances.h, include/tbgpu.h) -----------------------------------------
+// The rows are get_account_transfers' answer, left in `out`; the second scan runs in two halves like
+// the first, so that a node's shards scan side by side.  balance_enqueue: the rows' ascending
+// timestamps (in B.h_ts) go to the device, the bins are zeroed, tb_balance_effects runs over this
+// engine's log, and the k + 1 bins, the account's balances and the two flag words come back.
+// NT: every engine whose log may hold a post's pending transfer (a single engine: itself).
+static int balance_enqueue(tbgpu* E, const NodeTablesArgs& NT, u32 self, const QueryFilter& rows, u32 k) {
+    BalanceBufs& B = E->qs->qb;
+    HIPCK(hipSetDevice(E->device));
+    QueryFilter F = rows;
+    F.debits = F.credits = 1;  // the flags and the window choose rows, not what is summed
+    F.ts_min = B.h_ts[0] + 1;
+    F.ts_max = ~0ULL;
+    const u64 n = E->log_next, per = (u64)QUERY_THREADS * BALANCE_TILES, nb = (n + per - 1) / per;
+    const u64 bytes = BALANCE_SLOTS(k) * BALANCE_SLOT_WORDS * 8;
+    HIPCK(hipMemcpyAsync(B.d_ts, B.h_ts, (u64)k * 8, hipMemcpyHostToDevice, E->stream));
+    HIPCK(hipMemsetAsync(B.d_bins, 0, bytes, E->stream));
+    // A shard without a record still answers for the account it may own: one workgroup.
+    hipLaunchKernelGGL(tb_balance_effects, dim3((unsigned)std::max<u64>(nb, 1)), dim3(QUERY_THREADS), 0, E->stream, NT, self, F,
+                       n, B.d_ts, k, B.d_bins);
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpyAsync(B.h_bins, B.d_bins, bytes, hipMemcpyDeviceToHost, E->stream));
+    return TBGPU_STATUS_OK;
+}
+
+static int query_wait(tbgpu* E) {
+    HIPCK(hipSetDevice(E->device));
+    HIPCK(hipStreamSynchronize(E->stream));
+    return TBGPU_STATUS_OK;
+}
+
+// `enqueue(d)` on every listed engine in turn, until one fails; then every engine that launched is
+// waited for, whatever an earlier one returned.
+template <typename ENQUEUE>
+static int query_side_by_side(tbgpu* const* Es, u32 world, ENQUEUE enqueue) {
+    int status = TBGPU_STATUS_OK;
+    u32 issued = 0;
+    for (; issued < world && status == TBGPU_STATUS_OK; issued++) status = enqueue(issued);
+    for (u32 d = 0; d < issued; d++) {
+        const int st = query_wait(Es[d]);
+        if (st && status == TBGPU_STATUS_OK) status = st;
+    }
+    return status;
+}
+
+// The k rows' ascending timestamps from the k records of an answer (their last word).
+static void balance_row_timestamps(const u8* out, u32 k, bool reversed, u64* ts) {
+    for (u32 i = 0; i < k; i++) memcpy(&ts[i], out + (u64)(reversed ? k - 1 - i : i) * 128 + 120, 8);
+}
+
+// bins: [k + 1][4] summed over every engine that scanned; cur: the account's current balances.  Row i
+// by timestamp holds cur minus the bins above i, per column modulo 2^128, and goes where record i was.
+static void balance_write_rows(u8* out, u32 k, bool reversed, const u64* ts, const u128* bins, const u128 cur[4]) {
+    u128 later[4] = {0, 0, 0, 0};
+    for (u32 i = k; i-- > 0;) {
+        tbgpu_account_balance row{};
+        u64* w = &row.debits_pending_lo;
+        for (u32 c = 0; c < 4; c++) {
+            later[c] += bins[((u64)i + 1) * 4 + c];
+            const u128 v = cur[c] - later[c];
+            w[2 * c] = (u64)v, w[2 * c + 1] = (u64)(v >> 64);
+        }
+        row.timestamp = ts[i];
+        memcpy(out + (u64)(reversed ? k - 1 - i : i) * 128, &row, 128);
+    }
+}
+
+// The m rows in `out` become their balance rows.  Every listed engine gets the rows' timestamps in its
+// own pinned buffer and scans its own log on its own stream; a post's pending transfer is read on
+// home(pending_id) through the peers' tables, as tb_node_import reads owners.  The host adds the
+// engines' bins into Es[0]'s in place (modulo 2^128, like the device; a slot is 4 x {lo, hi},
+// little-endian, so the bins are u128s as they lie) and anchors them at the balances the account's
+// owner holds.
+static int balances_finish(const QueryCall& c, const QueryFilter& F, bool reversed, u32 m, u8* out, tbgpu_query_result* result) {
+    BalanceBufs& B = c.Es[0]->qs->qb;
+    balance_row_timestamps(out, m, reversed, B.h_ts);
+    NodeTablesArgs NT{};
+    NT.world = c.world;
+    for (u32 d = 0; d < c.world; d++) NT.T[d] = c.Es[d]->T;
+    const int status = query_side_by_side(c.Es, c.world, [&](u32 d) -> int {
+        if (d) memcpy(c.Es[d]->qs->qb.h_ts, B.h_ts, (u64)m * 8);
+        return balance_enqueue(c.Es[d], NT, d, F, m);
+    });
+    if (status) return status;
+    const u64 flag_words = ((u64)m + 2) * BALANCE_SLOT_WORDS;  // behind the bins and the balances' slot
+    const u64* owner = c.Es[tb_home(F.id_lo, F.id_hi, c.world)]->qs->qb.h_bins;
+    if (!owner[flag_words + 1]) return fail(TBGPU_STATUS_PANIC, "get_account_balances: transfers name an account its owner lacks");
+    u128 cur[4];
+    memcpy(cur, owner + flag_words - BALANCE_SLOT_WORDS, sizeof cur);
+    u128* bins = (u128*)B.h_bins;
+    bool orphan = B.h_bins[flag_words] != 0;
+    for (u32 d = 1; d < c.world; d++) {
+        const u64* h = c.Es[d]->qs->qb.h_bins;
+        for (u64 i = 0; i < ((u64)m + 1) * 4; i++) bins[i] += ((const u128*)h)[i];
+        orphan |= h[flag_words] != 0;
+    }
+    balance_write_rows(out, m, reversed, B.h_ts, bins, cur);
+    if (orphan) result->complete = 0;
+    result->count = m;
+    return TBGPU_STATUS_OK;
+}
+
+extern "C" int tbgpu_get_account_balances(tbgpu_t* E, const tbgpu_account_filter* filter, void* out,
+                                          uint32_t out_cap_records, tbgpu_query_result* result) {
+    QueryCall c;
+    if (const int st = query_begin(E, "get_account_balances", filter, out, out_cap_records, BATCH_EVENTS_MAX, true, result, &c)) {
+        return st;
+    }
+    if (!query_filter_valid(filter)) return TBGPU_STATUS_OK;
+    const QueryFilter F = query_account_filter_of(filter);
+    const bool reversed = (filter->flags & TBGPU_FILTER_REVERSED) != 0;
+    int st = query_log_rows(c, F, reversed, (u8*)out, result);
+    const u32 m = result->count;
+    result->count = 0;
+    if (st == TBGPU_STATUS_OK && m) st = balances_finish(c, F, reversed, m, (u8*)out, result);
+    return query_end(result, st);
+}
+
+// ---- query_transfers / query_accounts (k_query.h, k_query_filter.h, include/tbgpu.h) --------------
+static bool query_fields_valid(const tbgpu_query_filter* f) {
+    if (f->timestamp_min == ~0ULL || f->timestamp_max == ~0ULL) return false;
+    if (f->timestamp_max != 0 && f->timestamp_max < f->timestamp_min) return false;
+    if (f->limit == 0) return false;
+    if (f->flags & ~TBGPU_QUERY_REVERSED) return false;
+    for (u8 b : f->reserved) if (b) return false;
+    return true;
+}
+
+static QueryFieldFilter query_fields_of(const tbgpu_query_filter* f) {
+    QueryFieldFilter F{};
+    F.u128_lo = f->user_data_128_lo;
+    F.u128_hi = f->user_data_128_hi;
+    F.u64v = f->user_data_64;
+    F.u32v = f->user_data_32;
+    F.ledger = f->ledger;
+    F.code = f->code;
+    F.ts_min = f->timestamp_min;
+    F.ts_max = f->timestamp_max ? f->timestamp_max : ~0ULL;
+    return F;
+}
+
+extern "C" int tbgpu_query_transfers(tbgpu_t* E, const tbgpu_query_filter* filter, void* out, uint32_t out_cap_records,
+                                     tbgpu_query_result* result) {
+    QueryCall c;
+    if (const int st = query_begin(E, "query_transfers", filter, out, out_cap_records, BATCH_EVENTS_MAX, true, result, &c)) return st;
+    if (!query_fields_valid(filter)) return TBGPU_STATUS_OK;
+    const bool reversed = (filter->flags & TBGPU_QUERY_REVERSED) != 0;
+    return query_end(result, query_log_rows(c, query_fields_of(filter), reversed, (u8*)out, result));
+}
+
+// The account table in two halves, as the log scan: account_query_enqueue puts count -> scan -> the
+// select's passes -> collect -> emit on the engine stream, back to back (a pass that has nothing to
+// decide exits on the device); account_query_collect waits for the state words, then copies the
+// answer's records.  Nothing else crosses PCIe.  world != 0: a node shard answers for what it owns.
+static int account_query_enqueue(tbgpu* E, const QueryFieldFilter& F, u32 world, u32 self, u32 k, bool reversed) {
+    AccountQueryBufs& A = E->qs->qa;
+    HIPCK(hipSetDevice(E->device));
+    if (E->pending) {
+        int st = engine_sync(E);
+        if (st) return st;
+    }
+    A.k = k;
+    QaPred P{};
+    P.f = F;
+    P.world = world;
+    P.self = self;
+    P.cold = F.wants_u128() || F.u64v || F.u32v;
+    const u64 cap = E->account_cap, nb = A.nb;
+    const u32 rev = reversed ? 1u : 0u;
+    const unsigned wide = (unsigned)((nb + QA_TILES - 1) / QA_TILES);
+    u32* hist = (u32*)(A.d_state + QA_WORDS);
+    HIPCK(hipMemsetAsync(A.d_state, 0, QA_STATE_BYTES, E->stream));
+    hipLaunchKernelGGL(tb_qa_count, dim3((unsigned)nb), dim3(QUERY_THREADS), 0, E->stream, E->T, P, cap, A.d_counts, A.d_mins,
+                       A.d_maxs);
+    hipLaunchKernelGGL(tb_qa_scan, dim3(1), dim3(1024), 0, E->stream, A.d_counts, A.d_mins, A.d_maxs, nb, k, A.d_state);
+    for (u32 pass = 0; pass < QA_PASSES; pass++) {
+        hipLaunchKernelGGL(tb_qa_hist, dim3(wide), dim3(QUERY_THREADS), 0, E->stream, E->T, P, cap, A.d_counts, nb, k, rev, pass,
+                           A.d_state, hist);
+        hipLaunchKernelGGL(tb_qa_pick, dim3(1), dim3(1024), 0, E->stream, k, pass, hist, A.d_state);
+    }
+    hipLaunchKernelGGL(tb_qa_collect, dim3(wide), dim3(QUERY_THREADS), 0, E->stream, E->T, P, cap, A.d_counts, nb, k, rev,
+                       A.d_state, A.d_keys);
+    hipLaunchKernelGGL(tb_qa_emit, dim3(std::max<u32>(1, (k + QA_EMIT_KEYS - 1) / QA_EMIT_KEYS)), dim3(QUERY_THREADS), 0,
+                       E->stream, E->T, cap, k, A.d_state, A.d_keys, A.d_out);
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpyAsync(A.h_state, A.d_state, (u64)QA_WORDS * 8, hipMemcpyDeviceToHost, E->stream));
+    return TBGPU_STATUS_OK;
+}
+
+static int account_query_collect(tbgpu* E, u8* out, u32* count, u64* matched) {
+    AccountQueryBufs& A = E->qs->qa;
+    *count = 0;
+    *matched = 0;
+    HIPCK(hipSetDevice(E->device));
+    HIPCK(hipStreamSynchronize(E->stream));
+    const u64 total = A.h_state[QA_TOTAL];
+    const u32 m = (u32)std::min<u64>(A.k, total);
+    A.last_scans = A.h_state[QA_SCANS];
+    *matched = total;
+    if (m == 0) return TBGPU_STATUS_OK;
+    if (std::min<u64>(A.k, A.h_state[QA_NKEYS]) != m) {
+        return fail(TBGPU_STATUS_PANIC, "query_accounts: %llu keys selected for %u of %llu matches",
+                    (unsigned long long)A.h_state[QA_NKEYS], m, (unsigned long long)total);
+    }
+    HIPCK(hipMemcpyAsync(out, A.d_out, (u64)m * 128, hipMemcpyDeviceToHost, E->stream));
+    HIPCK(hipStreamSynchronize(E->stream));
+    *count = m;
+    return TBGPU_STATUS_OK;
+}
+
+// A node's shard d answers for the accounts with tb_home(id, world) == d — a home's imported copies of
+// foreign accounts do not match; the one engine owns every account and makes no owner test (world 0).
+extern "C" int tbgpu_query_accounts(tbgpu_t* E, const tbgpu_query_filter* filter, void* out, uint32_t out_cap_records,
+                                    tbgpu_query_result* result) {
+    QueryCall c;
+    if (const int st = query_begin(E, "query_accounts", filter, out, out_cap_records, BATCH_EVENTS_MAX, false, result, &c)) return st;
+    if (!query_fields_valid(filter)) return TBGPU_STATUS_OK;
+    const QueryFieldFilter F = query_fields_of(filter);
+    const bool reversed = (filter->flags & TBGPU_QUERY_REVERSED) != 0;
+    for (u32 d = 0; d < c.world; d++) {
+        const int st = account_query_enqueue(c.Es[d], F, c.world > 1 ? c.world : 0, d, c.k, reversed);
+        if (st) return st;
+    }
+    return query_end(result, query_collect_all(c, reversed, (u8*)out, result, account_query_collect));
+}
+
+extern "C" int tbgpu_bench_query_select_scans(tbgpu_t* E, uint64_t* scans) {
+    API_ENTER(E, false);
+    if (E->node) E = node_engine(E->node, 0);
+    *scans = E->qs->qa.last_scans;
+    return TBGPU_STATUS_OK;
+}
+
+extern "C" int tbgpu_bench_query_keys_max(tbgpu_t* E, uint32_t keys) {
+    API_ENTER(E, false);
+    if (E->node) {
+        for (u32 d = 0; d < node_world(E->node); d++) tbgpu_bench_query_keys_max(node_engine(E->node, d), keys);
+        return TBGPU_STATUS_OK;
+    }
+    E->qs->q.keys_max = keys ? std::min<u32>(std::max<u32>(keys, QUERY_THREADS), QUERY_KEYS_CAP) : QUERY_KEYS_CAP;
+    return TBGPU_STATUS_OK;
+}
+
+// ---- get_change_events (k_change_events.h, include/tbgpu.h) ---------------------------------------
+// The rows are query_transfers' answer for an all-zero field filter.  change_events_finish takes them
+// (m > 0, ascending by timestamp, on the host) with the engines whose logs hold the ledger — one, or a
+// node's shards — and writes the m events into `out`:
+//   the set      the rows' distinct accounts, an index each, in an open-addressing table the host
+//                builds in Es[0]'s pinned buffers (a node copies it into every shard's);
+//   the scans    every engine, on its own device and stream, side by side: set and ids up, bins zeroed,
+//                tb_change_effects over its own log for the records above the last row, bins back;
+//   the gather   Es[0]'s stream: each account's record from its owner, each post row's pending amount
+//                from home(pending_id), through the peers' tables as tb_balance_effects reads them;
+//   the walk     end(a) = current(a) - the engines' bins; the rows from the newest to the oldest, each
+//                written with its two accounts' balances and then taken out of them.
+static u32 change_set_insert(u32* set, u32 mask, u64* ids, u32* count, u64 lo, u64 hi) {
+    const u64 h = tb_change_hash(lo, hi);
+    const u32 tag = (u32)(h >> 48);
+    u32 s = (u32)h & mask;
+    for (;;) {  // the table is at most half full: an empty slot ends the probe
+        const u32 e = set[s];
+        if (e == 0) break;
+        if ((e >> 16) == tag) {
+            const u32 index = (e & 0xFFFFu) - 1;
+            if (ids[2 * (u64)index] == lo && ids[2 * (u64)index + 1] == hi) return index;
+        }
+        s = (s + 1) & mask;
+    }
+    const u32 index = (*count)++;
+    ids[2 * (u64)index] = lo, ids[2 * (u64)index + 1] = hi;
+    set[s] = tb_change_entry(h, index);
+    return index;
+}
+
+static u64 change_row_word(const u8* row, u32 word) {
+    u64 v;
+    memcpy(&v, row + 8 * word, 8);
+    return v;
+}
+
+// The walk.  rows: m records, ascending; row_idx: [m][2] their debit and credit account's index;
+// accounts, found: the indexed accounts' records and whether their owner holds them; p, found_p: the
+// post rows' pending amounts and whether they were resident; bal: [accounts][4] the balances after the
+// newest row, taken apart row by row.  Writes the m events of 384 B; false: an orphan post among the rows.
+static bool change_walk(const u8* rows, u32 m, const u32* row_idx, const u8* accounts, const u32* found, const u64* p,
+                        const u32* found_p, u128* bal, u8* out) {
+    bool complete = true;
+    for (u32 i = m; i-- > 0;) {
+        const u8* r = rows + (u64)i * 128;
+        u8* ev = out + (u64)i * 384;
+        memcpy(ev, r, 128);
+        for (u32 side = 0; side < 2; side++) {
+            const u32 a = row_idx[2 * i + side];
+            u8* block = ev + 128 + 128 * side;
+            if (!found[a]) {
+                memset(block, 0, 128);
+                continue;
+            }
+            memcpy(block, accounts + (u64)a * 128, 128);
+            memcpy(block + 16, &bal[(u64)a * 4], 64);
+        }
+        // The row's own effect leaves its two accounts: the balances of the next older row.
+        const u128 amount = tb_u128(change_row_word(r, 6), change_row_word(r, 7));
+        const u32 tf = (u32)(change_row_word(r, 14) >> 48);
+        u128 pending = amount;
+        if (tb_effect_is_post(tf)) {
+            if (found_p[i]) pending = tb_u128(p[2 * (u64)i], p[2 * (u64)i + 1]);
+            else complete = false;
+        }
+        const BalanceEffect e = tb_balance_effect(tf, amount, pending);
+        for (u32 side = 0; side < 2; side++) {
+            u128* b = &bal[(u64)row_idx[2 * i + side] * 4 + 2 * side];
+            b[0] -= e.pend, b[1] -= e.post;
+        }
+    }
+    return complete;
+}
+
+static int change_events_finish(tbgpu* const* Es, u32 world, const u8* rows, u32 m, u8* out, tbgpu_query_result* result) {
+    ChangeBufs& C = Es[0]->qs->qc;
+    u32 slots = tb_change_set_slots(2 * m), mask = slots - 1;  // for now: the accounts are at most 2m
+    memset(C.h_set, 0, (u64)slots * 4);
+    u32 na = 0;
+    for (u32 i = 0; i < m; i++) {
+        const u8* r = rows + (u64)i * 128;
+        for (u32 side = 0; side < 2; side++) {
+            C.h_row_idx[2 * i + side] =
+                change_set_insert(C.h_set, mask, C.h_ids, &na, change_row_word(r, 2 + 2 * side), change_row_word(r, 3 + 2 * side));
+        }
+        const bool post = tb_effect_is_post((u32)(change_row_word(r, 14) >> 48));
+        C.h_pids[2 * (u64)i] = post ? change_row_word(r, 8) : 0;
+        C.h_pids[2 * (u64)i + 1] = post ? change_row_word(r, 9) : 0;
+    }
+    if (tb_change_set_slots(na) < slots) {  // fewer distinct accounts: the smaller table, the same indices
+        slots = tb_change_set_slots(na), mask = slots - 1;
+        memset(C.h_set, 0, (u64)slots * 4);
+        u32 again = 0;
+        for (u32 a = 0; a < na; a++) change_set_insert(C.h_set, mask, C.h_ids, &again, C.h_ids[2 * (u64)a], C.h_ids[2 * (u64)a + 1]);
+    }
+    const u32 lds_bins = tb_change_lds_bins(slots);
+    const u64 t_last = change_row_word(rows + (u64)(m - 1) * 128, 15);
+    const u64 bin_bytes = ((u64)na + 1) * BALANCE_SLOT_WORDS * 8;
+    NodeTablesArgs NT{};
+    NT.world = world;
+    for (u32 d = 0; d < world; d++) NT.T[d] = Es[d]->T;
+    const int status = query_side_by_side(Es, world, [&](u32 d) -> int {
+        tbgpu* E = Es[d];
+        ChangeBufs& D = E->qs->qc;
+        HIPCK(hipSetDevice(E->device));
+        if (d) {
+            memcpy(D.h_set, C.h_set, (u64)slots * 4);
+            memcpy(D.h_ids, C.h_ids, (u64)na * 16);
+        }
+        HIPCK(hipMemcpyAsync(D.d_set, D.h_set, (u64)slots * 4, hipMemcpyHostToDevice, E->stream));
+        HIPCK(hipMemcpyAsync(D.d_ids, D.h_ids, (u64)na * 16, hipMemcpyHostToDevice, E->stream));
+        HIPCK(hipMemsetAsync(D.d_bins, 0, bin_bytes, E->stream));
+        const u64 n = E->log_next, per = (u64)CHANGE_THREADS * CHANGE_TILES, nb = (n + per - 1) / per;
+        if (nb) {
+            hipLaunchKernelGGL(tb_change_effects, dim3((unsigned)nb), dim3(CHANGE_THREADS),
+                               (size_t)slots * 4 + (size_t)lds_bins * BALANCE_SLOT_WORDS * 8, E->stream, NT, d, n, t_last,
+                               (const u32*)D.d_set, mask, (const u64*)D.d_ids, na, D.d_bins, lds_bins);
+            HIPCK(hipGetLastError());
+        }
+        HIPCK(hipMemcpyAsync(D.h_bins, D.d_bins, bin_bytes, hipMemcpyDeviceToHost, E->stream));
+        if (d == 0) {
+            HIPCK(hipMemcpyAsync(D.d_pids, D.h_pids, (u64)m * 16, hipMemcpyHostToDevice, E->stream));
+            hipLaunchKernelGGL(tb_change_gather, dim3((std::max(na, m) + QUERY_THREADS - 1) / QUERY_THREADS), dim3(QUERY_THREADS), 0,
+                               E->stream, NT, (const u64*)D.d_ids, na, D.d_accounts, D.d_found, (const u64*)D.d_pids, m, D.d_p,
+                               D.d_found_p);
+            HIPCK(hipGetLastError());
+            HIPCK(hipMemcpyAsync(D.h_accounts, D.d_accounts, (u64)na * 128, hipMemcpyDeviceToHost, E->stream));
+            HIPCK(hipMemcpyAsync(D.h_found, D.d_found, (u64)na * 4, hipMemcpyDeviceToHost, E->stream));
+            HIPCK(hipMemcpyAsync(D.h_p, D.d_p, (u64)m * 16, hipMemcpyDeviceToHost, E->stream));
+            HIPCK(hipMemcpyAsync(D.h_found_p, D.d_found_p, (u64)m * 4, hipMemcpyDeviceToHost, E->stream));
+        }
+        return TBGPU_STATUS_OK;
+    });
+    if (status) return status;
+    bool complete = result->complete != 0;
+    // end(a): into Es[0]'s bins in place, as u128s (a slot is 4 x {lo, hi}, little-endian).
+    u128* bal = (u128*)C.h_bins;
+    for (u32 d = 0; d < world; d++) complete &= Es[d]->qs->qc.h_bins[(u64)na * BALANCE_SLOT_WORDS + CHANGE_FLAG_ORPHAN] == 0;
+    for (u32 a = 0; a < na; a++) {
+        const u8* rec = C.h_accounts + (u64)a * 128;
+        for (u32 c = 0; c < 4; c++) {
+            u128 sum = bal[(u64)a * 4 + c];
+            for (u32 d = 1; d < world; d++) sum += ((const u128*)Es[d]->qs->qc.h_bins)[(u64)a * 4 + c];
+            const u128 cur = C.h_found[a] ? tb_u128(change_row_word(rec, 2 + 2 * c), change_row_word(rec, 3 + 2 * c)) : (u128)0;
+            bal[(u64)a * 4 + c] = cur - sum;
+        }
+        complete &= C.h_found[a] != 0;
+    }
+    complete &= change_walk(rows, m, C.h_row_idx, C.h_accounts, C.h_found, C.h_p, C.h_found_p, bal, out);
+    result->complete = complete ? 1 : 0;
+    result->count = m;
+    return TBGPU_STATUS_OK;
+}
+
+static bool change_filter_valid(const tbgpu_change_events_filter* f) {
+    if (f->timestamp_min == ~0ULL || f->timestamp_max == ~0ULL) return false;
+    if (f->timestamp_max != 0 && f->timestamp_max < f->timestamp_min) return false;
+    if (f->limit == 0) return false;
+    for (u8 b : f->reserved) if (b) return false;
+    return true;
+}
+
+// The rows go to Es[0]'s pinned h_rows: one engine's answer as it is, a node's merged.
+extern "C" int tbgpu_get_change_events(tbgpu_t* E, const tbgpu_change_events_filter* filter, void* out,
+                                       uint32_t out_cap_events, tbgpu_query_result* result) {
+    QueryCall c;
+    if (const int st = query_begin(E, "get_change_events", filter, out, out_cap_events, CHANGE_EVENTS_MAX, true, result, &c)) return st;
+    if (!change_filter_valid(filter)) return TBGPU_STATUS_OK;
+    QueryFieldFilter F{};
+    F.ts_min = filter->timestamp_min;
+    F.ts_max = filter->timestamp_max ? filter->timestamp_max : ~0ULL;
+    u8* rows = c.Es[0]->qs->qc.h_rows;
+    int st = query_log_rows(c, F, false, rows, result);
+    const u32 m = result->count;
+    result->count = 0;
+    if (st == TBGPU_STATUS_OK && m) st = change_events_finish(c.Es, c.world, rows, m, (u8*)out, result);
+    return query_end(result, st);
+}
