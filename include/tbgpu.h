@@ -325,6 +325,34 @@ typedef struct tbgpu_query_result {
 int tbgpu_get_account_transfers(tbgpu_t* engine, const tbgpu_account_filter* filter,
                                 void* out, uint32_t out_cap_records, tbgpu_query_result* result);
 
+/* get_account_transfers_many: up to TBGPU_QUERY_FILTERS_MAX account filters answered by one read of the
+ * transfer log instead of one read each (a replica serving several get_account_transfers requests
+ * between two writes hands them over together).  This sentence is its specification:
+ *   Answer i is exactly what tbgpu_get_account_transfers(engine, &filters[i],
+ *     (uint8_t*)out + i * out_cap_records * 128, out_cap_records, &results[i]) would have produced at the
+ *     same point: the records, their order, count, matched and complete are all the same.
+ *   So out has room for n_filters * out_cap_records records, answer i starts at record i *
+ *     out_cap_records and holds min(limit_i, out_cap_records, TBGPU_BATCH_EVENTS_MAX) records at most;
+ *     bytes of a slot past its count are not written.  REVERSED, DEBITS / CREDITS and the window apply
+ *     per filter; filters may name the same account, be identical, or mix directions.  An invalid
+ *     filter (the rules above) yields count = matched = 0 for its entry only, never a status; the other
+ *     filters are answered.  complete is the same for every entry.
+ *   n_filters == 0 returns TBGPU_STATUS_OK and writes nothing.  n_filters > TBGPU_QUERY_FILTERS_MAX is
+ *     TBGPU_STATUS_INVALID and writes nothing; so is a NULL filters, out or results with n_filters > 0.
+ *     After any failing status no result names a record.
+ *   The call contract of tbgpu_get_account_transfers: synchronous, drains a pending
+ *     tbgpu_commit_device_async first, a read that changes nothing, works on a stopped engine,
+ *     allocates nothing after tbgpu_init, and is legal beside an asynchronous write-back.
+ *   A node engine: every home shard scans its own log once for the whole batch, side by side, and the
+ *     host merges per filter.
+ *   Cost: one scan of the log for the batch, plus one more read of the chunks that hold a wanted
+ *     record.  A log out of timestamp order (loads, upserts) is answered filter by filter, as
+ *     n_filters single calls would. */
+#define TBGPU_QUERY_FILTERS_MAX 64u
+int tbgpu_get_account_transfers_many(tbgpu_t* engine, const tbgpu_account_filter* filters, uint32_t n_filters,
+                                     void* out, uint32_t out_cap_records /* per filter */,
+                                     tbgpu_query_result* results /* [n_filters] */);
+
 /* get_account_balances: an account's four balances as they stood right after each of its transfers.
  * Later references answer it from balance rows they store at every commit for accounts that opted in
  * with a `history` flag.  This engine stores nothing and asks for no flag: the transfer log is in HBM

@@ -69,6 +69,12 @@ int tbgpu_bench_flow_launch(tbgpu_t* engine, uint32_t workgroups);
  * Exact either way. */
 int tbgpu_bench_query_keys_max(tbgpu_t* engine, uint32_t keys);
 
+/* tbgpu_get_account_transfers_many gives each workgroup a chunk of consecutive 256-position tiles of
+ * the log: use chunks of this many tiles (clamped to [1, 64] and to what keeps the chunks within the
+ * buffers made at init, which hold 4096 chunks at least; 0: the default, 64), so a small test log
+ * spans many chunks.  Exact either way. */
+int tbgpu_bench_query_many_tiles(tbgpu_t* engine, uint32_t tiles);
+
 /* Table scans the radix select of the last tbgpu_query_accounts made (0: at most `limit` matches, or
  * one timestamp); on a node engine, its first shard's.  For tools/gpu/query_scan.py. */
 int tbgpu_bench_query_select_scans(tbgpu_t* engine, uint64_t* scans);

@@ -33,6 +33,7 @@
 #include "k_workload.h"
 #include "k_evict.h"
 #include "k_query.h"
+#include "k_query_many.h"
 #include "k_query_filter.h"
 #include "k_balances.h"
 #include "k_change_events.h"

@@ -1,6 +1,6 @@
-// query.h — the host side of the queries (include/tbgpu.h): get_account_transfers, get_account_balances,
-// query_transfers, query_accounts and get_change_events; their buffers, made at tbgpu_init, and their
-// entry points.  Included by engine.hip after the engine's own helpers and before node.h.
+// query.h — the host side of the queries (include/tbgpu.h): get_account_transfers and its batched form
+// get_account_transfers_many, get_account_balances, query_transfers, query_accounts and
+// get_change_events; their buffers, made at tbgpu_init, and their entry points.  Included by engine.hip after the engine's own helpers and before node.h.
 //
 // Every query is written once, over a list of engines (QueryCall): the one engine, or a node's shards.
 // A transfer lives on its home shard only and an account is answered by its owner only, so every
@@ -87,12 +87,36 @@ struct ChangeBufs {
     u32* h_row_idx = nullptr; // host [CHANGE_EVENTS_MAX][2] the rows' debit and credit account index
 };
 
+// tbgpu_get_account_transfers_many (k_query_many.h): the filter set, per-chunk counts, bases and bounds,
+// the totals and the answer area; made at tbgpu_init after every other buffer and shared with nothing.
+// Every word a query reads is a word it wrote, so tbgpu_reset clears none of them.
+#define QUERY_MANY_CHUNKS_MIN 4096u  // room for this many chunks whatever the log: a test's shrunk chunks
+#define QUERY_MANY_STAGE (1u << 15)  // records of one copy to the host (4 MiB)
+struct QueryManyBufs {
+    u64 nc_cap = 0;                  // chunks the per-chunk buffers hold
+    u32 tiles = QUERY_MANY_TILES;    // tiles of a chunk (tbgpu_bench_query_many_tiles)
+    QueryManyTable* d_tab = nullptr; // the filter set
+    QueryManyTable* h_tab = nullptr; // pinned: the host builds it here
+    u32* d_counts = nullptr;         // [nc_cap][64] matches per chunk and filter
+    u32* d_base = nullptr;           // [nc_cap][64] their exclusive prefix per filter
+    u64* d_cmin = nullptr;           // [nc_cap] the smallest timestamp of a chunk's hits
+    u64* d_cmax = nullptr;           // [nc_cap] ... and the largest (0: no hit)
+    u32* d_cord = nullptr;           // [nc_cap] 1: the chunk's hits rise with position
+    u64* d_ctiles = nullptr;         // [nc_cap] the chunk's tiles that hold a hit
+    u64* d_res = nullptr;            // [QM_RES_WORDS] totals, `ordered`, where each answer starts in d_out, their sum
+    u64* h_res = nullptr;            // pinned mirror
+    u8* d_out = nullptr;             // [64 x BATCH_EVENTS_MAX] the answers' records, packed
+    u8* h_stage = nullptr;           // pinned [QUERY_MANY_STAGE]: the records on their way to the caller's slots
+    u64 n = 0;                       // one batch in flight between query_many_enqueue and _collect
+};
+
 // One engine's query buffers (tbgpu::qs), in the order query_init makes them.
 struct QueryState {
     QueryBufs q;
     BalanceBufs qb;
     AccountQueryBufs qa;
     ChangeBufs qc;
+    QueryManyBufs qm;
 };
 
 // Called by tbgpu_init on the engine's device, after every other buffer; tbgpu_deinit calls query_free
@@ -160,6 +184,23 @@ static int query_init(tbgpu* E) {
         QINIT_CK(tbHostMalloc(&C.h_rows, nr * 128, hipHostMallocDefault));
         QINIT_CK(tbHostMalloc(&C.h_row_idx, nr * 8, hipHostMallocDefault));
     }
+    {  // tbgpu_get_account_transfers_many: the set, per-chunk counts, bases and bounds, the totals, the answers
+        QueryManyBufs& M = E->qs->qm;
+        const u64 nb_cap = E->qs->q.nb_cap;
+        M.nc_cap = std::max<u64>((nb_cap + QUERY_MANY_TILES - 1) / QUERY_MANY_TILES, std::min<u64>(nb_cap, QUERY_MANY_CHUNKS_MIN));
+        QINIT_CK(tbMalloc(&M.d_tab, sizeof(QueryManyTable)));
+        QINIT_CK(tbHostMalloc(&M.h_tab, sizeof(QueryManyTable), hipHostMallocDefault));
+        QINIT_CK(tbMalloc(&M.d_counts, M.nc_cap * QUERY_MANY_FILTERS * 4));
+        QINIT_CK(tbMalloc(&M.d_base, M.nc_cap * QUERY_MANY_FILTERS * 4));
+        QINIT_CK(tbMalloc(&M.d_cmin, M.nc_cap * 8));
+        QINIT_CK(tbMalloc(&M.d_cmax, M.nc_cap * 8));
+        QINIT_CK(tbMalloc(&M.d_cord, M.nc_cap * 4));
+        QINIT_CK(tbMalloc(&M.d_ctiles, M.nc_cap * 8));
+        QINIT_CK(tbMalloc(&M.d_res, QM_RES_WORDS * 8));
+        QINIT_CK(tbHostMalloc(&M.h_res, QM_RES_WORDS * 8, hipHostMallocDefault));
+        QINIT_CK(tbHostMalloc(&M.h_stage, (u64)QUERY_MANY_STAGE * 128, hipHostMallocDefault));
+        QINIT_CK(tbMalloc(&M.d_out, (u64)QUERY_MANY_FILTERS * BATCH_EVENTS_MAX * 128));
+    }
 #undef QINIT_CK
     return TBGPU_STATUS_OK;
 }
@@ -170,6 +211,14 @@ static void query_free(tbgpu* E) {
     const BalanceBufs& B = E->qs->qb;
     const AccountQueryBufs& A = E->qs->qa;
     const ChangeBufs& C = E->qs->qc;
+    const QueryManyBufs& M = E->qs->qm;
+    for (void* p : {(void*)M.d_tab, (void*)M.d_counts, (void*)M.d_base, (void*)M.d_cmin, (void*)M.d_cmax, (void*)M.d_cord,
+                    (void*)M.d_ctiles, (void*)M.d_res, (void*)M.d_out}) {
+        if (p) (void)hipFree(p);
+    }
+    for (void* p : {(void*)M.h_tab, (void*)M.h_res, (void*)M.h_stage}) {
+        if (p) (void)hipHostFree(p);
+    }
     for (void* p : {(void*)Q.d_counts, (void*)Q.d_mins, (void*)Q.d_maxs, (void*)Q.d_ordered, (void*)Q.d_base, (void*)Q.d_res,
                     (void*)Q.d_out, (void*)Q.d_keys, (void*)B.d_ts, (void*)B.d_bins, (void*)A.d_counts, (void*)A.d_mins,
                     (void*)A.d_maxs, (void*)A.d_state, (void*)A.d_keys, (void*)A.d_out, (void*)C.d_set, (void*)C.d_ids,
@@ -422,6 +471,204 @@ extern "C" int tbgpu_get_account_transfers(tbgpu_t* E, const tbgpu_account_filte
     if (!query_filter_valid(filter)) return TBGPU_STATUS_OK;
     const bool reversed = (filter->flags & TBGPU_FILTER_REVERSED) != 0;
     return query_end(result, query_log_rows(c, query_account_filter_of(filter), reversed, (u8*)out, result));
+}
+
+// ---- get_account_transfers_many (k_query_many.h, include/tbgpu.h) ----------------------------------
+// A batch of account filters over one read of every listed engine's log.  The host builds the filter
+// set once; query_many_enqueue puts the set's copy and count -> scan -> scatter on the engine stream
+// and query_many_collect waits and copies each filter's records, as query_enqueue / query_collect do
+// for one.  When the union of the hits is out of timestamp order (loads, upserts) the totals stand and
+// each filter with a match is answered through query_enqueue / query_collect, which has the exact
+// keyed rounds: rare, exact, and in the single query's buffers.
+struct QueryManyCall {
+    u32 nf = 0;
+    const tbgpu_account_filter* filters = nullptr;
+    bool valid[QUERY_MANY_FILTERS];
+    u32 k[QUERY_MANY_FILTERS];  // records asked for: the limit under the caller's room and one message body
+};
+
+// The set of the call's valid filters: invalid ones are in no mask and match nothing.
+static void query_many_table(const QueryManyCall& M, QueryManyTable* tab) {
+    memset(tab, 0, sizeof *tab);
+    for (u32 i = 0; i < M.nf; i++) {
+        if (!M.valid[i]) continue;
+        const QueryFilter F = query_account_filter_of(&M.filters[i]);
+        u32 h = tb_qm_slot(F.id_lo, F.id_hi);  // at most 64 ids in 128 slots: an empty slot ends the probe
+        while ((tab->id[h].x | tab->id[h].y) != 0 && !(tab->id[h].x == F.id_lo && tab->id[h].y == F.id_hi)) {
+            h = (h + 1) & (QUERY_MANY_SLOTS - 1);
+        }
+        tab->id[h].x = F.id_lo, tab->id[h].y = F.id_hi;
+        tab->mask[h] |= 1ULL << i;
+        tab->ts_min[i] = F.ts_min, tab->ts_max[i] = F.ts_max;
+        tab->k[i] = M.k[i];
+        if (F.debits) tab->debits |= 1ULL << i;
+        if (F.credits) tab->credits |= 1ULL << i;
+        if (M.filters[i].flags & TBGPU_FILTER_REVERSED) tab->reversed |= 1ULL << i;
+        if (F.ts_min != 0 || F.ts_max != ~0ULL) tab->windows = 1;
+    }
+}
+
+// The set is in E's pinned h_tab.
+static int query_many_enqueue(tbgpu* E) {
+    QueryManyBufs& M = E->qs->qm;
+    HIPCK(hipSetDevice(E->device));
+    if (E->pending) {
+        int st = engine_sync(E);
+        if (st) return st;
+    }
+    M.n = E->log_next;
+    for (u32 i = 0; i < QM_RES_WORDS; i++) M.h_res[i] = 0;
+    const u64 nb = (M.n + QUERY_THREADS - 1) / QUERY_THREADS, nc = (nb + M.tiles - 1) / M.tiles;
+    if (nc == 0) return TBGPU_STATUS_OK;
+    if (nc > M.nc_cap) return fail(TBGPU_STATUS_PANIC, "query: the log's end %llu is past its capacity", (unsigned long long)M.n);
+    HIPCK(hipMemcpyAsync(M.d_tab, M.h_tab, sizeof(QueryManyTable), hipMemcpyHostToDevice, E->stream));
+    hipLaunchKernelGGL(tb_qm_count, dim3((unsigned)nc), dim3(QUERY_THREADS), 0, E->stream, E->T, (const QueryManyTable*)M.d_tab,
+                       M.n, M.tiles, M.d_counts, M.d_cmin, M.d_cmax, M.d_cord, M.d_ctiles);
+    hipLaunchKernelGGL(tb_qm_scan, dim3(1), dim3(1024), 0, E->stream, (const QueryManyTable*)M.d_tab, M.d_counts, M.d_cmin,
+                       M.d_cmax, M.d_cord, nc, M.d_base, M.d_res);
+    hipLaunchKernelGGL(tb_qm_scatter, dim3((unsigned)nc), dim3(QUERY_THREADS), 0, E->stream, E->T, (const QueryManyTable*)M.d_tab,
+                       M.n, M.tiles, M.d_counts, M.d_base, M.d_ctiles, M.d_res, M.d_out);
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpyAsync(M.h_res, M.d_res, QM_RES_WORDS * 8, hipMemcpyDeviceToHost, E->stream));
+    return TBGPU_STATUS_OK;
+}
+
+// Filter i's records go to out + off[i] (room for its k records); count[i] = records written,
+// matched[i] = every match.
+static int query_many_collect(tbgpu* E, const QueryManyCall& C, u8* out, const u64* off, u32* count, u64* matched) {
+    QueryManyBufs& M = E->qs->qm;
+    for (u32 i = 0; i < C.nf; i++) count[i] = 0, matched[i] = 0;
+    HIPCK(hipSetDevice(E->device));
+    HIPCK(hipStreamSynchronize(E->stream));
+    if (M.n == 0) return TBGPU_STATUS_OK;
+    const bool ordered = M.h_res[QM_RES_ORDERED] != 0;
+    u64 totals[QUERY_MANY_FILTERS];
+    for (u32 i = 0; i < C.nf; i++) totals[i] = C.valid[i] ? M.h_res[i] : 0;
+    if (!ordered) {
+        for (u32 i = 0; i < C.nf; i++) {
+            if (totals[i] == 0) continue;
+            const bool reversed = (C.filters[i].flags & TBGPU_FILTER_REVERSED) != 0;
+            int st = query_enqueue(E, query_account_filter_of(&C.filters[i]), C.k[i], reversed);
+            if (st == TBGPU_STATUS_OK) st = query_collect(E, out + off[i], &count[i], &matched[i]);
+            if (st) return st;
+            if (matched[i] != totals[i]) {
+                return fail(TBGPU_STATUS_PANIC, "query: filter %u matched %llu records, then %llu", i,
+                            (unsigned long long)totals[i], (unsigned long long)matched[i]);
+            }
+        }
+        return TBGPU_STATUS_OK;
+    }
+    // The answers lie packed on the device: a copy per QUERY_MANY_STAGE records into the pinned stage,
+    // and from there each filter's part into its slot.
+    u64 start[QUERY_MANY_FILTERS + 1];
+    start[0] = 0;
+    for (u32 i = 0; i < C.nf; i++) {
+        count[i] = (u32)std::min<u64>(C.k[i], totals[i]);
+        matched[i] = totals[i];
+        start[i + 1] = start[i] + count[i];
+        if (count[i] && M.h_res[QM_RES_START + i] != start[i]) {
+            return fail(TBGPU_STATUS_PANIC, "query: filter %u's records start at %llu, not %llu", i,
+                        (unsigned long long)M.h_res[QM_RES_START + i], (unsigned long long)start[i]);
+        }
+    }
+    const u64 all = start[C.nf];
+    for (u64 p0 = 0; p0 < all; p0 += QUERY_MANY_STAGE) {
+        const u64 p1 = std::min<u64>(all, p0 + QUERY_MANY_STAGE);
+        HIPCK(hipMemcpyAsync(M.h_stage, M.d_out + p0 * 128, (p1 - p0) * 128, hipMemcpyDeviceToHost, E->stream));
+        HIPCK(hipStreamSynchronize(E->stream));
+        for (u32 i = 0; i < C.nf; i++) {
+            const u64 a = std::max(p0, start[i]), b = std::min(p1, start[i + 1]);
+            if (a < b) memcpy(out + off[i] + (a - start[i]) * 128, M.h_stage + (a - p0) * 128, (b - a) * 128);
+        }
+    }
+    return TBGPU_STATUS_OK;
+}
+
+// Every listed engine scans its own log for the whole batch, side by side; one engine's answers go
+// straight into the caller's buffer, a node's are merged per filter.  Every engine is waited for,
+// whatever an earlier one returned.
+static int query_many_rows(const QueryCall& c, const QueryManyCall& C, u8* out, u64 out_stride, tbgpu_query_result* results) {
+    QueryManyTable* tab = c.Es[0]->qs->qm.h_tab;
+    query_many_table(C, tab);
+    for (u32 d = 0; d < c.world; d++) {
+        if (d) memcpy(c.Es[d]->qs->qm.h_tab, tab, sizeof *tab);
+        const int st = query_many_enqueue(c.Es[d]);
+        if (st) return st;
+    }
+    u64 off[QUERY_MANY_FILTERS];
+    u32 cnt[NODE_WORLD_MAX][QUERY_MANY_FILTERS];
+    u64 matched[QUERY_MANY_FILTERS];
+    if (c.world == 1) {
+        for (u32 i = 0; i < C.nf; i++) off[i] = i * out_stride;
+        const int st = query_many_collect(c.Es[0], C, out, off, cnt[0], matched);
+        if (st) return st;
+        for (u32 i = 0; i < C.nf; i++) results[i].count = cnt[0][i], results[i].matched = matched[i];
+        return TBGPU_STATUS_OK;
+    }
+    u64 per = 0;  // one engine's answers: filter i's room of k records at off[i]
+    for (u32 i = 0; i < C.nf; i++) off[i] = per, per += (u64)std::max<u32>(C.k[i], 1) * 128;
+    std::vector<u8> recs(c.world * per);
+    u64 sums[QUERY_MANY_FILTERS] = {};
+    int status = TBGPU_STATUS_OK;
+    for (u32 d = 0; d < c.world; d++) {
+        const int st = query_many_collect(c.Es[d], C, recs.data() + d * per, off, cnt[d], matched);
+        if (st && status == TBGPU_STATUS_OK) status = st;
+        for (u32 i = 0; i < C.nf; i++) sums[i] += matched[i];
+    }
+    if (status) return status;
+    for (u32 i = 0; i < C.nf; i++) {
+        u32 ci[NODE_WORLD_MAX];
+        for (u32 d = 0; d < c.world; d++) ci[d] = cnt[d][i];
+        const bool reversed = (C.filters[i].flags & TBGPU_FILTER_REVERSED) != 0;
+        results[i].count = query_merge(recs.data() + off[i], per, ci, c.world, C.k[i], reversed, out + i * out_stride);
+        results[i].matched = sums[i];
+    }
+    return TBGPU_STATUS_OK;
+}
+
+extern "C" int tbgpu_get_account_transfers_many(tbgpu_t* E, const tbgpu_account_filter* filters, uint32_t n_filters, void* out,
+                                                uint32_t out_cap_records, tbgpu_query_result* results) {
+    API_ENTER(E, false);
+    if (n_filters > TBGPU_QUERY_FILTERS_MAX) {
+        return fail(TBGPU_STATUS_INVALID, "get_account_transfers_many: %u filters (at most %u)", n_filters, TBGPU_QUERY_FILTERS_MAX);
+    }
+    if (n_filters == 0) return TBGPU_STATUS_OK;
+    if (!filters || !out || !results) return fail(TBGPU_STATUS_INVALID, "get_account_transfers_many: NULL filters, out or results");
+    QueryCall c;
+    c.world = E->node ? node_world(E->node) : 1;
+    u32 complete = 1;
+    for (u32 d = 0; d < c.world; d++) {
+        c.Es[d] = E->node ? node_engine(E->node, d) : E;
+        if (c.Es[d]->evicted_total) complete = 0;
+    }
+    QueryManyCall C;
+    C.nf = n_filters;
+    C.filters = filters;
+    bool any = false;
+    for (u32 i = 0; i < n_filters; i++) {
+        results[i].count = 0, results[i].matched = 0, results[i].complete = complete;
+        C.valid[i] = query_filter_valid(&filters[i]);
+        C.k[i] = C.valid[i] ? std::min<u32>(std::min<u32>(filters[i].limit, out_cap_records), BATCH_EVENTS_MAX) : 0;
+        any |= C.valid[i];
+    }
+    if (!any) return TBGPU_STATUS_OK;
+    const int st = query_many_rows(c, C, (u8*)out, (u64)out_cap_records * 128, results);
+    if (st) {
+        for (u32 i = 0; i < n_filters; i++) results[i].count = 0, results[i].matched = 0;
+    }
+    return st;
+}
+
+extern "C" int tbgpu_bench_query_many_tiles(tbgpu_t* E, uint32_t tiles) {
+    API_ENTER(E, false);
+    if (E->node) {
+        for (u32 d = 0; d < node_world(E->node); d++) tbgpu_bench_query_many_tiles(node_engine(E->node, d), tiles);
+        return TBGPU_STATUS_OK;
+    }
+    QueryManyBufs& M = E->qs->qm;
+    M.tiles = tiles ? std::min<u32>(tiles, QUERY_MANY_TILES) : QUERY_MANY_TILES;
+    while ((E->qs->q.nb_cap + M.tiles - 1) / M.tiles > M.nc_cap) M.tiles++;  // the chunks fit the buffers made at init
+    return TBGPU_STATUS_OK;
 }
 
 // ---- get_account_balances (k_balances.h, include/tbgpu.h) -----------------------------------------

@@ -287,6 +287,12 @@ tbgpu_query_result StateMachine::get_account_transfers(const tbgpu_account_filte
     return r;
 }
 
+void StateMachine::get_account_transfers_many(const tbgpu_account_filter* filters, uint32_t n_filters, void* out,
+                                              uint32_t out_cap_records, tbgpu_query_result* results) {
+    check(tbgpu_get_account_transfers_many(engine_, filters, n_filters, out, out_cap_records, results),
+          "get_account_transfers_many");
+}
+
 tbgpu_query_result StateMachine::get_account_balances(const tbgpu_account_filter& filter, void* out,
                                                       uint32_t out_cap_records) {
     tbgpu_query_result r{};

@@ -234,6 +234,13 @@ public:
     // result.complete == 0: the engine has evicted transfers, and the caller merges with its forest.
     tbgpu_query_result get_account_transfers(const tbgpu_account_filter& filter, void* out, uint32_t out_cap_records);
 
+    // Up to TBGPU_QUERY_FILTERS_MAX of those queries over one read of the log
+    // (tbgpu_get_account_transfers_many): for consecutive query requests with no write between them.
+    // Answer i is get_account_transfers(filters[i], out + i * out_cap_records records, out_cap_records)
+    // and lands in results[i]; an invalid filter's entry is empty.
+    void get_account_transfers_many(const tbgpu_account_filter* filters, uint32_t n_filters, void* out,
+                                    uint32_t out_cap_records, tbgpu_query_result* results);
+
     // The balance history (tbgpu_get_account_balances; a read): one tbgpu_account_balance row per
     // transfer get_account_transfers returns for the same filter, in the same order — the account's
     // four balances right after that transfer, derived from the current balances and the resident

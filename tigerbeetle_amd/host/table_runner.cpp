@@ -304,7 +304,10 @@ std::string run_table(tb::StateMachine& sm, const std::string& text) {
 // (the records are tbgpu_account_balance rows).
 // --query-change-events (tests/test_gpu_change_events_cpp.py): the prepares ending in a
 // tbgpu_change_events_filter, answered by get_change_events (the records are 384-byte events).
-enum QueryKind { ACCOUNT_TRANSFERS, ACCOUNT_BALANCES, QUERY_TRANSFERS, QUERY_ACCOUNTS, CHANGE_EVENTS };
+// --query-many (tests/test_gpu_query_many_cpp.py): the prepares ending in {0, 0, n * 64, n
+// tbgpu_account_filter}, answered by get_account_transfers_many; <answer.bin> receives, per filter,
+// the 16-byte tbgpu_query_result and then its records.
+enum QueryKind { ACCOUNT_TRANSFERS, ACCOUNT_BALANCES, QUERY_TRANSFERS, QUERY_ACCOUNTS, CHANGE_EVENTS, ACCOUNT_TRANSFERS_MANY };
 
 int run_query(tb::StateMachine& sm, QueryKind kind, const char* in_path, const char* out_path) {
     std::ifstream in(in_path, std::ios::binary);
@@ -331,6 +334,26 @@ int run_query(tb::StateMachine& sm, QueryKind kind, const char* in_path, const c
     tbgpu_query_filter q;
     tbgpu_change_events_filter c;
     static_assert(sizeof(f) == sizeof(q) && sizeof(f) == sizeof(c), "every filter is 64 bytes");
+    if (kind == ACCOUNT_TRANSFERS_MANY) {
+        const size_t n = body.size() / sizeof(f);
+        if (body.size() % sizeof(f) || n == 0 || n > TBGPU_QUERY_FILTERS_MAX) {
+            fprintf(stderr, "%s: 1 to %u filters of %zu bytes\n", in_path, TBGPU_QUERY_FILTERS_MAX, sizeof(f));
+            return 2;
+        }
+        std::vector<tbgpu_account_filter> filters(n);
+        memcpy(filters.data(), body.data(), body.size());
+        std::vector<tbgpu_query_result> results(n);
+        std::vector<uint8_t> out(n * (size_t)TBGPU_BATCH_EVENTS_MAX * 128);
+        sm.get_account_transfers_many(filters.data(), (uint32_t)n, out.data(), TBGPU_BATCH_EVENTS_MAX, results.data());
+        std::ofstream o(out_path, std::ios::binary);
+        for (size_t i = 0; i < n; i++) {
+            o.write((const char*)&results[i], sizeof(results[i]))
+                .write((const char*)out.data() + i * (size_t)TBGPU_BATCH_EVENTS_MAX * 128, (size_t)results[i].count * 128);
+            printf("query %zu: %u of %llu records, complete %u\n", i, results[i].count, (unsigned long long)results[i].matched,
+                   results[i].complete);
+        }
+        return o ? 0 : 2;
+    }
     if (body.size() != sizeof(f)) {
         fprintf(stderr, "%s: a filter is %zu bytes\n", in_path, sizeof(f));
         return 2;
@@ -357,8 +380,9 @@ int main(int argc, char** argv) {
     const bool fields = argc > 1 && std::string(argv[1]) == "--query-fields";
     const bool balances = argc > 1 && std::string(argv[1]) == "--query-balances";
     const bool changes = argc > 1 && std::string(argv[1]) == "--query-change-events";
-    const bool query = fields || balances || changes || (argc > 1 && std::string(argv[1]) == "--query");
-    QueryKind kind = balances ? ACCOUNT_BALANCES : changes ? CHANGE_EVENTS : ACCOUNT_TRANSFERS;
+    const bool many = argc > 1 && std::string(argv[1]) == "--query-many";
+    const bool query = fields || balances || changes || many || (argc > 1 && std::string(argv[1]) == "--query");
+    QueryKind kind = balances ? ACCOUNT_BALANCES : changes ? CHANGE_EVENTS : many ? ACCOUNT_TRANSFERS_MANY : ACCOUNT_TRANSFERS;
     const char* self = argv[0];
     if (fields && argc > 2) {
         const std::string which = argv[2];
@@ -369,10 +393,11 @@ int main(int argc, char** argv) {
     if (argc < 2 || (query && argc < 4)) {
         fprintf(stderr,
                 "usage: %s <state_machine_tables.txt> [device]\n       %s --query <prepares.bin> <answer.bin> [device]\n"
+                "       %s --query-many <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-balances <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-change-events <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-fields <transfers|accounts> <prepares.bin> <answer.bin> [device]\n",
-                self, self, self, self, self);
+                self, self, self, self, self, self);
         return 2;
     }
     if (query) {

@@ -275,6 +275,33 @@ class Engine:
         _lib.check(fn(self.h, src, out.ctypes.data, cap, ctypes.byref(res)))
         return out[:res.count], int(res.matched), bool(res.complete)
 
+    FILTERS_MAX = 64  # TBGPU_QUERY_FILTERS_MAX
+
+    def get_account_transfers_many(self, filters, out_cap_records=None):
+        """Up to 64 account filters over one read of the log (tbgpu_get_account_transfers_many).
+        filters: a list of 64-byte tbgpu_account_filter records (account_filter(...) builds one).
+        Returns a list of (records, matched, complete), entry i exactly what
+        get_account_transfers_raw(filters[i], out_cap_records) returns; an invalid filter's entry is
+        empty.  out_cap_records: room per filter (default: the largest limit, one message body at most)."""
+        filters = [bytes(f) for f in filters]
+        if len(filters) > self.FILTERS_MAX:
+            raise ValueError("at most %d filters in one call" % self.FILTERS_MAX)
+        for f in filters:
+            if len(f) != ACCOUNT_FILTER_DTYPE.itemsize:
+                raise ValueError("an account filter is %d bytes" % ACCOUNT_FILTER_DTYPE.itemsize)
+        if not filters:
+            return []
+        src = np.frombuffer(b"".join(filters), dtype=ACCOUNT_FILTER_DTYPE).copy()
+        cap = int(min(src["limit"].max(), BATCH_MAX)) if out_cap_records is None else int(out_cap_records)
+        out = np.zeros((len(filters), max(cap, 1)), dtype=TRANSFER_DTYPE)
+        res = (_lib.tbgpu_query_result * len(filters))()
+        _lib.check(self.lib.tbgpu_get_account_transfers_many(self.h, src.ctypes.data, len(filters), out.ctypes.data, cap, res))
+        return [(out[i, :r.count].copy(), int(r.matched), bool(r.complete)) for i, r in enumerate(res)]
+
+    def query_many_tiles(self, tiles):
+        """Tiles per chunk of get_account_transfers_many's scan (tbgpu_bench_query_many_tiles)."""
+        _lib.check(self.lib.tbgpu_bench_query_many_tiles(self.h, int(tiles)))
+
     def get_account_balances(self, account_id, *, debits=True, credits=True, reversed=False, timestamp_min=0,
                              timestamp_max=0, limit=8190, out_cap_records=None):
         """The balances of `account_id` right after each transfer get_account_transfers returns for
@@ -668,6 +695,11 @@ class StateMachine:
         """The account-filter query (Engine.get_account_transfers): a read, no operation number in
         the reference's enum, so it does not go through commit."""
         return self.engine.get_account_transfers(account_id, **filter)
+
+    def get_account_transfers_many(self, filters, out_cap_records=None):
+        """Consecutive get_account_transfers requests with no write between them, answered by one
+        read of the log (Engine.get_account_transfers_many): a read, not a commit."""
+        return self.engine.get_account_transfers_many(filters, out_cap_records)
 
     def get_account_balances(self, account_id, **filter):
         """The balance history of one account (Engine.get_account_balances): a read, not a commit."""

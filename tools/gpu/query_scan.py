@@ -1,7 +1,7 @@
 """The account-filter scan (tbgpu_get_account_transfers, csrc/k_query.h) over a 16M-transfer log (2 GB)
 against a device-to-device copy of the same log range, in one process.
 
-usage: python tools/gpu/query_scan.py [transfers] [runs] [--only account|fields|balances|change_events]
+usage: python tools/gpu/query_scan.py [transfers] [runs] [--only account|fields|balances|change_events|many]
 
 The log is built by the device generator, committed in place (the way tools/gpu/device_pass.py builds
 a pass): once with uniform C2 ids, where the queried account is a cold one (a few dozen matches), and
@@ -26,6 +26,12 @@ once more, so the bar is about twice the time (explain a cold-account ratio abov
 query_transfers with the same window and limit and beside the copy of the log: the newest page of the
 uniform log (nothing is newer: the second scan reads timestamps only), its oldest page (the whole log
 is newer) and the oldest page of the Zipf log, whose set holds the hottest account.
+
+`--only many` (tbgpu_get_account_transfers_many) times the batched call — the C call alone,
+into buffers made once — for 1, 8 and 64 cold filters on distinct accounts of the uniform log, the 64 all
+newest first, and 64 filters of the Zipf log that include its hottest account, beside the copy of the
+log and one single cold query of the same run; 64 x that single query's median is the yardstick.  It
+also times the 64 cold filters with chunks of 8, 16, 32 and 64 tiles.
 """
 import json
 import os
@@ -227,8 +233,93 @@ def measure_change_events():
     return out
 
 
+def measure_many():
+    """get_account_transfers_many beside the copy of the log and one single cold query, in one process."""
+    import ctypes
+
+    from tigerbeetle_amd import _lib
+    os.environ["TBGPU_QUERY_COOP"] = "0"
+    e = Engine(Options(accounts_max=n_acct, transfers_max=n_xfer, pass_events_max=pb * batch, pass_batches_max=pb))
+    a_lens = batches(n_acct, batch)
+    a_ts, t = timestamps(a_lens, 1_000_000_000)
+    acct = e.alloc(n_acct * 128)
+    e.generate_accounts(acct, 0, n_acct, seed=42)
+    res = e.alloc(max(n_acct, n_xfer) * 8)
+    rb = e.alloc((n_xfer // batch + 2) * 4)
+    e.commit_device_async(128, a_ts, a_lens, acct, res, rb)
+    e.sync()
+    spare = e.alloc(n_xfer * 128)
+    # The caller's buffers are made once, as a replica's are: the timed call is the C call alone.
+    h_out = np.zeros((64, 8190), dtype=TRANSFER_DTYPE)
+    h_res = (_lib.tbgpu_query_result * 64)()
+
+    def raw_many(filters):
+        src = ctypes.create_string_buffer(b"".join(filters), 64 * len(filters))
+        return lambda: _lib.check(e.lib.tbgpu_get_account_transfers_many(e.h, src, len(filters), h_out.ctypes.data, 8190, h_res))
+
+    def raw_single(f):
+        src = ctypes.create_string_buffer(f, 64)
+        return lambda: _lib.check(e.lib.tbgpu_get_account_transfers(e.h, src, h_out.ctypes.data, 8190, h_res))
+
+    def many_row(filters, single_ms):
+        want = [e.get_account_transfers_raw(f) for f in filters]
+        got = e.get_account_transfers_many(filters)
+        assert all(g[0].tobytes() == w[0].tobytes() and g[1:] == w[1:] for g, w in zip(got, want))
+        med, lo_ms, hi_ms = timed(e, raw_many(filters))
+        return row(med, lo_ms, hi_ms, filters=len(filters), matched=sum(w[1] for w in want), records=sum(len(w[0]) for w in want),
+                   per_filter_ms=round(med / len(filters), 4), singles_ms=round(len(filters) * single_ms, 4),
+                   speedup_over_singles=round(len(filters) * single_ms / med, 2))
+
+    out = {}
+    for name, kind in (("uniform", "c2"), ("zipf", "c3")):
+        if name != "uniform":
+            e.reset_transfers()
+        log = e.log_window(n_xfer)
+        e.generate_transfers(log, 0, n_xfer, n_acct, seed=42, kind=KINDS[kind])
+        e.sync()
+        x_lens = batches(n_xfer, batch)
+        x_ts, t = timestamps(x_lens, t + 10)
+        e.commit_device_async(129, x_ts, x_lens, log, res, rb)
+        e.sync()
+        sample = e.to_host(log + (n_xfer // 2) * 128, min(n_xfer // 2, 1 << 16) * 128).view(TRANSFER_DTYPE)
+        ids, counts = np.unique(sample[["debit_account_id_lo", "debit_account_id_hi"]], return_counts=True)
+        if name == "uniform":
+            accounts = [int(lo) | (int(hi) << 64) for lo, hi in ids[:: max(1, len(ids) // 64)][:64]]  # distinct cold accounts
+            assert len(set(accounts)) == 64
+            cold = [Engine.account_filter(a, limit=8190) for a in accounts]
+            med, lo_ms, hi_ms = timed(e, lambda: e.copy_device_async(spare, log, n_xfer * 128))
+            out["copy_d2d"] = dict(rates(med), min_ms=round(lo_ms, 4), max_ms=round(hi_ms, 4))
+            med, lo_ms, hi_ms = timed(e, lambda: e.get_account_transfers(accounts[0], limit=8190))
+            out["single_cold_wrapper"] = dict(rates(med), min_ms=round(lo_ms, 4), max_ms=round(hi_ms, 4))
+            med, lo_ms, hi_ms = timed(e, raw_single(cold[0]))
+            out["single_cold"] = dict(rates(med), min_ms=round(lo_ms, 4), max_ms=round(hi_ms, 4))
+            single_ms = med
+            for n in (1, 8, 64):
+                out["many_%d_cold" % n] = many_row(cold[:n], single_ms)
+            out["many_64_reversed"] = many_row([Engine.account_filter(a, reversed=True, limit=8190) for a in accounts], single_ms)
+            out["bar_64_cold_below_64_singles"] = out["many_64_cold"]["ms"] < 64 * single_ms
+            for tiles in (8, 16, 32, 64):  # the chunk's length
+                e.query_many_tiles(tiles)
+                med, lo_ms, hi_ms = timed(e, raw_many(cold))
+                out["many_64_cold_tiles_%d" % tiles] = row(med, lo_ms, hi_ms)
+            e.query_many_tiles(0)
+        else:
+            order = np.argsort(-counts)
+            accounts = [int(lo) | (int(hi) << 64) for lo, hi in ids[order[:1]]]  # the hottest account ...
+            accounts += [int(lo) | (int(hi) << 64) for lo, hi in ids[order[len(order) // 2:][:63]]]  # ... among 63 others
+            assert len(set(accounts)) == 64
+            hot = [Engine.account_filter(a, limit=8190) for a in accounts]
+            med, lo_ms, hi_ms = timed(e, raw_single(hot[0]))
+            out["single_hot"] = dict(rates(med), min_ms=round(lo_ms, 4), max_ms=round(hi_ms, 4))
+            out["many_64_with_hottest"] = many_row(hot, single_ms)
+    e.close()
+    return out
+
+
 result = dict(transfers=n_xfer, log_bytes=n_xfer * 128, runs=runs, warmups=WARMUPS)
-if only == "balances":
+if only == "many":
+    result["many"] = measure_many()
+elif only == "balances":
     result["balances"] = measure(False, balances=True)
 elif only == "change_events":
     result["change_events"] = measure_change_events()
@@ -237,6 +328,6 @@ elif only != "fields":
     for shape in ("lane_per_record", "cooperative"):
         r = result[shape]
         r["bar_query_le_copy"] = all(v["ms"] <= r["copy_d2d"]["ms"] for k, v in r.items() if k != "copy_d2d")
-if only not in ("account", "balances", "change_events"):
+if only not in ("account", "balances", "change_events", "many"):
     result["field_filters"] = measure_fields()
 print(json.dumps(result))
