@@ -40,7 +40,8 @@
  *     (a HIP error).  The Zig wrapper turns PANIC/DEVICE into @panic.
  *   - No allocation after tbgpu_init: every device buffer, pinned host buffer and HIP event is
  *     made there (tbgpu_debug_allocations, tbgpu_bench.h, counts them; tests/test_gpu_alloc.py
- *     holds the commit, prefetch and write-back entry points to zero).
+ *     holds the commit, prefetch and write-back entry points to zero).  tbgpu_deinit, and a
+ *     tbgpu_init that fails, release every one of them (tbgpu_debug_live).
  *   - A device panic (the reference would have trapped mid-commit) leaves state the reference
  *     never reaches, so the engine stops: every later call that changes state returns
  *     TBGPU_STATUS_PANIC until tbgpu_reset (or tbgpu_deinit).  Reads (exports, stats) still work.

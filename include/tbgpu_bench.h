@@ -126,6 +126,17 @@ double tbgpu_marker_elapsed_ms(tbgpu_t* engine, uint32_t a, uint32_t b);
  * tbgpu_init". */
 uint64_t tbgpu_debug_allocations(void);
 
+/* Device allocations, pinned host allocations, HIP events and streams the library holds right now
+ * (every engine of the process, calls in progress, and tbgpu_device_alloc blocks not yet freed): back
+ * to its earlier value once what was made since is released — after tbgpu_deinit, after a tbgpu_init
+ * that failed, after any call that made temporaries. */
+uint64_t tbgpu_debug_live(void);
+
+/* Tests only: the nth creation the library counts from now (1: the next one) returns
+ * hipErrorOutOfMemory without calling HIP, so the caller takes its ordinary error path
+ * (TBGPU_STATUS_DEVICE).  Host-side only, one shot; 0 disarms it. */
+void tbgpu_debug_fail_allocation(uint64_t nth);
+
 /* Device address of a single-device engine's event staging buffer (pass_events_max x 128 B): where a
  * host commit's events are copied, or written through by kernel 1 when it reads them from registered
  * memory.  Read-only for the engine's purposes: a test plants a sentinel behind a call's events and

@@ -1,9 +1,11 @@
 """The engine's conventions (include/tbgpu.h): no allocation after tbgpu_init on the commit,
 prefetch and write-back entry points; a prefetch-staged body belongs to the very next commit only;
-a device panic stops the engine until tbgpu_reset; kernel launch spans on the device clock; and the
+a device panic stops the engine until tbgpu_reset; kernel launch spans on the device clock; the
 asynchronous write-back returns exactly what the synchronous one does, however many commits run
-while it is in flight."""
+while it is in flight; and everything the library creates is released — by tbgpu_deinit, by a
+tbgpu_init that fails at any point, and by every call that makes temporaries (tbgpu_debug_live)."""
 import ctypes
+import gc
 
 import numpy as np
 import pytest
@@ -12,7 +14,8 @@ from tests.harness.oracle import OracleEngine
 from tests.harness.workload import Scenario, make_scenario, run_many, run_oracle
 from tests.test_gpu_differential import CONFIGS
 from tigerbeetle_amd import _lib
-from tigerbeetle_amd._lib import EnginePanic
+from tigerbeetle_amd._lib import EngineError, EnginePanic
+from tigerbeetle_amd.state_machine import Engine, Options
 from tigerbeetle_amd.types import ACCOUNT_DTYPE, TRANSFER_DTYPE, TransferFlags
 
 pytestmark = pytest.mark.gpu
@@ -20,6 +23,16 @@ pytestmark = pytest.mark.gpu
 
 def allocations():
     return int(_lib.load().tbgpu_debug_allocations())
+
+
+def live():
+    """What the library holds right now; engines that earlier tests dropped unclosed are collected first."""
+    gc.collect()
+    return int(_lib.load().tbgpu_debug_live())
+
+
+def _fail_allocation(nth):
+    _lib.load().tbgpu_debug_fail_allocation(nth)
 
 
 def _accounts(n, ledger=1):
@@ -400,3 +413,141 @@ def test_chunked_write_back_bound_copy_out(stage, gpu_engine_factory):
             sorted(zip(map(bytes, d_a.accounts.view(np.uint8).reshape(-1, 128)), map(bytes, d_a.accounts_before)))
     e_async.unregister_host(buf)
     assert e_async.export_accounts().tobytes() == oracle.export_accounts().tobytes()
+
+
+# -- ownership: what is created is released ------------------------------------------------------------
+
+SMALL = dict(accounts_max=1 << 12, transfers_max=1 << 18, pass_events_max=1 << 14, pass_batches_max=16)
+# A shard of the two-shard node of SMALL, as node_init (csrc/node.h) sizes it: the log of the transfers
+# homed there with room for imbalance and one pass's receipts, routed passes of 1.25 source blocks + 8192
+# events (at most the receipts of a pass), the owned accounts plus the import room.
+SMALL_NODE2_SHARD = dict(accounts_max=(1 << 12) + (1 << 12), transfers_max=(1 << 17) + (1 << 14) + (1 << 15) + 4096,
+                         pass_events_max=(1 << 14) + (1 << 12) + 8192, pass_batches_max=16)
+FORMS = {"single": SMALL, "profile": dict(SMALL, profile=True), "node2": dict(SMALL, devices=(0, 0))}
+
+_creations = {}
+
+
+def _init_creations(form, **opts):
+    """Creations tbgpu_init counts for these options (taken once)."""
+    if form not in _creations:
+        before = allocations()
+        engine = Engine(Options(**opts))
+        _creations[form] = allocations() - before
+        engine.close()
+    return _creations[form]
+
+
+@pytest.mark.parametrize("form", ["single", "profile", "node2"])
+def test_deinit_releases_everything(form):
+    """After commits, a batched query, every export, a write-back and (one engine) tbgpu_route_init,
+    tbgpu_deinit leaves the library holding what it held before tbgpu_init; while the engine lived it
+    held at least as many resources as init counted creations."""
+    before, created = live(), allocations()
+    engine = Engine(Options(**FORMS[form]))
+    try:
+        created = allocations() - created
+        assert live() - before >= created > 0
+        assert engine.commit(128, 10**9, _accounts(64).tobytes()) == b""
+        assert engine.commit(129, 2 * 10**9, _transfers(1000, 1, 64).tobytes()) == b""
+        many = engine.get_account_transfers_many([engine.account_filter(a, limit=10) for a in (1, 2)])
+        assert [len(r) for r, _, _ in many] == [10, 10]
+        assert len(engine.export_accounts()) == 64 and len(engine.export_transfers(cap=2048)) == 1000
+        assert len(engine.export_posted(cap=2048)) == 0
+        assert len(engine.checkpoint_delta(caps=(1 << 12, 1 << 12, 1 << 12)).transfers) == 1000
+        if form != "node2":
+            engine.route_init(2, 1 << 14)
+        assert live() - before >= created
+    finally:
+        engine.close()
+    assert live() == before
+
+
+POSITIONS = {"first": lambda t, t1: 1, "quarter": lambda t, t1: t // 4, "half": lambda t, t1: t // 2,
+             "three_quarters": lambda t, t1: 3 * t // 4, "last": lambda t, t1: t,
+             "second_shard_first": lambda t, t1: t1 + 1}
+
+
+@pytest.mark.parametrize("form,where", [("single", w) for w in list(POSITIONS)[:5]] + [("node2", w) for w in POSITIONS])
+def test_failed_init_releases_everything(form, where):
+    """tbgpu_init whose nth creation fails (the tables, the flow buffers, the write-back block, the queries'
+    buffers, the residency probe; on a node also the second shard's first and the sequencer's last)
+    returns the device status, hands out no handle and holds nothing it made; the next init of the same
+    shape works."""
+    opts = FORMS[form]
+    t = _init_creations(form, **opts)
+    nth = POSITIONS[where](t, _init_creations("node2_shard", **SMALL_NODE2_SHARD) if form == "node2" else 0)
+    assert 1 <= nth <= t
+    before = live()
+    failed = Engine.__new__(Engine)
+    _fail_allocation(nth)
+    try:
+        with pytest.raises(EngineError) as err:
+            failed.__init__(Options(**opts))
+    finally:
+        _fail_allocation(0)
+        failed.close()
+    assert err.value.status == _lib.STATUS_DEVICE and getattr(failed, "h", None) is None
+    assert live() == before
+    engine = Engine(Options(**opts))
+    try:
+        assert engine.commit(128, 10**9, _accounts(64).tobytes()) == b""
+        assert engine.commit(129, 2 * 10**9, _transfers(100, 1, 64).tobytes()) == b""
+    finally:
+        engine.close()
+    assert live() == before
+
+
+def test_call_scoped_allocations_are_released(gpu_engine_factory):
+    """The exports and the ledger summary hold nothing once they return, and an export (or
+    tbgpu_route_dependents) whose temporary cannot be made returns the device status, holds nothing
+    and leaves the engine answering as before."""
+    engine = gpu_engine_factory(**SMALL)
+    assert engine.commit(128, 10**9, _accounts(64).tobytes()) == b""
+    assert engine.commit(129, 2 * 10**9, _transfers(1000, 1, 64).tobytes()) == b""
+    held = live()
+    expected = engine.export_transfers(cap=2048).tobytes()
+    assert len(expected) == 1000 * 128 and live() == held
+    assert len(engine.export_accounts()) == 64 and live() == held
+    assert len(engine.export_posted(cap=2048)) == 0 and live() == held
+    assert engine.ledger_summary()["accounts"] == 64 and live() == held
+    _fail_allocation(2)
+    try:
+        with pytest.raises(EngineError) as err:
+            engine.export_transfers(cap=2048)
+    finally:
+        _fail_allocation(0)
+    assert err.value.status == _lib.STATUS_DEVICE and live() == held
+    assert engine.export_transfers(cap=2048).tobytes() == expected
+
+    engine.route_init(2, 1 << 14)
+    events, dep = engine.alloc(128), engine.alloc(64)
+    engine.to_device(events, _transfers(1, 5000, 64).view(np.uint8))
+    marked = np.array([[1, 0]], dtype=np.uint64)
+    held = live()
+    _fail_allocation(1)
+    try:
+        status = engine.lib.tbgpu_route_dependents(engine.h, 1, (ctypes.c_uint32 * 1)(1), events, marked.ctypes.data, 1, dep)
+    finally:
+        _fail_allocation(0)
+    assert status == _lib.STATUS_DEVICE and live() == held
+    engine.free(events)
+    engine.free(dep)
+    assert live() == held - 2
+
+
+def test_route_init_failing_part_way_is_released_at_deinit():
+    before = live()
+    engine = Engine(Options(**SMALL))
+    try:
+        _fail_allocation(3)
+        try:
+            status = engine.lib.tbgpu_route_init(engine.h, 2, 1 << 14)
+        finally:
+            _fail_allocation(0)
+        assert status == _lib.STATUS_DEVICE
+        assert engine.commit(128, 10**9, _accounts(64).tobytes()) == b""
+        assert engine.commit(129, 2 * 10**9, _transfers(100, 1, 64).tobytes()) == b""
+    finally:
+        engine.close()
+    assert live() == before

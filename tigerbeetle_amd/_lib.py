@@ -208,6 +208,8 @@ SIGNATURES = [
     ("tbgpu_last_error", ctypes.c_char_p, []),
     ("tbgpu_checksum", None, [_P, _U64, _P]),
     ("tbgpu_debug_allocations", _U64, []),
+    ("tbgpu_debug_live", _U64, []),
+    ("tbgpu_debug_fail_allocation", None, [_U64]),
     ("tbgpu_debug_staging", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_void_p)]),
     ("tbgpu_bench_generate_accounts", ctypes.c_int, [_P, _P, _U64, _U64, ctypes.POINTER(tbgpu_workload)]),
     ("tbgpu_bench_generate_transfers", ctypes.c_int, [_P, _P, _U64, _U64, ctypes.POINTER(tbgpu_workload)]),

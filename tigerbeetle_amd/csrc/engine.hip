@@ -41,27 +41,94 @@
 
 static thread_local std::string g_err;
 
-// Every device / pinned allocation and HIP event the library makes goes through these (counted):
-// tbgpu.h promises none after tbgpu_init on the commit path, and tests/test_gpu_alloc.py holds the
-// library to it with tbgpu_debug_allocations().
-static std::atomic<uint64_t> g_allocs{0};
+// Every device / pinned allocation, HIP event and stream the library makes is created through the
+// wrappers below (counted) into an Owner, which alone releases it: an engine's owner at tbgpu_deinit,
+// a call-scoped one when the call returns, on every path.  tbgpu.h promises no creation after
+// tbgpu_init on the commit path, and tests/test_gpu_alloc.py holds the library to it with
+// tbgpu_debug_allocations(), and to "everything created is released" with tbgpu_debug_live().
+static std::atomic<uint64_t> g_allocs{0};   // creations so far
+static std::atomic<uint64_t> g_live{0};     // resources held now (owners, and tbgpu_device_alloc blocks)
+static std::atomic<uint64_t> g_fail_in{0};  // tbgpu_debug_fail_allocation: the creation that many from now fails
+
+struct Owner {
+    enum Kind : uint8_t { DEVICE, PINNED, EVENT, STREAM };
+    struct Held {
+        void* p;
+        int device;
+        Kind kind;
+    };
+    std::vector<Held> held;  // in the order of creation; an alias of a held pointer is never added
+
+    Owner() = default;
+    Owner(const Owner&) = delete;
+    Owner& operator=(const Owner&) = delete;
+    ~Owner() { release(); }
+
+    // Counts one creation; false: it is the one armed to fail, and HIP is not called.
+    static bool count() {
+        g_allocs++;
+        for (uint64_t n = g_fail_in.load(); n;) {
+            if (g_fail_in.compare_exchange_weak(n, n - 1)) return n != 1;
+        }
+        return true;
+    }
+    // Takes what a successful creation wrote to *p.
+    hipError_t hold(Kind kind, hipError_t e, void** p) {
+        if (e != hipSuccess) return e;
+        int device = 0;
+        (void)hipGetDevice(&device);
+        held.push_back({*p, device, kind});
+        g_live++;
+        return hipSuccess;
+    }
+    // Waits for every stream held.
+    void drain() {
+        for (const Held& h : held) {
+            if (h.kind == STREAM && hipSetDevice(h.device) == hipSuccess) (void)hipStreamSynchronize((hipStream_t)h.p);
+        }
+    }
+    // Newest first, each on the device it was made on.
+    void release() {
+        for (; !held.empty(); held.pop_back(), g_live--) {
+            const Held& h = held.back();
+            (void)hipSetDevice(h.device);
+            switch (h.kind) {
+            case DEVICE: (void)hipFree(h.p); break;
+            case PINNED: (void)hipHostFree(h.p); break;
+            case EVENT: (void)hipEventDestroy((hipEvent_t)h.p); break;
+            case STREAM: (void)hipStreamDestroy((hipStream_t)h.p); break;
+            }
+        }
+    }
+    // tbgpu_device_alloc: the caller owns them from here (tbgpu_device_free); they stay live.
+    void disown() { held.clear(); }
+};
+
 template <typename T>
-static hipError_t tbMalloc(T** p, size_t bytes) {
-    g_allocs++;
-    return hipMalloc((void**)p, bytes);
+static hipError_t tbMalloc(Owner& o, T** p, size_t bytes) {
+    if (!Owner::count()) return hipErrorOutOfMemory;
+    return o.hold(Owner::DEVICE, hipMalloc((void**)p, bytes), (void**)p);
 }
 template <typename T>
-static hipError_t tbHostMalloc(T** p, size_t bytes, unsigned flags) {
-    g_allocs++;
-    return hipHostMalloc((void**)p, bytes, flags);
+static hipError_t tbHostMalloc(Owner& o, T** p, size_t bytes, unsigned flags) {
+    if (!Owner::count()) return hipErrorOutOfMemory;
+    return o.hold(Owner::PINNED, hipHostMalloc((void**)p, bytes, flags), (void**)p);
 }
-static hipError_t tbEventCreate(hipEvent_t* e) {
-    g_allocs++;
-    return hipEventCreate(e);
+static hipError_t tbEventCreate(Owner& o, hipEvent_t* e) {
+    if (!Owner::count()) return hipErrorOutOfMemory;
+    return o.hold(Owner::EVENT, hipEventCreate(e), (void**)e);
 }
-static hipError_t tbEventCreateWithFlags(hipEvent_t* e, unsigned flags) {
-    g_allocs++;
-    return hipEventCreateWithFlags(e, flags);
+static hipError_t tbEventCreateWithFlags(Owner& o, hipEvent_t* e, unsigned flags) {
+    if (!Owner::count()) return hipErrorOutOfMemory;
+    return o.hold(Owner::EVENT, hipEventCreateWithFlags(e, flags), (void**)e);
+}
+// A non-blocking stream; `priority` non-null: at that priority.  Held and live like the rest, but not
+// among the counted creations: streams are made at init only, where nothing asserts on the count.
+static hipError_t tbStreamCreate(Owner& o, hipStream_t* s, const int* priority = nullptr) {
+    return o.hold(Owner::STREAM,
+                  priority ? hipStreamCreateWithPriority(s, hipStreamNonBlocking, *priority)
+                           : hipStreamCreateWithFlags(s, hipStreamNonBlocking),
+                  (void**)s);
 }
 
 static int fail(int status, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
@@ -101,7 +168,7 @@ struct ProfilePair {
 };
 
 struct TbNode;      // node.h: the multi-device engine (tbgpu_config.device_count > 1)
-struct QueryState;  // query.h: the queries' buffers, made by query_init and released by query_free
+struct QueryState;  // query.h: the queries' buffers, made by query_init into the engine's owner
 
 // Groove write-back buffers (tbgpu_checkpoint_delta / _async), every one allocated at tbgpu_init.
 #define WB_IDS_MAX (1ULL << 20)  // listed ids (creates, direct balance writes) between write-backs
@@ -163,6 +230,7 @@ struct tbgpu {
     tbgpu_config cfg{};
     TbNode* node = nullptr;  // set: this handle is a node engine; every call goes to node.h
     int device = 0;
+    Owner own;  // every device resource of this engine: its own, the queries', tbgpu_route_init's, a node's on this shard
     hipStream_t stream = nullptr;
 
     Tables T{};
@@ -454,8 +522,9 @@ __global__ __launch_bounds__(FLOW_THREADS) void tb_residency_probe(u32* counter,
 }
 
 static int residency_probe(tbgpu* E, u32 grid) {
+    Owner scratch;
     u32* d = nullptr;
-    HIPCK(tbMalloc(&d, 8));
+    HIPCK(tbMalloc(scratch, &d, 8));
     hipFuncAttributes attr{};
     size_t lds = 0;
     if (hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&tb_flow)) == hipSuccess) lds = attr.sharedSizeBytes;
@@ -481,7 +550,6 @@ static int residency_probe(tbgpu* E, u32 grid) {
     }
     if (e == hipSuccess) e = hipMemcpyAsync(h, d, 8, hipMemcpyDeviceToHost, E->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(E->stream);
-    (void)hipFree(d);
     if (e != hipSuccess) return fail(TBGPU_STATUS_DEVICE, "tbgpu_init: residency probe: %s", hipGetErrorString(e));
     if (h[1]) {
         st = fail(TBGPU_STATUS_DEVICE,
@@ -535,9 +603,13 @@ static int node_api_set_commit_timestamp(TbNode* N, u64 timestamp);
 static int query_init(tbgpu* E);
 static void query_free(tbgpu* E);
 
+static int engine_init(tbgpu* E);
+
+// A failing init releases what it had made: whatever engine_init returned at, tbgpu_deinit frees the
+// engine's owner as far as it was filled.
 extern "C" int tbgpu_init(const tbgpu_config* config, tbgpu_t** out) {
-    if (config && config->device_count > 1) return node_api_init(config, out);
     *out = nullptr;
+    if (config && config->device_count > 1) return node_api_init(config, out);
     if (!config || config->accounts_max == 0 || config->transfers_max == 0 || config->pass_events_max == 0 ||
         config->pass_batches_max == 0) {
         return fail(TBGPU_STATUS_INVALID, "tbgpu_init: invalid config");
@@ -560,18 +632,19 @@ extern "C" int tbgpu_init(const tbgpu_config* config, tbgpu_t** out) {
     if (const char* ab = getenv("TBGPU_ABLATE")) E->ablate = (u32)strtoul(ab, nullptr, 0);  // timing experiments only
     E->kclock_off = getenv("TBGPU_NO_KCLOCK") != nullptr;  // timing experiments: no launch-span stamps
 #endif
-    int st = TBGPU_STATUS_OK;
-#define INIT_CK(x)                                                                                 \
-    do {                                                                                           \
-        hipError_t e_ = (x);                                                                       \
-        if (e_ != hipSuccess) {                                                                    \
-            st = fail(TBGPU_STATUS_DEVICE, "%s: %s", #x, hipGetErrorString(e_));                   \
-            tbgpu_deinit(E);                                                                       \
-            return st;                                                                             \
-        }                                                                                          \
-    } while (0)
-    INIT_CK(hipSetDevice(E->device));
-    INIT_CK(hipStreamCreateWithFlags(&E->stream, hipStreamNonBlocking));
+    const int st = engine_init(E);
+    if (st) {
+        tbgpu_deinit(E);
+        return st;
+    }
+    *out = E;
+    return TBGPU_STATUS_OK;
+}
+
+static int engine_init(tbgpu* E) {
+    const tbgpu_config* config = &E->cfg;
+    HIPCK(hipSetDevice(E->device));
+    HIPCK(tbStreamCreate(E->own, &E->stream));
     dev_register(E, true);
 
     // Account table slots per account (load factor <= 1/2).  4 slots shorten the probes (validate
@@ -604,33 +677,31 @@ extern "C" int tbgpu_init(const tbgpu_config* config, tbgpu_t** out) {
     }
 
     size_t free_b = 0, total_b = 0;
-    INIT_CK(hipMemGetInfo(&free_b, &total_b));
+    HIPCK(hipMemGetInfo(&free_b, &total_b));
     const u64 need = E->account_cap * (sizeof(Account) + 4) + E->xlog_cap * (sizeof(Transfer) + 1) +
                      E->xidx_cap * (sizeof(u64) + 1) +
                      (u64)E->pe_max * (4 * 4 + 8 * 4 + 128 * PIPE_SLOTS + 8 + 4) + E->dedup_cap * 8;
     if (need > free_b) {
-        st = fail(TBGPU_STATUS_INVALID, "tbgpu_init: needs %llu bytes of HBM, %llu free",
-                  (unsigned long long)need, (unsigned long long)free_b);
-        tbgpu_deinit(E);
-        return st;
+        return fail(TBGPU_STATUS_INVALID, "tbgpu_init: needs %llu bytes of HBM, %llu free",
+                    (unsigned long long)need, (unsigned long long)free_b);
     }
 
-    INIT_CK(tbMalloc(&E->T.acct_hot, E->account_cap * sizeof(AccountHot)));
-    INIT_CK(tbMalloc(&E->T.bal.lo, E->account_cap * sizeof(AccountBal)));  // low plane, then high plane
+    HIPCK(tbMalloc(E->own, &E->T.acct_hot, E->account_cap * sizeof(AccountHot)));
+    HIPCK(tbMalloc(E->own, &E->T.bal.lo, E->account_cap * sizeof(AccountBal)));  // low plane, then high plane
     E->T.bal.hi = E->T.bal.lo + 4 * E->account_cap;
-    INIT_CK(tbMalloc(&E->T.acct_cold, E->account_cap * sizeof(AccountCold)));
-    INIT_CK(tbMalloc(&E->T.account_mark, E->account_cap * sizeof(u32)));
-    INIT_CK(tbMalloc(&E->T.xidx, E->xidx_cap * sizeof(u64)));
-    INIT_CK(tbMalloc(&E->T.xdup, E->xidx_cap));
-    INIT_CK(tbMalloc(&E->T.xlog, E->xlog_cap * sizeof(Transfer)));
-    INIT_CK(tbMalloc(&E->T.xposted, E->xlog_cap));
-    INIT_CK(tbMalloc(&E->g, sizeof(Globals)));
+    HIPCK(tbMalloc(E->own, &E->T.acct_cold, E->account_cap * sizeof(AccountCold)));
+    HIPCK(tbMalloc(E->own, &E->T.account_mark, E->account_cap * sizeof(u32)));
+    HIPCK(tbMalloc(E->own, &E->T.xidx, E->xidx_cap * sizeof(u64)));
+    HIPCK(tbMalloc(E->own, &E->T.xdup, E->xidx_cap));
+    HIPCK(tbMalloc(E->own, &E->T.xlog, E->xlog_cap * sizeof(Transfer)));
+    HIPCK(tbMalloc(E->own, &E->T.xposted, E->xlog_cap));
+    HIPCK(tbMalloc(E->own, &E->g, sizeof(Globals)));
     {
         // The evicted-id filter: 8 bits per log position (about 2 % false positives at one log's worth
         // of evicted ids with 3 hashes; more evictions raise it — extra forest lookups, never errors).
         const u64 bits = std::min<u64>(1ULL << 34, pow2_at_least(std::max<u64>(1ULL << 16, 8 * E->xlog_cap)));
         E->bloom_mask = bits - 1;
-        INIT_CK(tbMalloc(&E->bloom, bits / 8));
+        HIPCK(tbMalloc(E->own, &E->bloom, bits / 8));
     }
     {
         // tb_flow: 1024-thread workgroups, all resident (see flow_grid).
@@ -676,60 +747,60 @@ extern "C" int tbgpu_init(const tbgpu_config* config, tbgpu_t** out) {
     E->T.g = E->g;
 
     const u64 pe = E->pe_max;
-    INIT_CK(tbMalloc(&E->info, pe * 4));
-    INIT_CK(tbMalloc(&E->eflags, pe * 2));
-    INIT_CK(tbMalloc(&E->dr, pe * 4));
-    INIT_CK(tbMalloc(&E->cr, pe * 4));
-    INIT_CK(tbMalloc(&E->ps, pe * 4));
-    INIT_CK(tbMalloc(&E->rs, pe * 4));
-    INIT_CK(tbMalloc(&E->dep_list, pe * 4));
-    INIT_CK(tbMalloc(&E->dep_count, (u64)E->pb_max * 4));
-    INIT_CK(tbMalloc(&E->amt, pe * 16));
-    INIT_CK(tbMalloc(&E->kid, pe * 8));
-    INIT_CK(tbMalloc(&E->kpid, pe * 8));
-    INIT_CK(tbMalloc(&E->dedup, E->dedup_cap * 8));
-    INIT_CK(tbMalloc(&E->sum_shards, SUM_WORDS * 8));
-    INIT_CK(tbMalloc(&E->undo, (u64)E->undo_cap * sizeof(UndoEntry)));
+    HIPCK(tbMalloc(E->own, &E->info, pe * 4));
+    HIPCK(tbMalloc(E->own, &E->eflags, pe * 2));
+    HIPCK(tbMalloc(E->own, &E->dr, pe * 4));
+    HIPCK(tbMalloc(E->own, &E->cr, pe * 4));
+    HIPCK(tbMalloc(E->own, &E->ps, pe * 4));
+    HIPCK(tbMalloc(E->own, &E->rs, pe * 4));
+    HIPCK(tbMalloc(E->own, &E->dep_list, pe * 4));
+    HIPCK(tbMalloc(E->own, &E->dep_count, (u64)E->pb_max * 4));
+    HIPCK(tbMalloc(E->own, &E->amt, pe * 16));
+    HIPCK(tbMalloc(E->own, &E->kid, pe * 8));
+    HIPCK(tbMalloc(E->own, &E->kpid, pe * 8));
+    HIPCK(tbMalloc(E->own, &E->dedup, E->dedup_cap * 8));
+    HIPCK(tbMalloc(E->own, &E->sum_shards, SUM_WORDS * 8));
+    HIPCK(tbMalloc(E->own, &E->undo, (u64)E->undo_cap * sizeof(UndoEntry)));
     if (E->legs_ok) {
-        INIT_CK(tbMalloc(&E->resolve_slow, (u64)E->pb_max * 4));
-        INIT_CK(tbMalloc(&E->leg_w, pe * 2 * 8));
-        INIT_CK(tbMalloc(&E->leg_off, (u64)std::min<u32>(E->pb_max, LEG_PREPARES_MAX) * (E->leg_buckets + 1) * 4));
-        INIT_CK(tbMalloc(&E->leg_tot, ((u64)E->leg_buckets + 1) * 4));
-        INIT_CK(hipMemset(E->leg_tot, 0, ((u64)E->leg_buckets + 1) * 4));
+        HIPCK(tbMalloc(E->own, &E->resolve_slow, (u64)E->pb_max * 4));
+        HIPCK(tbMalloc(E->own, &E->leg_w, pe * 2 * 8));
+        HIPCK(tbMalloc(E->own, &E->leg_off, (u64)std::min<u32>(E->pb_max, LEG_PREPARES_MAX) * (E->leg_buckets + 1) * 4));
+        HIPCK(tbMalloc(E->own, &E->leg_tot, ((u64)E->leg_buckets + 1) * 4));
+        HIPCK(hipMemset(E->leg_tot, 0, ((u64)E->leg_buckets + 1) * 4));
     }
     if (E->flow_ok) {
         FlowArgs& F = E->F;
-        INIT_CK(tbMalloc(&F.f_pe, pe * 4));
-        INIT_CK(tbMalloc(&F.f_batch, pe * 4));
-        INIT_CK(tbMalloc(&F.f_len, pe * 4));
-        INIT_CK(tbMalloc(&F.need, pe * 4));
-        INIT_CK(tbMalloc(&F.nsucc, pe * 4));
-        INIT_CK(tbMalloc(&F.queue, pe * 4));
-        INIT_CK(tbMalloc(&F.uflags, pe * 4));
-        INIT_CK(tbMalloc(&F.nacct, pe * 4));
-        INIT_CK(tbMalloc(&F.rpos, pe * 4));
-        INIT_CK(tbMalloc(&F.succ, pe * 4 * FLOW_RMAX));
-        INIT_CK(tbMalloc(&F.run, pe * sizeof(RunEntry) * FLOW_RMAX));
+        HIPCK(tbMalloc(E->own, &F.f_pe, pe * 4));
+        HIPCK(tbMalloc(E->own, &F.f_batch, pe * 4));
+        HIPCK(tbMalloc(E->own, &F.f_len, pe * 4));
+        HIPCK(tbMalloc(E->own, &F.need, pe * 4));
+        HIPCK(tbMalloc(E->own, &F.nsucc, pe * 4));
+        HIPCK(tbMalloc(E->own, &F.queue, pe * 4));
+        HIPCK(tbMalloc(E->own, &F.uflags, pe * 4));
+        HIPCK(tbMalloc(E->own, &F.nacct, pe * 4));
+        HIPCK(tbMalloc(E->own, &F.rpos, pe * 4));
+        HIPCK(tbMalloc(E->own, &F.succ, pe * 4 * FLOW_RMAX));
+        HIPCK(tbMalloc(E->own, &F.run, pe * sizeof(RunEntry) * FLOW_RMAX));
         for (int k = 0; k < 2; k++) {
-            INIT_CK(tbMalloc(&F.keys[k], pe * 4 * FLOW_RMAX));
-            INIT_CK(tbMalloc(&F.vals[k], pe * 4 * FLOW_RMAX));
+            HIPCK(tbMalloc(E->own, &F.keys[k], pe * 4 * FLOW_RMAX));
+            HIPCK(tbMalloc(E->own, &F.vals[k], pe * 4 * FLOW_RMAX));
         }
-        INIT_CK(tbMalloc(&F.hist, (u64)F.grid * 256 * 4));
-        INIT_CK(tbMalloc(&F.words, FW_WORDS * 4));
-        INIT_CK(tbMalloc(&F.undo, pe * 4 * sizeof(UndoEntry)));
-        INIT_CK(tbMalloc(&F.b_st, pe * 4));
-        INIT_CK(tbMalloc(&F.b_vd, pe));
-        INIT_CK(tbMalloc(&F.b_vc, pe));
-        INIT_CK(tbMalloc(&F.b_amt, pe * 8 * FLOW_RMAX));
-        INIT_CK(tbMalloc(&F.b_meta, pe * 4 * FLOW_RMAX));
-        INIT_CK(tbMalloc(&F.b_blk, (u64)F.grid * 5 * 8));
-        INIT_CK(tbMalloc(&F.b_qd, pe * 4));
-        INIT_CK(tbMalloc(&F.b_qc, pe * 4));
-        INIT_CK(tbMalloc(&F.b_head, pe * 4 * FLOW_RMAX));
-        INIT_CK(tbMalloc(&F.b_xy, pe * 16 * FLOW_RMAX));
-        INIT_CK(tbMalloc(&F.b_ex, pe * 16 * FLOW_RMAX));
-        INIT_CK(tbMalloc(&F.b_rec, pe * sizeof(SweepRec)));
-        INIT_CK(tbMalloc(&F.b_vw, pe * 4));
+        HIPCK(tbMalloc(E->own, &F.hist, (u64)F.grid * 256 * 4));
+        HIPCK(tbMalloc(E->own, &F.words, FW_WORDS * 4));
+        HIPCK(tbMalloc(E->own, &F.undo, pe * 4 * sizeof(UndoEntry)));
+        HIPCK(tbMalloc(E->own, &F.b_st, pe * 4));
+        HIPCK(tbMalloc(E->own, &F.b_vd, pe));
+        HIPCK(tbMalloc(E->own, &F.b_vc, pe));
+        HIPCK(tbMalloc(E->own, &F.b_amt, pe * 8 * FLOW_RMAX));
+        HIPCK(tbMalloc(E->own, &F.b_meta, pe * 4 * FLOW_RMAX));
+        HIPCK(tbMalloc(E->own, &F.b_blk, (u64)F.grid * 5 * 8));
+        HIPCK(tbMalloc(E->own, &F.b_qd, pe * 4));
+        HIPCK(tbMalloc(E->own, &F.b_qc, pe * 4));
+        HIPCK(tbMalloc(E->own, &F.b_head, pe * 4 * FLOW_RMAX));
+        HIPCK(tbMalloc(E->own, &F.b_xy, pe * 16 * FLOW_RMAX));
+        HIPCK(tbMalloc(E->own, &F.b_ex, pe * 16 * FLOW_RMAX));
+        HIPCK(tbMalloc(E->own, &F.b_rec, pe * sizeof(SweepRec)));
+        HIPCK(tbMalloc(E->own, &F.b_vw, pe * 4));
         F.walk = (config->flags & TBGPU_CONFIG_SWEEP_WINDOW) ? 0u : 1u;
         F.walk_merge = WALK_MERGE_DEFAULT;
 
@@ -738,141 +809,95 @@ extern "C" int tbgpu_init(const tbgpu_config* config, tbgpu_t** out) {
                       : (config->flags & TBGPU_CONFIG_SWEEP_EARLY) ? 0xFFFFFFFFu
                                                                    : FLOW_SWEEP_MIN;
     }
-    INIT_CK(tbMalloc(&E->staging, pe * 128));
-    INIT_CK(tbMalloc(&E->results, pe * 8));
-    INIT_CK(tbMalloc(&E->reply_bytes, E->meta_cap * 4));
-    INIT_CK(tbMalloc(&E->meta, (2 * E->meta_cap + 1) * 8));
-    INIT_CK(tbHostMalloc(&E->h_meta, (2 * E->meta_cap + 1) * 8, hipHostMallocDefault));
-    INIT_CK(tbHostMalloc(&E->h_globals, sizeof(Globals), hipHostMallocDefault));
-    INIT_CK(tbHostMalloc(&E->h_rb, E->meta_cap * 4, hipHostMallocDefault));
+    HIPCK(tbMalloc(E->own, &E->staging, pe * 128));
+    HIPCK(tbMalloc(E->own, &E->results, pe * 8));
+    HIPCK(tbMalloc(E->own, &E->reply_bytes, E->meta_cap * 4));
+    HIPCK(tbMalloc(E->own, &E->meta, (2 * E->meta_cap + 1) * 8));
+    HIPCK(tbHostMalloc(E->own, &E->h_meta, (2 * E->meta_cap + 1) * 8, hipHostMallocDefault));
+    HIPCK(tbHostMalloc(E->own, &E->h_globals, sizeof(Globals), hipHostMallocDefault));
+    HIPCK(tbHostMalloc(E->own, &E->h_rb, E->meta_cap * 4, hipHostMallocDefault));
     E->h_results_events = std::min<u64>(E->pe_max, 1ULL << 16);
-    INIT_CK(tbHostMalloc(&E->h_results, E->h_results_events * 8, hipHostMallocDefault));
-    INIT_CK(hipStreamCreateWithFlags(&E->copy_stream, hipStreamNonBlocking));
+    HIPCK(tbHostMalloc(E->own, &E->h_results, E->h_results_events * 8, hipHostMallocDefault));
+    HIPCK(tbStreamCreate(E->own, &E->copy_stream));
     for (int k = 0; k < PIPE_SLOTS; k++) {
         tbgpu::PipeSlot& S = E->pipe[k];
         if (k == 0) S.staging = E->staging;
-        else INIT_CK(tbMalloc(&S.staging, pe * 128));
-        INIT_CK(tbMalloc(&S.meta, (2 * E->meta_cap + 1) * 8));
-        INIT_CK(tbHostMalloc(&S.h_meta, (2 * E->meta_cap + 1) * 8, hipHostMallocDefault));
-        INIT_CK(tbHostMalloc(&S.h_reply, pipe_reply_bytes(E) + 64, hipHostMallocMapped));  // + the done word
+        else HIPCK(tbMalloc(E->own, &S.staging, pe * 128));
+        HIPCK(tbMalloc(E->own, &S.meta, (2 * E->meta_cap + 1) * 8));
+        HIPCK(tbHostMalloc(E->own, &S.h_meta, (2 * E->meta_cap + 1) * 8, hipHostMallocDefault));
+        HIPCK(tbHostMalloc(E->own, &S.h_reply, pipe_reply_bytes(E) + 64, hipHostMallocMapped));  // + the done word
         memset(S.h_reply + pipe_reply_bytes(E), 0, 64);
-        INIT_CK(hipHostGetDevicePointer((void**)&S.d_reply, S.h_reply, 0));
-        INIT_CK(tbEventCreate(&S.start));
-        INIT_CK(tbEventCreate(&S.copied));
-        INIT_CK(tbEventCreate(&S.done));
+        HIPCK(hipHostGetDevicePointer((void**)&S.d_reply, S.h_reply, 0));
+        HIPCK(tbEventCreate(E->own, &S.start));
+        HIPCK(tbEventCreate(E->own, &S.copied));
+        HIPCK(tbEventCreate(E->own, &S.done));
     }
-    INIT_CK(tbMalloc(&E->lookup_ids, (u64)E->lookup_cap * 16));
-    INIT_CK(tbMalloc(&E->lookup_out, (u64)E->lookup_cap * 128));
-    INIT_CK(tbMalloc(&E->lookup_found, E->lookup_cap));
-    INIT_CK(tbMalloc(&E->d_status, 16));
-    INIT_CK(tbMalloc(&E->pf_staging, (u64)BATCH_EVENTS_MAX * 128));
-    INIT_CK(tbEventCreateWithFlags(&E->pf_done, hipEventDisableTiming));
+    HIPCK(tbMalloc(E->own, &E->lookup_ids, (u64)E->lookup_cap * 16));
+    HIPCK(tbMalloc(E->own, &E->lookup_out, (u64)E->lookup_cap * 128));
+    HIPCK(tbMalloc(E->own, &E->lookup_found, E->lookup_cap));
+    HIPCK(tbMalloc(E->own, &E->d_status, 16));
+    HIPCK(tbMalloc(E->own, &E->pf_staging, (u64)BATCH_EVENTS_MAX * 128));
+    HIPCK(tbEventCreateWithFlags(E->own, &E->pf_done, hipEventDisableTiming));
     {  // groove write-back (tbgpu_checkpoint_delta*): snapshot, marks and one slice of buffers
         WbBufs& W = E->wb;
         W.cap_t = std::max<u64>(1, std::min<u64>(E->xlog_cap, std::max<u64>(pe, 64ULL * BATCH_EVENTS_MAX)));
         W.cap_ids = WB_IDS_MAX;
         W.cap_a = std::min<u64>(E->account_cap, std::max<u64>(2 * W.cap_t, W.cap_ids));
         const u64 nb = (W.cap_t + DELTA_THREADS - 1) / DELTA_THREADS;
-        INIT_CK(tbMalloc(&E->ckpt_bal, E->account_cap * sizeof(AccountBal)));
-        INIT_CK(tbMalloc(&E->ckpt_mark, E->account_cap * sizeof(u32)));
-        INIT_CK(hipMemset(E->ckpt_mark, 0, E->account_cap * sizeof(u32)));
-        INIT_CK(tbMalloc(&W.d_bc, nb * 4));
-        INIT_CK(tbMalloc(&W.d_base, nb * 8));
-        INIT_CK(tbMalloc(&W.d_out, W.cap_t * 128));
-        INIT_CK(tbMalloc(&W.d_ids, W.cap_t * 32));
-        INIT_CK(tbMalloc(&W.d_pv, W.cap_t * 24));
-        INIT_CK(tbMalloc(&W.d_pairs, W.cap_t * 16));
-        INIT_CK(tbMalloc(&W.d_hids, W.cap_ids * 16));
-        INIT_CK(tbMalloc(&W.d_acc, W.cap_a * 128));
-        INIT_CK(tbMalloc(&W.d_before, W.cap_a * sizeof(AccountBal)));
-        INIT_CK(tbMalloc(&W.d_slots, E->account_cap * 4));
-        INIT_CK(tbMalloc(&W.d_cap, W.cap_a * sizeof(AccountBal)));
-        INIT_CK(tbMalloc(&W.d_cnt, WB_COUNT_WORDS * 8));
-        INIT_CK(tbHostMalloc(&W.h_cnt, WB_COUNT_WORDS * 8, hipHostMallocDefault));
+        HIPCK(tbMalloc(E->own, &E->ckpt_bal, E->account_cap * sizeof(AccountBal)));
+        HIPCK(tbMalloc(E->own, &E->ckpt_mark, E->account_cap * sizeof(u32)));
+        HIPCK(hipMemset(E->ckpt_mark, 0, E->account_cap * sizeof(u32)));
+        HIPCK(tbMalloc(E->own, &W.d_bc, nb * 4));
+        HIPCK(tbMalloc(E->own, &W.d_base, nb * 8));
+        HIPCK(tbMalloc(E->own, &W.d_out, W.cap_t * 128));
+        HIPCK(tbMalloc(E->own, &W.d_ids, W.cap_t * 32));
+        HIPCK(tbMalloc(E->own, &W.d_pv, W.cap_t * 24));
+        HIPCK(tbMalloc(E->own, &W.d_pairs, W.cap_t * 16));
+        HIPCK(tbMalloc(E->own, &W.d_hids, W.cap_ids * 16));
+        HIPCK(tbMalloc(E->own, &W.d_acc, W.cap_a * 128));
+        HIPCK(tbMalloc(E->own, &W.d_before, W.cap_a * sizeof(AccountBal)));
+        HIPCK(tbMalloc(E->own, &W.d_slots, E->account_cap * 4));
+        HIPCK(tbMalloc(E->own, &W.d_cap, W.cap_a * sizeof(AccountBal)));
+        HIPCK(tbMalloc(E->own, &W.d_cnt, WB_COUNT_WORDS * 8));
+        HIPCK(tbHostMalloc(E->own, &W.h_cnt, WB_COUNT_WORDS * 8, hipHostMallocDefault));
         {   // the copy-out and the work beside the commits: the lowest priority, so the commits' kernels
             // are dispatched first
             int least = 0, greatest = 0;
-            INIT_CK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-            INIT_CK(hipStreamCreateWithPriority(&W.stream, hipStreamNonBlocking, least));
+            HIPCK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+            HIPCK(tbStreamCreate(E->own, &W.stream, &least));
         }
-        INIT_CK(tbEventCreateWithFlags(&W.gathered, hipEventDisableTiming));
-        INIT_CK(tbEventCreateWithFlags(&W.done, hipEventDisableTiming));
-        INIT_CK(tbEventCreateWithFlags(&W.read_done, hipEventDisableTiming));
-        INIT_CK(tbEventCreateWithFlags(&W.captured, hipEventDisableTiming));
+        HIPCK(tbEventCreateWithFlags(E->own, &W.gathered, hipEventDisableTiming));
+        HIPCK(tbEventCreateWithFlags(E->own, &W.done, hipEventDisableTiming));
+        HIPCK(tbEventCreateWithFlags(E->own, &W.read_done, hipEventDisableTiming));
+        HIPCK(tbEventCreateWithFlags(E->own, &W.captured, hipEventDisableTiming));
     }
-    INIT_CK(tbHostMalloc(&E->h_pub, 8, hipHostMallocDefault));
-    INIT_CK(tbMalloc(&E->kclock, (u64)KCLOCK_SLOTS * KCLOCK_WORDS * 8));
-    INIT_CK(tbHostMalloc(&E->h_kclock, (u64)KCLOCK_SLOTS * KCLOCK_WORDS * 8, hipHostMallocDefault));
-    for (int i = 0; i < 16; i++) INIT_CK(tbEventCreate(&E->markers[i]));
+    HIPCK(tbHostMalloc(E->own, &E->h_pub, 8, hipHostMallocDefault));
+    HIPCK(tbMalloc(E->own, &E->kclock, (u64)KCLOCK_SLOTS * KCLOCK_WORDS * 8));
+    HIPCK(tbHostMalloc(E->own, &E->h_kclock, (u64)KCLOCK_SLOTS * KCLOCK_WORDS * 8, hipHostMallocDefault));
+    for (int i = 0; i < 16; i++) HIPCK(tbEventCreate(E->own, &E->markers[i]));
     if (E->profile) {
         E->event_pool.resize(PROF_EVENTS);
-        for (auto& ev : E->event_pool) INIT_CK(tbEventCreate(&ev));
+        for (auto& ev : E->event_pool) HIPCK(tbEventCreate(E->own, &ev));
     }
-#undef INIT_CK
-    st = query_init(E);
-    if (st == TBGPU_STATUS_OK) st = engine_clear(E);
-    if (st == TBGPU_STATUS_OK && E->flow_ok) st = residency_probe(E, flow_grid(E));
-    if (st) {
-        tbgpu_deinit(E);
-        return st;
-    }
-    *out = E;
-    return TBGPU_STATUS_OK;
+    if (const int st = query_init(E)) return st;
+    if (const int st = engine_clear(E)) return st;
+    return E->flow_ok ? residency_probe(E, flow_grid(E)) : TBGPU_STATUS_OK;
 }
 
+// Nothing of the engine is in flight once every stream it owns has drained; a node has drained all its
+// devices before it comes here (node_free).
 extern "C" void tbgpu_deinit(tbgpu_t* E) {
-    if (E && E->node) {
+    if (!E) return;
+    if (E->node) {
         node_free(E->node);
         delete E;
         return;
     }
-    if (!E) return;
     (void)hipSetDevice(E->device);
     dev_register(E, false);
-    if (E->stream) (void)hipStreamSynchronize(E->stream);
-    void* bufs[] = {E->ckpt_bal, E->ckpt_mark, E->T.acct_hot, E->T.bal.lo, E->T.acct_cold, E->T.account_mark, E->T.xidx, E->T.xdup, E->T.xlog,
-                    E->T.xposted, E->g, E->bloom, E->info, E->eflags, E->dr,
-                    E->cr, E->ps, E->rs, E->dep_list, E->dep_count, E->amt, E->kid, E->kpid, E->dedup,
-                    E->sum_shards, E->undo, E->staging, E->results, E->reply_bytes, E->meta,
-                    E->lookup_ids, E->lookup_out, E->lookup_found, E->d_status, E->pf_staging, E->kclock, E->r_home,
-                    E->wb.d_bc, E->wb.d_base, E->wb.d_out, E->wb.d_ids, E->wb.d_pv, E->wb.d_pairs, E->wb.d_hids,
-                    E->wb.d_acc, E->wb.d_before, E->wb.d_slots, E->wb.d_cap, E->wb.d_cnt,
-                    E->r_block_counts, E->r_words, E->r_meta, E->resolve_slow, E->leg_w, E->leg_off, E->leg_tot,
-                    E->F.f_pe, E->F.f_batch, E->F.f_len, E->F.need, E->F.nsucc, E->F.queue, E->F.uflags, E->F.nacct, E->F.rpos, E->F.succ,
-                    E->F.run, E->F.keys[0], E->F.keys[1], E->F.vals[0], E->F.vals[1], E->F.hist, E->F.words, E->F.undo,
-                    E->F.b_st, E->F.b_vd, E->F.b_vc, E->F.b_amt, E->F.b_meta, E->F.b_blk,
-                    E->F.b_qd, E->F.b_qc, E->F.b_head, E->F.b_xy, E->F.b_ex, E->F.b_rec, E->F.b_vw};
-    for (void* p : bufs) if (p) (void)hipFree(p);
-    for (int k = 0; k < PIPE_SLOTS; k++) {
-        tbgpu::PipeSlot& S = E->pipe[k];
-        if (k > 0 && S.staging) (void)hipFree(S.staging);
-        if (S.meta) (void)hipFree(S.meta);
-        if (S.h_meta) (void)hipHostFree(S.h_meta);
-        if (S.h_reply) (void)hipHostFree(S.h_reply);
-        for (hipEvent_t e : {S.start, S.copied, S.done}) if (e) (void)hipEventDestroy(e);
-    }
-    if (E->copy_stream) (void)hipStreamDestroy(E->copy_stream);
-    if (E->h_meta) (void)hipHostFree(E->h_meta);
-    if (E->h_globals) (void)hipHostFree(E->h_globals);
-    if (E->h_rb) (void)hipHostFree(E->h_rb);
-    if (E->h_results) (void)hipHostFree(E->h_results);
-    if (E->h_rmeta) (void)hipHostFree(E->h_rmeta);
-    if (E->h_kclock) (void)hipHostFree(E->h_kclock);
-    if (E->h_pub) (void)hipHostFree(E->h_pub);
+    E->own.drain();
+    E->own.release();
     query_free(E);
-    if (E->wb.h_cnt) (void)hipHostFree(E->wb.h_cnt);
-    if (E->wb.stream) {
-        (void)hipStreamSynchronize(E->wb.stream);
-        (void)hipStreamDestroy(E->wb.stream);
-    }
-    if (E->wb.gathered) (void)hipEventDestroy(E->wb.gathered);
-    if (E->wb.done) (void)hipEventDestroy(E->wb.done);
-    if (E->wb.read_done) (void)hipEventDestroy(E->wb.read_done);
-    if (E->wb.captured) (void)hipEventDestroy(E->wb.captured);
-    for (hipEvent_t e : E->event_pool) (void)hipEventDestroy(e);
-    if (E->pf_done) (void)hipEventDestroy(E->pf_done);
-    for (int i = 0; i < 16; i++) if (E->markers[i]) (void)hipEventDestroy(E->markers[i]);
-    if (E->stream) (void)hipStreamDestroy(E->stream);
     delete E;
 }
 
@@ -1636,12 +1661,13 @@ static int export_records(tbgpu* E, std::vector<u8>& recs, std::vector<u64>* pos
     }
     const u64 cap = ACCOUNTS ? E->account_cap : E->xidx_cap;
     const u64 chunk = std::min<u64>(cap, 1ULL << 20);
+    Owner scratch;
     u8* d_out = nullptr;
     u64* d_cnt = nullptr;
     u64* d_posted = nullptr;
-    HIPCK(tbMalloc(&d_out, chunk * 128));
-    HIPCK(tbMalloc(&d_cnt, 16));
-    HIPCK(tbMalloc(&d_posted, chunk * 16));
+    HIPCK(tbMalloc(scratch, &d_out, chunk * 128));
+    HIPCK(tbMalloc(scratch, &d_cnt, 16));
+    HIPCK(tbMalloc(scratch, &d_posted, chunk * 16));
     int st = TBGPU_STATUS_OK;
     for (u64 s = 0; s < cap && st == TBGPU_STATUS_OK; s += chunk) {
         const u64 n = std::min<u64>(chunk, cap - s);
@@ -1671,10 +1697,8 @@ static int export_records(tbgpu* E, std::vector<u8>& recs, std::vector<u64>* pos
         }
         if (e != hipSuccess) st = fail(TBGPU_STATUS_DEVICE, "export: %s", hipGetErrorString(e));
     }
-    (void)hipFree(d_out);
-    (void)hipFree(d_cnt);
-    (void)hipFree(d_posted);
     if (st) return st;
+    scratch.release();  // before the host sort
     const u64 n = recs.size() / 128;
     std::vector<u64> idx(n);
     for (u64 i = 0; i < n; i++) idx[i] = i;
@@ -2348,6 +2372,8 @@ extern "C" void tbgpu_reset_stats(tbgpu_t* E) {
 extern "C" const char* tbgpu_last_error(void) { return g_err.c_str(); }
 
 extern "C" uint64_t tbgpu_debug_allocations(void) { return g_allocs.load(); }
+extern "C" uint64_t tbgpu_debug_live(void) { return g_live.load(); }
+extern "C" void tbgpu_debug_fail_allocation(uint64_t nth) { g_fail_in.store(nth); }
 
 // vsr.checksum (src/vsr/checksum.zig:50): host only, no device or engine needed.
 extern "C" void tbgpu_checksum(const void* data, uint64_t len, uint8_t out[16]) {
@@ -2469,11 +2495,12 @@ extern "C" int tbgpu_bench_access_mix(tbgpu_t* E, uint64_t transfers, double out
     A.index_mask = E->xidx_cap - 1;
     void *ev = nullptr, *rec = nullptr, *s4 = nullptr, *s2 = nullptr, *s8 = nullptr, *rw = nullptr, *ix = nullptr,
          *sink = nullptr;
+    Owner scratch;
     int st = TBGPU_STATUS_OK;
-    if (tbMalloc(&ev, transfers * 128) != hipSuccess || tbMalloc(&rec, transfers * 128) != hipSuccess ||
-        tbMalloc(&s4, transfers * 16) != hipSuccess || tbMalloc(&s2, transfers * 2) != hipSuccess ||
-        tbMalloc(&s8, transfers * 24) != hipSuccess || tbMalloc(&rw, rows * 32) != hipSuccess ||
-        tbMalloc(&ix, E->xidx_cap * 8) != hipSuccess || tbMalloc(&sink, 8) != hipSuccess ||
+    if (tbMalloc(scratch, &ev, transfers * 128) != hipSuccess || tbMalloc(scratch, &rec, transfers * 128) != hipSuccess ||
+        tbMalloc(scratch, &s4, transfers * 16) != hipSuccess || tbMalloc(scratch, &s2, transfers * 2) != hipSuccess ||
+        tbMalloc(scratch, &s8, transfers * 24) != hipSuccess || tbMalloc(scratch, &rw, rows * 32) != hipSuccess ||
+        tbMalloc(scratch, &ix, E->xidx_cap * 8) != hipSuccess || tbMalloc(scratch, &sink, 8) != hipSuccess ||
         hipMemsetAsync(ev, 1, transfers * 128, E->stream) != hipSuccess ||
         hipMemsetAsync(rw, 2, rows * 32, E->stream) != hipSuccess) {
         st = fail(TBGPU_STATUS_DEVICE, "access mix: allocation failed");
@@ -2496,8 +2523,6 @@ extern "C" int tbgpu_bench_access_mix(tbgpu_t* E, uint64_t transfers, double out
             if (t[k] < 0) st = fail(TBGPU_STATUS_DEVICE, "access mix: launch failed");
         }
     }
-    void* bufs[] = {ev, rec, s4, s2, s8, rw, ix, sink};
-    for (void* p : bufs) if (p) (void)hipFree(p);
     return st;
 }
 
@@ -2517,8 +2542,9 @@ static int ledger_summary(tbgpu* E, u32 world, u32 self, u64 out[10]) {
         int st = engine_sync(E);
         if (st) return st;
     }
+    Owner scratch;
     u64* d = nullptr;
-    HIPCK(tbMalloc(&d, 80));
+    HIPCK(tbMalloc(scratch, &d, 80));
     hipError_t e = hipMemsetAsync(d, 0, 80, E->stream);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(tb_ledger_summary, dim3((unsigned)((E->account_cap + 255) / 256)), dim3(256), 0, E->stream, E->T,
@@ -2527,7 +2553,6 @@ static int ledger_summary(tbgpu* E, u32 world, u32 self, u64 out[10]) {
     }
     if (e == hipSuccess) e = hipMemcpyAsync(out, d, 80, hipMemcpyDeviceToHost, E->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(E->stream);
-    (void)hipFree(d);
     if (e != hipSuccess) return fail(TBGPU_STATUS_DEVICE, "ledger summary: %s", hipGetErrorString(e));
     return TBGPU_STATUS_OK;
 }
@@ -2555,7 +2580,9 @@ extern "C" int tbgpu_device_alloc(tbgpu_t* E, uint64_t bytes, void** out) {
     API_ENTER(E, false);
     if (E->node) E = node_engine(E->node, 0);
     HIPCK(hipSetDevice(E->device));
-    HIPCK(tbMalloc(out, bytes));
+    Owner caller;
+    HIPCK(tbMalloc(caller, out, bytes));
+    caller.disown();
     return TBGPU_STATUS_OK;
 }
 
@@ -2564,6 +2591,7 @@ extern "C" int tbgpu_device_free(tbgpu_t* E, void* ptr) {
     if (E->node) E = node_engine(E->node, 0);
     HIPCK(hipSetDevice(E->device));
     HIPCK(hipFree(ptr));
+    if (ptr) g_live--;
     return TBGPU_STATUS_OK;
 }
 
@@ -2741,12 +2769,12 @@ extern "C" int tbgpu_route_init(tbgpu_t* E, uint32_t world, uint64_t events_max)
     E->route_world = world;
     E->route_events_max = events_max;
     const u64 nblocks = (events_max + ROUTE_THREADS - 1) / ROUTE_THREADS;
-    HIPCK(tbMalloc(&E->r_home, events_max));
-    HIPCK(tbMalloc(&E->r_block_counts, 2 * nblocks * world * 4));  // counts, then bases
+    HIPCK(tbMalloc(E->own, &E->r_home, events_max));
+    HIPCK(tbMalloc(E->own, &E->r_block_counts, 2 * nblocks * world * 4));  // counts, then bases
     E->r_block_cap = nblocks * world;
-    HIPCK(tbMalloc(&E->r_words, ROUTE_WORDS * 8));
-    HIPCK(tbMalloc(&E->r_meta, (2 * E->meta_cap + 1) * 8));
-    HIPCK(tbHostMalloc(&E->h_rmeta, (2 * E->meta_cap + 1) * 8, hipHostMallocDefault));
+    HIPCK(tbMalloc(E->own, &E->r_words, ROUTE_WORDS * 8));
+    HIPCK(tbMalloc(E->own, &E->r_meta, (2 * E->meta_cap + 1) * 8));
+    HIPCK(tbHostMalloc(E->own, &E->h_rmeta, (2 * E->meta_cap + 1) * 8, hipHostMallocDefault));
     return TBGPU_STATUS_OK;
 }
 
@@ -2794,9 +2822,10 @@ extern "C" int tbgpu_route_dependents(tbgpu_t* E, uint32_t nb, const uint32_t* l
     int st = route_meta(E, nb, nullptr, lens, &n);
     if (st) return st;
     if (n == 0) return TBGPU_STATUS_OK;
+    Owner scratch;
     u64* d_marked = nullptr;
     if (n_marked) {
-        HIPCK(tbMalloc(&d_marked, (u64)n_marked * 16));
+        HIPCK(tbMalloc(scratch, &d_marked, (u64)n_marked * 16));
         HIPCK(hipMemcpyAsync(d_marked, marked_ids, (u64)n_marked * 16, hipMemcpyHostToDevice, E->stream));
     }
     RouteArgs A{};
@@ -2809,7 +2838,6 @@ extern "C" int tbgpu_route_dependents(tbgpu_t* E, uint32_t nb, const uint32_t* l
                        E->stream, A, d_marked, n_marked, dep_dev);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(E->stream);
-    if (d_marked) (void)hipFree(d_marked);
     if (e != hipSuccess) return fail(TBGPU_STATUS_DEVICE, "route dependents: %s", hipGetErrorString(e));
     return TBGPU_STATUS_OK;
 }

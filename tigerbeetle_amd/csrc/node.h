@@ -71,7 +71,6 @@ struct NodeDev {
     u32* results = nullptr;      // the block's sparse replies (tb_node_replies)
     u32* reply_bytes = nullptr;
     // Home / owner side.
-    u8* recv = nullptr;
     u8* codes = nullptr;
     u64* legs = nullptr;
     u64* leg_counts = nullptr;
@@ -301,46 +300,23 @@ static void node_free(TbNode* N) {
                 (unsigned long long)N->t_calls, N->t_us[0] / c, N->t_us[1] / c, N->t_us[2] / c, N->t_us[3] / c,
                 N->t_us[4] / c, N->t_us[5] / c);
     }
+    // Every device drains before any shard is released: a shard's kernels read its peers' tables
+    // over xGMI (k_node.h), and the sequencer (on the first device) reads and is read by all of them.
     for (u32 d = 0; d < N->world; d++) {
-        NodeDev& D = N->D[d];
-        if (D.E) {
-            (void)hipSetDevice(D.device);
-            (void)hipDeviceSynchronize();
-        }
-        void* dev[] = {D.stage[0], D.stage[1], D.send[0], D.send[1], D.slot[0], D.slot[1], D.home[0], D.home[1],
-                       D.words[0], D.words[1], D.meta[0], D.meta[1], D.block_counts, D.results, D.reply_bytes,
-                       D.recv, D.codes, D.legs, D.leg_counts, D.hmeta_dev[0], D.hmeta_dev[1], D.hmeta_dev[2],
-                       D.dep1, D.dep[0], D.dep[1], D.dkeys, D.dbal, D.dcounts, D.keyset, D.markset, D.wb_count,
-                       D.imp_flag, D.imp_count, D.imp_os, D.limbits};
-        for (void* p : dev) if (p) (void)hipFree(p);
-        void* host[] = {D.h_words[0], D.h_words[1], D.h_meta[0], D.h_meta[1], D.hmeta_host[0], D.hmeta_host[1],
-                        D.hmeta_host[2], D.h_arena[0], D.h_arena[1], D.h_arena[2], D.h_dcounts, D.h_flags};
-        for (void* p : host) if (p) (void)hipHostFree(p);
-        hipEvent_t evs[] = {D.ev_start[0], D.ev_start[1], D.ev_start[2], D.ev_done[0], D.ev_done[1], D.ev_done[2],
-                            D.ev_planned[0], D.ev_planned[1], D.ev_copied, D.ev_gathered, D.ev_committed,
-                            D.ev_applied, D.ev_replied, D.ev_cls, D.ev_marked, D.ev_pre, D.ev_xwb};
-        for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
-        if (D.rs) (void)hipStreamDestroy(D.rs);
-        if (D.E) tbgpu_deinit(D.E);
+        if (!N->D[d].E) continue;
+        (void)hipSetDevice(N->D[d].device);
+        (void)hipDeviceSynchronize();
     }
-    if (N->X) {
-        (void)hipSetDevice(N->D[0].device);
-        void* dev[] = {N->tset_e, N->aset_e, N->tset_list, N->aset_list, N->seq_counts, N->tset_dups, N->aset_dups,
-                       N->seq_codes, N->seq_xcodes, N->seq_map, N->seq_ts, N->seq_blk, N->seq_bal0, N->xclr_list,
-                       N->xclr_count};
-        for (void* p : dev) if (p) (void)hipFree(p);
-        if (N->ev_xread) (void)hipEventDestroy(N->ev_xread);
-        if (N->ev_x) (void)hipEventDestroy(N->ev_x);
-        if (N->h_seq) (void)hipHostFree(N->h_seq);
-        tbgpu_deinit(N->X);
-    }
+    for (u32 d = 0; d < N->world; d++) tbgpu_deinit(N->D[d].E);  // with the node's resources on that shard
+    tbgpu_deinit(N->X);                                           // ... and the sequencer's
     delete N;
 }
 
 static u64 node_arena_bytes(const TbNode* N) { return 16 + (u64)N->pb_src * 4 + N->pe_src * 8; }
 
-static int node_init(const tbgpu_config* config, TbNode** out) {
-    *out = nullptr;
+// On a failure node_api_init frees the node: each engine made so far releases its owner, which holds
+// the node's resources on that shard (N->X's: the sequencer's).
+static int node_init(TbNode* N, const tbgpu_config* config) {
     const u32 W = config->device_count;
     if (W < 2 || W > NODE_WORLD_MAX) return fail(TBGPU_STATUS_INVALID, "device_count %u out of range (2..%u)", W, NODE_WORLD_MAX);
     int ndev = 0;
@@ -350,7 +326,6 @@ static int node_init(const tbgpu_config* config, TbNode** out) {
             return fail(TBGPU_STATUS_INVALID, "tbgpu_init: devices[%u] = %d out of range (%d devices)", d, config->devices[d], ndev);
         }
     }
-    TbNode* N = new TbNode();
     if (const char* t = getenv("TBGPU_NODE_TIMING")) N->timing = atoi(t) != 0;
     {
         const char* t = getenv("TBGPU_NODE_THREADS");
@@ -384,16 +359,11 @@ static int node_init(const tbgpu_config* config, TbNode** out) {
     const u64 owned = std::min<u64>(config->accounts_max, config->accounts_max / W + config->accounts_max / (8 * W) + 4096);
     const u64 import_room = std::min<u64>(config->accounts_max, 2 * (u64)sc.pass_events_max);
     sc.accounts_max = std::min<u64>(1ULL << 31, owned + import_room);
-    int st = TBGPU_STATUS_OK;
-    for (u32 d = 0; d < W && st == TBGPU_STATUS_OK; d++) {
+    for (u32 d = 0; d < W; d++) {
         NodeDev& D = N->D[d];
         D.device = config->devices[d];
         sc.device = D.device;
-        st = tbgpu_init(&sc, &D.E);
-    }
-    if (st) {
-        node_free(N);
-        return st;
+        if (const int st = tbgpu_init(&sc, &D.E)) return st;
     }
     // Peer access between distinct devices (a kernel on one reads the other's HBM over xGMI).
     for (u32 a = 0; a < W; a++) {
@@ -402,102 +372,88 @@ static int node_init(const tbgpu_config* config, TbNode** out) {
             if (da == db) continue;
             int can = 0;
             if (hipDeviceCanAccessPeer(&can, da, db) != hipSuccess || !can) {
-                node_free(N);
                 return fail(TBGPU_STATUS_DEVICE, "tbgpu_init: device %d cannot access device %d (no xGMI/P2P path)", da, db);
             }
             (void)hipSetDevice(da);
             const hipError_t e = hipDeviceEnablePeerAccess(db, 0);
-            if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) {
-                node_free(N);
-                return node_fail_dev("hipDeviceEnablePeerAccess", e);
-            }
+            if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) return node_fail_dev("hipDeviceEnablePeerAccess", e);
             (void)hipGetLastError();  // clear "already enabled"
         }
     }
     const u64 pe = N->pe_src, nblocks = (pe + ROUTE_THREADS - 1) / ROUTE_THREADS;
     const u64 legs_cap_total = (u64)W * 2 * N->recv_cap;  // W regions of up to 2 legs per received event
-    hipError_t e = hipSuccess;
-#define NALLOC(x) \
-    if (e == hipSuccess) e = (x)
-    for (u32 d = 0; d < W && e == hipSuccess; d++) {
+    for (u32 d = 0; d < W; d++) {
         NodeDev& D = N->D[d];
-        NALLOC(hipSetDevice(D.device));
-        NALLOC(hipStreamCreateWithFlags(&D.rs, hipStreamNonBlocking));
+        HIPCK(hipSetDevice(D.device));
+        HIPCK(tbStreamCreate(D.E->own, &D.rs));
         for (int k = 0; k < 2; k++) {
-            NALLOC(tbMalloc(&D.stage[k], pe * 128));
-            NALLOC(tbMalloc(&D.send[k], pe * 128));
-            NALLOC(tbMalloc(&D.slot[k], pe * 4));
-            NALLOC(tbMalloc(&D.home[k], pe));
-            NALLOC(tbMalloc(&D.words[k], ROUTE_WORDS * 8));
-            NALLOC(hipMemsetAsync(D.words[k], 0, ROUTE_WORDS * 8, D.rs));
-            NALLOC(tbHostMalloc(&D.h_words[k], ROUTE_WORDS * 8, hipHostMallocMapped));
-            if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&D.d_words_host[k], D.h_words[k], 0);
-            NALLOC(tbMalloc(&D.meta[k], (2 * (u64)N->pb_src + 1) * 8));
-            NALLOC(tbHostMalloc(&D.h_meta[k], (2 * (u64)N->pb_src + 1) * 8, hipHostMallocDefault));
-            NALLOC(tbEventCreateWithFlags(&D.ev_planned[k], hipEventDisableTiming));
+            HIPCK(tbMalloc(D.E->own, &D.stage[k], pe * 128));
+            HIPCK(tbMalloc(D.E->own, &D.send[k], pe * 128));
+            HIPCK(tbMalloc(D.E->own, &D.slot[k], pe * 4));
+            HIPCK(tbMalloc(D.E->own, &D.home[k], pe));
+            HIPCK(tbMalloc(D.E->own, &D.words[k], ROUTE_WORDS * 8));
+            HIPCK(hipMemsetAsync(D.words[k], 0, ROUTE_WORDS * 8, D.rs));
+            HIPCK(tbHostMalloc(D.E->own, &D.h_words[k], ROUTE_WORDS * 8, hipHostMallocMapped));
+            HIPCK(hipHostGetDevicePointer((void**)&D.d_words_host[k], D.h_words[k], 0));
+            HIPCK(tbMalloc(D.E->own, &D.meta[k], (2 * (u64)N->pb_src + 1) * 8));
+            HIPCK(tbHostMalloc(D.E->own, &D.h_meta[k], (2 * (u64)N->pb_src + 1) * 8, hipHostMallocDefault));
+            HIPCK(tbEventCreateWithFlags(D.E->own, &D.ev_planned[k], hipEventDisableTiming));
         }
-        NALLOC(tbMalloc(&D.block_counts, 2 * nblocks * W * 4));
-        NALLOC(tbMalloc(&D.results, pe * 8));
-        NALLOC(tbMalloc(&D.reply_bytes, (u64)N->pb_src * 4));
-        NALLOC(tbMalloc(&D.codes, N->recv_cap));
-        NALLOC(tbMalloc(&D.legs, legs_cap_total * NODE_LEG_WORDS * 8));
-        NALLOC(tbMalloc(&D.leg_counts, (u64)W * 8));
+        HIPCK(tbMalloc(D.E->own, &D.block_counts, 2 * nblocks * W * 4));
+        HIPCK(tbMalloc(D.E->own, &D.results, pe * 8));
+        HIPCK(tbMalloc(D.E->own, &D.reply_bytes, (u64)N->pb_src * 4));
+        HIPCK(tbMalloc(D.E->own, &D.codes, N->recv_cap));
+        HIPCK(tbMalloc(D.E->own, &D.legs, legs_cap_total * NODE_LEG_WORDS * 8));
+        HIPCK(tbMalloc(D.E->own, &D.leg_counts, (u64)W * 8));
         const u64 hm = 2 * ((N->recv_cap + BATCH_EVENTS_MAX - 2) / (BATCH_EVENTS_MAX - 1) + 2) + 1;
         for (int k = 0; k < 3; k++) {
-            NALLOC(tbMalloc(&D.hmeta_dev[k], hm * 8));
-            NALLOC(tbHostMalloc(&D.hmeta_host[k], hm * 8, hipHostMallocDefault));
-            NALLOC(tbHostMalloc(&D.h_arena[k], node_arena_bytes(N), hipHostMallocMapped));
-            if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&D.d_arena[k], D.h_arena[k], 0);
-            NALLOC(tbEventCreate(&D.ev_start[k]));
-            NALLOC(tbEventCreate(&D.ev_done[k]));
+            HIPCK(tbMalloc(D.E->own, &D.hmeta_dev[k], hm * 8));
+            HIPCK(tbHostMalloc(D.E->own, &D.hmeta_host[k], hm * 8, hipHostMallocDefault));
+            HIPCK(tbHostMalloc(D.E->own, &D.h_arena[k], node_arena_bytes(N), hipHostMallocMapped));
+            HIPCK(hipHostGetDevicePointer((void**)&D.d_arena[k], D.h_arena[k], 0));
+            HIPCK(tbEventCreate(D.E->own, &D.ev_start[k]));
+            HIPCK(tbEventCreate(D.E->own, &D.ev_done[k]));
         }
-        NALLOC(tbHostMalloc(&D.h_flags, 64, hipHostMallocMapped));
-        if (e == hipSuccess) {
-            memset(D.h_flags, 0, 64);
-            e = hipHostGetDevicePointer((void**)&D.d_flags, D.h_flags, 0);
-        }
-        NALLOC(tbEventCreateWithFlags(&D.ev_copied, hipEventDisableTiming));
-        NALLOC(tbEventCreateWithFlags(&D.ev_gathered, hipEventDisableTiming));
-        NALLOC(tbEventCreateWithFlags(&D.ev_committed, hipEventDisableTiming));
-        NALLOC(tbEventCreateWithFlags(&D.ev_applied, hipEventDisableTiming));
-        NALLOC(tbEventCreateWithFlags(&D.ev_replied, hipEventDisableTiming));
+        HIPCK(tbHostMalloc(D.E->own, &D.h_flags, 64, hipHostMallocMapped));
+        memset(D.h_flags, 0, 64);
+        HIPCK(hipHostGetDevicePointer((void**)&D.d_flags, D.h_flags, 0));
+        HIPCK(tbEventCreateWithFlags(D.E->own, &D.ev_copied, hipEventDisableTiming));
+        HIPCK(tbEventCreateWithFlags(D.E->own, &D.ev_gathered, hipEventDisableTiming));
+        HIPCK(tbEventCreateWithFlags(D.E->own, &D.ev_committed, hipEventDisableTiming));
+        HIPCK(tbEventCreateWithFlags(D.E->own, &D.ev_applied, hipEventDisableTiming));
+        HIPCK(tbEventCreateWithFlags(D.E->own, &D.ev_replied, hipEventDisableTiming));
         // The events of "the previous pass" exist before the first pass: record them once.
-        NALLOC(hipEventRecord(D.ev_gathered, D.E->stream));
-        NALLOC(hipEventRecord(D.ev_applied, D.E->stream));
-        NALLOC(hipEventRecord(D.ev_replied, D.E->stream));
+        HIPCK(hipEventRecord(D.ev_gathered, D.E->stream));
+        HIPCK(hipEventRecord(D.ev_applied, D.E->stream));
+        HIPCK(hipEventRecord(D.ev_replied, D.E->stream));
         // Dirty passes: the block's classification, the key sets (every source's keys), the
         // sequencer write-back counter.
         D.set_mask = pow2_at_least(std::max<u64>(1024, 4 * (u64)W * pe)) - 1;
-        NALLOC(tbMalloc(&D.dep1, pe));
-        NALLOC(tbMalloc(&D.dep[0], pe));
-        NALLOC(tbMalloc(&D.dep[1], pe));
-        NALLOC(tbMalloc(&D.dkeys, 2 * pe * 16));
-        NALLOC(tbMalloc(&D.dbal, 2 * pe * 16));
-        NALLOC(tbMalloc(&D.dcounts, NODE_DC_WORDS * 8));
-        NALLOC(tbHostMalloc(&D.h_dcounts, NODE_DC_WORDS * 8, hipHostMallocDefault));
-        NALLOC(tbMalloc(&D.keyset, (D.set_mask + 1) * 8));
-        NALLOC(tbMalloc(&D.markset, (D.set_mask + 1) * 8));
-        NALLOC(tbMalloc(&D.wb_count, 8));
-        NALLOC(tbEventCreateWithFlags(&D.ev_cls, hipEventDisableTiming));
-        NALLOC(tbEventCreateWithFlags(&D.ev_marked, hipEventDisableTiming));
-        NALLOC(tbEventCreateWithFlags(&D.ev_pre, hipEventDisableTiming));
-        NALLOC(tbEventCreateWithFlags(&D.ev_xwb, hipEventDisableTiming));
+        HIPCK(tbMalloc(D.E->own, &D.dep1, pe));
+        HIPCK(tbMalloc(D.E->own, &D.dep[0], pe));
+        HIPCK(tbMalloc(D.E->own, &D.dep[1], pe));
+        HIPCK(tbMalloc(D.E->own, &D.dkeys, 2 * pe * 16));
+        HIPCK(tbMalloc(D.E->own, &D.dbal, 2 * pe * 16));
+        HIPCK(tbMalloc(D.E->own, &D.dcounts, NODE_DC_WORDS * 8));
+        HIPCK(tbHostMalloc(D.E->own, &D.h_dcounts, NODE_DC_WORDS * 8, hipHostMallocDefault));
+        HIPCK(tbMalloc(D.E->own, &D.keyset, (D.set_mask + 1) * 8));
+        HIPCK(tbMalloc(D.E->own, &D.markset, (D.set_mask + 1) * 8));
+        HIPCK(tbMalloc(D.E->own, &D.wb_count, 8));
+        HIPCK(tbEventCreateWithFlags(D.E->own, &D.ev_cls, hipEventDisableTiming));
+        HIPCK(tbEventCreateWithFlags(D.E->own, &D.ev_marked, hipEventDisableTiming));
+        HIPCK(tbEventCreateWithFlags(D.E->own, &D.ev_pre, hipEventDisableTiming));
+        HIPCK(tbEventCreateWithFlags(D.E->own, &D.ev_xwb, hipEventDisableTiming));
         D.imp_cap = import_room;
-        NALLOC(tbMalloc(&D.imp_flag, 4));
-        NALLOC(tbMalloc(&D.imp_count, 8));
-        NALLOC(hipMemset(D.imp_count, 0, 8));
-        NALLOC(tbMalloc(&D.imp_os, D.E->account_cap * 4));
+        HIPCK(tbMalloc(D.E->own, &D.imp_flag, 4));
+        HIPCK(tbMalloc(D.E->own, &D.imp_count, 8));
+        HIPCK(hipMemset(D.imp_count, 0, 8));
+        HIPCK(tbMalloc(D.E->own, &D.imp_os, D.E->account_cap * 4));
         // 16 bits per account of the ledger: a false positive (which only sequences an event) is at
         // most 1 in 16 even when every account is limited.
         const u64 lim_bits = std::min<u64>(1ULL << 34, pow2_at_least(std::max<u64>(1ULL << 16, 16 * config->accounts_max)));
         D.limmask = lim_bits - 1;
-        NALLOC(tbMalloc(&D.limbits, lim_bits / 8));
-        NALLOC(hipMemset(D.limbits, 0, lim_bits / 8));
-    }
-#undef NALLOC
-    if (e != hipSuccess) {
-        node_free(N);
-        return node_fail_dev("tbgpu_init (node buffers)", e);
+        HIPCK(tbMalloc(D.E->own, &D.limbits, lim_bits / 8));
+        HIPCK(hipMemset(D.limbits, 0, lim_bits / 8));
     }
     // The sequencer: one whole pass (every source's block) with the objects it can read — two
     // transfers (id, pending id) and up to four accounts per event.
@@ -511,11 +467,7 @@ static int node_init(const tbgpu_config* config, TbNode** out) {
         xc.transfers_max = N->seq_tcap + pass;
         xc.pass_events_max = (u32)std::min<u64>(pass, 0xFFFFFFFFull);
         xc.pass_batches_max = W * N->pb_src;
-        int st2 = tbgpu_init(&xc, &N->X);
-        if (st2) {
-            node_free(N);
-            return st2;
-        }
+        if (const int st = tbgpu_init(&xc, &N->X)) return st;
         // The sequencer's passes are the dependent events of a node pass: a tenth to a quarter of it
         // in C3 / C4, Zipf-hot.  Balance legs (per-account LDS sums) from 8K events on: below the
         // single engine's threshold, atomics on the hot accounts would serialise.
@@ -523,37 +475,29 @@ static int node_init(const tbgpu_config* config, TbNode** out) {
         (void)hipSetDevice(N->D[0].device);
         N->tset_mask = pow2_at_least(4 * pass) - 1;
         N->aset_mask = pow2_at_least(2 * (xc.accounts_max + 2 * pass)) - 1;
-#define XALLOC(x) \
-    if (e == hipSuccess) e = (x)
-        XALLOC(tbMalloc(&N->tset_e, (N->tset_mask + 1) * sizeof(SeqEntry)));
-        XALLOC(tbMalloc(&N->aset_e, (N->aset_mask + 1) * sizeof(SeqEntry)));
-        XALLOC(tbMalloc(&N->tset_list, 2 * pass * 4));
-        XALLOC(tbMalloc(&N->aset_list, 6 * pass * 4));
-        XALLOC(tbMalloc(&N->seq_counts, 8 * 8));
-        XALLOC(tbMalloc(&N->tset_dups, 2 * pass * 24));
-        XALLOC(tbMalloc(&N->aset_dups, 6 * pass * 24));
-        XALLOC(tbMalloc(&N->seq_codes, pass));
-        XALLOC(tbMalloc(&N->seq_xcodes, pass));
-        XALLOC(tbMalloc(&N->seq_map, pass * 4));
-        XALLOC(tbMalloc(&N->seq_ts, pass * 8));
-        XALLOC(tbMalloc(&N->seq_blk, (pass / 256 + 2) * 4));
-        XALLOC(tbMalloc(&N->seq_bal0, 6 * pass * sizeof(AccountBal)));
+        HIPCK(tbMalloc(N->X->own, &N->tset_e, (N->tset_mask + 1) * sizeof(SeqEntry)));
+        HIPCK(tbMalloc(N->X->own, &N->aset_e, (N->aset_mask + 1) * sizeof(SeqEntry)));
+        HIPCK(tbMalloc(N->X->own, &N->tset_list, 2 * pass * 4));
+        HIPCK(tbMalloc(N->X->own, &N->aset_list, 6 * pass * 4));
+        HIPCK(tbMalloc(N->X->own, &N->seq_counts, 8 * 8));
+        HIPCK(tbMalloc(N->X->own, &N->tset_dups, 2 * pass * 24));
+        HIPCK(tbMalloc(N->X->own, &N->aset_dups, 6 * pass * 24));
+        HIPCK(tbMalloc(N->X->own, &N->seq_codes, pass));
+        HIPCK(tbMalloc(N->X->own, &N->seq_xcodes, pass));
+        HIPCK(tbMalloc(N->X->own, &N->seq_map, pass * 4));
+        HIPCK(tbMalloc(N->X->own, &N->seq_ts, pass * 8));
+        HIPCK(tbMalloc(N->X->own, &N->seq_blk, (pass / 256 + 2) * 4));
+        HIPCK(tbMalloc(N->X->own, &N->seq_bal0, 6 * pass * sizeof(AccountBal)));
         N->xclr_cap = 2 * (N->seq_tcap + pass);  // two entries per log position (a withdrawn claim and a new one)
-        XALLOC(tbMalloc(&N->xclr_list, N->xclr_cap * 4));
-        XALLOC(tbMalloc(&N->xclr_count, 8));
-        XALLOC(tbEventCreateWithFlags(&N->ev_xread, hipEventDisableTiming));
-        XALLOC(tbEventCreateWithFlags(&N->ev_x, hipEventDisableTiming));
-        XALLOC(hipEventRecord(N->ev_xread, N->X->stream));  // "the previous split pass" exists before the first
-        XALLOC(tbHostMalloc(&N->h_seq, 16 * 8, hipHostMallocDefault));
-        XALLOC(hipMemset(N->tset_e, 0, (N->tset_mask + 1) * sizeof(SeqEntry)));
-        XALLOC(hipMemset(N->aset_e, 0, (N->aset_mask + 1) * sizeof(SeqEntry)));
-#undef XALLOC
-        if (e != hipSuccess) {
-            node_free(N);
-            return node_fail_dev("tbgpu_init (node sequencer)", e);
-        }
+        HIPCK(tbMalloc(N->X->own, &N->xclr_list, N->xclr_cap * 4));
+        HIPCK(tbMalloc(N->X->own, &N->xclr_count, 8));
+        HIPCK(tbEventCreateWithFlags(N->X->own, &N->ev_xread, hipEventDisableTiming));
+        HIPCK(tbEventCreateWithFlags(N->X->own, &N->ev_x, hipEventDisableTiming));
+        HIPCK(hipEventRecord(N->ev_xread, N->X->stream));  // "the previous split pass" exists before the first
+        HIPCK(tbHostMalloc(N->X->own, &N->h_seq, 16 * 8, hipHostMallocDefault));
+        HIPCK(hipMemset(N->tset_e, 0, (N->tset_mask + 1) * sizeof(SeqEntry)));
+        HIPCK(hipMemset(N->aset_e, 0, (N->aset_mask + 1) * sizeof(SeqEntry)));
     }
-    *out = N;
     return TBGPU_STATUS_OK;
 }
 
@@ -1712,9 +1656,11 @@ static int node_lookup(TbNode* N, bool accounts, const void* input, u32 input_le
 // -- the tbgpu.h entry points of a node engine --------------------------------------------------------
 
 static int node_api_init(const tbgpu_config* config, tbgpu_t** out) {
-    TbNode* N = nullptr;
-    const int st = node_init(config, &N);
-    if (st) return st;
+    TbNode* N = new TbNode();
+    if (const int st = node_init(N, config)) {
+        node_free(N);
+        return st;
+    }
     tbgpu* E = new tbgpu();
     E->cfg = *config;
     E->node = N;

@@ -64,8 +64,8 @@ struct AccountQueryBufs {
 #define QA_STATE_BYTES ((u64)QA_WORDS * 8 + (u64)QA_PASSES * QA_BINS * 4)
 
 // tbgpu_get_change_events (k_change_events.h): the page's account set, the bins, the accounts' records
-// and the post rows' pending amounts, on the device and pinned; made at tbgpu_init after every other
-// buffer and shared with nothing.  The rows themselves are chosen through QueryBufs.
+// and the post rows' pending amounts, on the device and pinned; made by query_init and shared with
+// nothing.  The rows themselves are chosen through QueryBufs.
 struct ChangeBufs {
     u32* d_set = nullptr;     // [CHANGE_SET_SLOTS_MAX] the set's entries
     u64* d_ids = nullptr;     // [CHANGE_ACCOUNTS_MAX][2] the accounts' ids by index
@@ -88,7 +88,7 @@ struct ChangeBufs {
 };
 
 // tbgpu_get_account_transfers_many (k_query_many.h): the filter set, per-chunk counts, bases and bounds,
-// the totals and the answer area; made at tbgpu_init after every other buffer and shared with nothing.
+// the totals and the answer area; made by query_init and shared with nothing.
 // Every word a query reads is a word it wrote, so tbgpu_reset clears none of them.
 #define QUERY_MANY_CHUNKS_MIN 4096u  // room for this many chunks whatever the log: a test's shrunk chunks
 #define QUERY_MANY_STAGE (1u << 15)  // records of one copy to the host (4 MiB)
@@ -119,120 +119,87 @@ struct QueryState {
     QueryManyBufs qm;
 };
 
-// Called by tbgpu_init on the engine's device, after every other buffer; tbgpu_deinit calls query_free
-// whether or not query_init finished.
+// Called by engine_init on the engine's device, after every other buffer.  The buffers go into the
+// engine's owner, which releases as many as were made; query_free deletes the host struct only.
 static int query_init(tbgpu* E) {
-#define QINIT_CK(x)                                                                      \
-    do {                                                                                 \
-        const hipError_t e_ = (x);                                                       \
-        if (e_ != hipSuccess) return fail(TBGPU_STATUS_DEVICE, "%s: %s", #x, hipGetErrorString(e_)); \
-    } while (0)
     E->qs = new QueryState();
     {  // the log scan: per-tile counts and bounds, the answer, the unordered path's keys
         QueryBufs& Q = E->qs->q;
         Q.nb_cap = (E->xlog_cap + QUERY_THREADS - 1) / QUERY_THREADS;
-        QINIT_CK(tbMalloc(&Q.d_counts, Q.nb_cap * 4));
-        QINIT_CK(tbMalloc(&Q.d_mins, Q.nb_cap * 8));
-        QINIT_CK(tbMalloc(&Q.d_maxs, Q.nb_cap * 8));
-        QINIT_CK(tbMalloc(&Q.d_ordered, Q.nb_cap * 4));
-        QINIT_CK(tbMalloc(&Q.d_base, Q.nb_cap * 8));
-        QINIT_CK(tbMalloc(&Q.d_res, 16));
-        QINIT_CK(tbHostMalloc(&Q.h_res, 16, hipHostMallocDefault));
-        QINIT_CK(tbMalloc(&Q.d_out, (u64)BATCH_EVENTS_MAX * 128));
-        QINIT_CK(tbMalloc(&Q.d_keys, (u64)QUERY_KEYS_CAP * 16));
-        QINIT_CK(tbHostMalloc(&Q.h_keys, (u64)QUERY_KEYS_CAP * 16, hipHostMallocDefault));
-        QINIT_CK(tbHostMalloc(&Q.h_base, (Q.nb_cap + 1) * 8, hipHostMallocDefault));
+        HIPCK(tbMalloc(E->own, &Q.d_counts, Q.nb_cap * 4));
+        HIPCK(tbMalloc(E->own, &Q.d_mins, Q.nb_cap * 8));
+        HIPCK(tbMalloc(E->own, &Q.d_maxs, Q.nb_cap * 8));
+        HIPCK(tbMalloc(E->own, &Q.d_ordered, Q.nb_cap * 4));
+        HIPCK(tbMalloc(E->own, &Q.d_base, Q.nb_cap * 8));
+        HIPCK(tbMalloc(E->own, &Q.d_res, 16));
+        HIPCK(tbHostMalloc(E->own, &Q.h_res, 16, hipHostMallocDefault));
+        HIPCK(tbMalloc(E->own, &Q.d_out, (u64)BATCH_EVENTS_MAX * 128));
+        HIPCK(tbMalloc(E->own, &Q.d_keys, (u64)QUERY_KEYS_CAP * 16));
+        HIPCK(tbHostMalloc(E->own, &Q.h_keys, (u64)QUERY_KEYS_CAP * 16, hipHostMallocDefault));
+        HIPCK(tbHostMalloc(E->own, &Q.h_base, (Q.nb_cap + 1) * 8, hipHostMallocDefault));
         if (const char* v = getenv("TBGPU_QUERY_COOP")) Q.coop = atoi(v) != 0;  // the load-shape measurement
     }
     {  // tbgpu_get_account_balances: the rows' timestamps and the bins
         BalanceBufs& B = E->qs->qb;
-        QINIT_CK(tbMalloc(&B.d_ts, (u64)BATCH_EVENTS_MAX * 8));
-        QINIT_CK(tbHostMalloc(&B.h_ts, (u64)BATCH_EVENTS_MAX * 8, hipHostMallocDefault));
-        QINIT_CK(tbMalloc(&B.d_bins, BALANCE_SLOTS(BATCH_EVENTS_MAX) * BALANCE_SLOT_WORDS * 8));
-        QINIT_CK(tbHostMalloc(&B.h_bins, BALANCE_SLOTS(BATCH_EVENTS_MAX) * BALANCE_SLOT_WORDS * 8, hipHostMallocDefault));
+        HIPCK(tbMalloc(E->own, &B.d_ts, (u64)BATCH_EVENTS_MAX * 8));
+        HIPCK(tbHostMalloc(E->own, &B.h_ts, (u64)BATCH_EVENTS_MAX * 8, hipHostMallocDefault));
+        HIPCK(tbMalloc(E->own, &B.d_bins, BALANCE_SLOTS(BATCH_EVENTS_MAX) * BALANCE_SLOT_WORDS * 8));
+        HIPCK(tbHostMalloc(E->own, &B.h_bins, BALANCE_SLOTS(BATCH_EVENTS_MAX) * BALANCE_SLOT_WORDS * 8, hipHostMallocDefault));
     }
     {  // tbgpu_query_accounts: per-tile counts and bounds, the select's state and histograms, keys, the answer
         AccountQueryBufs& A = E->qs->qa;
         A.nb = (E->account_cap + QUERY_THREADS - 1) / QUERY_THREADS;
-        QINIT_CK(tbMalloc(&A.d_counts, A.nb * 4));
-        QINIT_CK(tbMalloc(&A.d_mins, A.nb * 8));
-        QINIT_CK(tbMalloc(&A.d_maxs, A.nb * 8));
-        QINIT_CK(tbMalloc(&A.d_state, QA_STATE_BYTES));
-        QINIT_CK(tbHostMalloc(&A.h_state, (u64)QA_WORDS * 8, hipHostMallocDefault));
-        QINIT_CK(tbMalloc(&A.d_keys, (u64)BATCH_EVENTS_MAX * 16));
-        QINIT_CK(tbMalloc(&A.d_out, (u64)BATCH_EVENTS_MAX * 128));
+        HIPCK(tbMalloc(E->own, &A.d_counts, A.nb * 4));
+        HIPCK(tbMalloc(E->own, &A.d_mins, A.nb * 8));
+        HIPCK(tbMalloc(E->own, &A.d_maxs, A.nb * 8));
+        HIPCK(tbMalloc(E->own, &A.d_state, QA_STATE_BYTES));
+        HIPCK(tbHostMalloc(E->own, &A.h_state, (u64)QA_WORDS * 8, hipHostMallocDefault));
+        HIPCK(tbMalloc(E->own, &A.d_keys, (u64)BATCH_EVENTS_MAX * 16));
+        HIPCK(tbMalloc(E->own, &A.d_out, (u64)BATCH_EVENTS_MAX * 128));
     }
     {  // tbgpu_get_change_events: the set, the bins, the accounts, the pending amounts, the rows
         ChangeBufs& C = E->qs->qc;
         const u64 na = CHANGE_ACCOUNTS_MAX, nr = CHANGE_EVENTS_MAX;
-        QINIT_CK(tbMalloc(&C.d_set, (u64)CHANGE_SET_SLOTS_MAX * 4));
-        QINIT_CK(tbMalloc(&C.d_ids, na * 16));
-        QINIT_CK(tbMalloc(&C.d_pids, nr * 16));
-        QINIT_CK(tbMalloc(&C.d_bins, (na + 1) * BALANCE_SLOT_WORDS * 8));
-        QINIT_CK(tbMalloc(&C.d_accounts, na * 128));
-        QINIT_CK(tbMalloc(&C.d_found, na * 4));
-        QINIT_CK(tbMalloc(&C.d_p, nr * 16));
-        QINIT_CK(tbMalloc(&C.d_found_p, nr * 4));
-        QINIT_CK(tbHostMalloc(&C.h_set, (u64)CHANGE_SET_SLOTS_MAX * 4, hipHostMallocDefault));
-        QINIT_CK(tbHostMalloc(&C.h_ids, na * 16, hipHostMallocDefault));
-        QINIT_CK(tbHostMalloc(&C.h_pids, nr * 16, hipHostMallocDefault));
-        QINIT_CK(tbHostMalloc(&C.h_bins, (na + 1) * BALANCE_SLOT_WORDS * 8, hipHostMallocDefault));
-        QINIT_CK(tbHostMalloc(&C.h_accounts, na * 128, hipHostMallocDefault));
-        QINIT_CK(tbHostMalloc(&C.h_found, na * 4, hipHostMallocDefault));
-        QINIT_CK(tbHostMalloc(&C.h_p, nr * 16, hipHostMallocDefault));
-        QINIT_CK(tbHostMalloc(&C.h_found_p, nr * 4, hipHostMallocDefault));
-        QINIT_CK(tbHostMalloc(&C.h_rows, nr * 128, hipHostMallocDefault));
-        QINIT_CK(tbHostMalloc(&C.h_row_idx, nr * 8, hipHostMallocDefault));
+        HIPCK(tbMalloc(E->own, &C.d_set, (u64)CHANGE_SET_SLOTS_MAX * 4));
+        HIPCK(tbMalloc(E->own, &C.d_ids, na * 16));
+        HIPCK(tbMalloc(E->own, &C.d_pids, nr * 16));
+        HIPCK(tbMalloc(E->own, &C.d_bins, (na + 1) * BALANCE_SLOT_WORDS * 8));
+        HIPCK(tbMalloc(E->own, &C.d_accounts, na * 128));
+        HIPCK(tbMalloc(E->own, &C.d_found, na * 4));
+        HIPCK(tbMalloc(E->own, &C.d_p, nr * 16));
+        HIPCK(tbMalloc(E->own, &C.d_found_p, nr * 4));
+        HIPCK(tbHostMalloc(E->own, &C.h_set, (u64)CHANGE_SET_SLOTS_MAX * 4, hipHostMallocDefault));
+        HIPCK(tbHostMalloc(E->own, &C.h_ids, na * 16, hipHostMallocDefault));
+        HIPCK(tbHostMalloc(E->own, &C.h_pids, nr * 16, hipHostMallocDefault));
+        HIPCK(tbHostMalloc(E->own, &C.h_bins, (na + 1) * BALANCE_SLOT_WORDS * 8, hipHostMallocDefault));
+        HIPCK(tbHostMalloc(E->own, &C.h_accounts, na * 128, hipHostMallocDefault));
+        HIPCK(tbHostMalloc(E->own, &C.h_found, na * 4, hipHostMallocDefault));
+        HIPCK(tbHostMalloc(E->own, &C.h_p, nr * 16, hipHostMallocDefault));
+        HIPCK(tbHostMalloc(E->own, &C.h_found_p, nr * 4, hipHostMallocDefault));
+        HIPCK(tbHostMalloc(E->own, &C.h_rows, nr * 128, hipHostMallocDefault));
+        HIPCK(tbHostMalloc(E->own, &C.h_row_idx, nr * 8, hipHostMallocDefault));
     }
     {  // tbgpu_get_account_transfers_many: the set, per-chunk counts, bases and bounds, the totals, the answers
         QueryManyBufs& M = E->qs->qm;
         const u64 nb_cap = E->qs->q.nb_cap;
         M.nc_cap = std::max<u64>((nb_cap + QUERY_MANY_TILES - 1) / QUERY_MANY_TILES, std::min<u64>(nb_cap, QUERY_MANY_CHUNKS_MIN));
-        QINIT_CK(tbMalloc(&M.d_tab, sizeof(QueryManyTable)));
-        QINIT_CK(tbHostMalloc(&M.h_tab, sizeof(QueryManyTable), hipHostMallocDefault));
-        QINIT_CK(tbMalloc(&M.d_counts, M.nc_cap * QUERY_MANY_FILTERS * 4));
-        QINIT_CK(tbMalloc(&M.d_base, M.nc_cap * QUERY_MANY_FILTERS * 4));
-        QINIT_CK(tbMalloc(&M.d_cmin, M.nc_cap * 8));
-        QINIT_CK(tbMalloc(&M.d_cmax, M.nc_cap * 8));
-        QINIT_CK(tbMalloc(&M.d_cord, M.nc_cap * 4));
-        QINIT_CK(tbMalloc(&M.d_ctiles, M.nc_cap * 8));
-        QINIT_CK(tbMalloc(&M.d_res, QM_RES_WORDS * 8));
-        QINIT_CK(tbHostMalloc(&M.h_res, QM_RES_WORDS * 8, hipHostMallocDefault));
-        QINIT_CK(tbHostMalloc(&M.h_stage, (u64)QUERY_MANY_STAGE * 128, hipHostMallocDefault));
-        QINIT_CK(tbMalloc(&M.d_out, (u64)QUERY_MANY_FILTERS * BATCH_EVENTS_MAX * 128));
+        HIPCK(tbMalloc(E->own, &M.d_tab, sizeof(QueryManyTable)));
+        HIPCK(tbHostMalloc(E->own, &M.h_tab, sizeof(QueryManyTable), hipHostMallocDefault));
+        HIPCK(tbMalloc(E->own, &M.d_counts, M.nc_cap * QUERY_MANY_FILTERS * 4));
+        HIPCK(tbMalloc(E->own, &M.d_base, M.nc_cap * QUERY_MANY_FILTERS * 4));
+        HIPCK(tbMalloc(E->own, &M.d_cmin, M.nc_cap * 8));
+        HIPCK(tbMalloc(E->own, &M.d_cmax, M.nc_cap * 8));
+        HIPCK(tbMalloc(E->own, &M.d_cord, M.nc_cap * 4));
+        HIPCK(tbMalloc(E->own, &M.d_ctiles, M.nc_cap * 8));
+        HIPCK(tbMalloc(E->own, &M.d_res, QM_RES_WORDS * 8));
+        HIPCK(tbHostMalloc(E->own, &M.h_res, QM_RES_WORDS * 8, hipHostMallocDefault));
+        HIPCK(tbHostMalloc(E->own, &M.h_stage, (u64)QUERY_MANY_STAGE * 128, hipHostMallocDefault));
+        HIPCK(tbMalloc(E->own, &M.d_out, (u64)QUERY_MANY_FILTERS * BATCH_EVENTS_MAX * 128));
     }
-#undef QINIT_CK
     return TBGPU_STATUS_OK;
 }
 
-static void query_free(tbgpu* E) {
-    if (!E->qs) return;
-    const QueryBufs& Q = E->qs->q;
-    const BalanceBufs& B = E->qs->qb;
-    const AccountQueryBufs& A = E->qs->qa;
-    const ChangeBufs& C = E->qs->qc;
-    const QueryManyBufs& M = E->qs->qm;
-    for (void* p : {(void*)M.d_tab, (void*)M.d_counts, (void*)M.d_base, (void*)M.d_cmin, (void*)M.d_cmax, (void*)M.d_cord,
-                    (void*)M.d_ctiles, (void*)M.d_res, (void*)M.d_out}) {
-        if (p) (void)hipFree(p);
-    }
-    for (void* p : {(void*)M.h_tab, (void*)M.h_res, (void*)M.h_stage}) {
-        if (p) (void)hipHostFree(p);
-    }
-    for (void* p : {(void*)Q.d_counts, (void*)Q.d_mins, (void*)Q.d_maxs, (void*)Q.d_ordered, (void*)Q.d_base, (void*)Q.d_res,
-                    (void*)Q.d_out, (void*)Q.d_keys, (void*)B.d_ts, (void*)B.d_bins, (void*)A.d_counts, (void*)A.d_mins,
-                    (void*)A.d_maxs, (void*)A.d_state, (void*)A.d_keys, (void*)A.d_out, (void*)C.d_set, (void*)C.d_ids,
-                    (void*)C.d_pids, (void*)C.d_bins, (void*)C.d_accounts, (void*)C.d_found, (void*)C.d_p, (void*)C.d_found_p}) {
-        if (p) (void)hipFree(p);
-    }
-    for (void* p : {(void*)Q.h_res, (void*)Q.h_keys, (void*)Q.h_base, (void*)B.h_ts, (void*)B.h_bins, (void*)A.h_state,
-                    (void*)C.h_set, (void*)C.h_ids, (void*)C.h_pids, (void*)C.h_bins, (void*)C.h_accounts, (void*)C.h_found,
-                    (void*)C.h_p, (void*)C.h_found_p, (void*)C.h_rows, (void*)C.h_row_idx}) {
-        if (p) (void)hipHostFree(p);
-    }
-    delete E->qs;
-    E->qs = nullptr;
-}
+static void query_free(tbgpu* E) { delete E->qs; }
 
 // ---- the engine list and what every entry point does first and last --------------------------------
 struct QueryCall {
@@ -241,9 +208,21 @@ struct QueryCall {
     u32 k = 0;                  // records asked for: the filter's limit under the caller's room and k_max
 };
 
+// Lists the engines a query asks: the engine itself, or a node's shards.  Returns `complete`: of a log
+// query (`evictable`), 1 while no listed engine has evicted a transfer; of the account table, always 1
+// (accounts are never evicted).
+static u32 query_engines(tbgpu* E, bool evictable, QueryCall* c) {
+    u32 complete = 1;
+    c->world = E->node ? node_world(E->node) : 1;
+    for (u32 d = 0; d < c->world; d++) {
+        c->Es[d] = E->node ? node_engine(E->node, d) : E;
+        if (evictable && c->Es[d]->evicted_total) complete = 0;
+    }
+    return complete;
+}
+
 // A read: legal on a stopped engine, like the exports.  Zeroes `result`, lists the engines and sets
-// `complete`: of a log query (`evictable`), 1 while no listed engine has evicted a transfer; of the
-// account table, always 1 (accounts are never evicted).
+// `complete`.
 template <typename FILTER>
 static int query_begin(tbgpu* E, const char* name, const FILTER* filter, const void* out, u32 out_cap, u32 k_max,
                        bool evictable, tbgpu_query_result* result, QueryCall* c) {
@@ -251,12 +230,7 @@ static int query_begin(tbgpu* E, const char* name, const FILTER* filter, const v
     if (!filter || !out || !result) return fail(TBGPU_STATUS_INVALID, "%s: a NULL filter, out or result", name);
     result->count = 0;
     result->matched = 0;
-    result->complete = 1;
-    c->world = E->node ? node_world(E->node) : 1;
-    for (u32 d = 0; d < c->world; d++) {
-        c->Es[d] = E->node ? node_engine(E->node, d) : E;
-        if (evictable && c->Es[d]->evicted_total) result->complete = 0;
-    }
+    result->complete = query_engines(E, evictable, c);
     c->k = std::min<u32>(std::min<u32>(filter->limit, out_cap), k_max);  // one reply is one message body
     return TBGPU_STATUS_OK;
 }
@@ -635,12 +609,7 @@ extern "C" int tbgpu_get_account_transfers_many(tbgpu_t* E, const tbgpu_account_
     if (n_filters == 0) return TBGPU_STATUS_OK;
     if (!filters || !out || !results) return fail(TBGPU_STATUS_INVALID, "get_account_transfers_many: NULL filters, out or results");
     QueryCall c;
-    c.world = E->node ? node_world(E->node) : 1;
-    u32 complete = 1;
-    for (u32 d = 0; d < c.world; d++) {
-        c.Es[d] = E->node ? node_engine(E->node, d) : E;
-        if (c.Es[d]->evicted_total) complete = 0;
-    }
+    const u32 complete = query_engines(E, true, &c);
     QueryManyCall C;
     C.nf = n_filters;
     C.filters = filters;
