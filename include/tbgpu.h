@@ -22,6 +22,7 @@
  *   (later references: the account_balances groove)        tbgpu_get_account_balances (likewise;
  *                                                             derived from the log, nothing stored)
  *   (later references: get_change_events)                  tbgpu_get_change_events (likewise)
+ *   (no reference: accounts as of a timestamp)             tbgpu_lookup_accounts_at (likewise)
  *   `setup` action of the table tests (:1398-1407)         tbgpu_test_set_balances (test only)
  *   StateMachine.commit_timestamp field (:251)             tbgpu_commit_timestamp
  *
@@ -510,6 +511,50 @@ typedef struct tbgpu_change_event {           /* 384 bytes, no padding */
 
 int tbgpu_get_change_events(tbgpu_t* engine, const tbgpu_change_events_filter* filter, void* out,
                             uint32_t out_cap_events, tbgpu_query_result* result);
+
+/* lookup_accounts_at: the records of the accounts the caller names, as they stood at a timestamp the
+ * caller names — what a statement run, an end-of-day close or a reconciliation starts from.  No
+ * reference has an operation for it; this engine stores nothing at commit and derives the balances
+ * from the log in HBM and the current balances, as tbgpu_get_change_events does for the accounts of a
+ * page.  One scan of the log answers the call, whatever the number of ids.  An entry point of its own,
+ * as above; this comment is its specification.
+ *   Which records: lookup_accounts' — one 128-byte record per requested id that the account table
+ *     holds, in request order.  Absent ids and the reserved ids (0, 2^128-1) are skipped; a repeated
+ *     id is answered once per occurrence.  An account whose own timestamp is above `timestamp` did
+ *     not exist then and is skipped like an absent one.  `matched` is the number of ids that yield a
+ *     record; count = min(matched, out_cap_records), the first ones in request order; bytes past
+ *     count records are not written.
+ *   What a record holds: the account's current record with its four balances replaced by
+ *       balance_at(a, T) = current(a) - the sum of the effects on a of every live resident record
+ *                          that names a and has a timestamp strictly above T,
+ *     per column modulo 2^128, with the effect table, the P rule and the liveness rule of
+ *     tbgpu_get_account_balances (a post whose pending transfer is not resident is summed with P =
+ *     its own amount).  The anchor is the current balance: the answers stay exact after eviction of
+ *     an old prefix, after tbgpu_load_accounts and after tbgpu_test_set_balances; timestamps older
+ *     than such a step follow this definition, not the ledger's past.
+ *   timestamp == 0 means now: the answer is byte-identical to tbgpu_commit(operation 130) for the
+ *     same ids, and no log is scanned.  A timestamp at or above every resident record's gives the same
+ *     bytes, except for accounts loaded with a later timestamp, which the rule above skips; its scan
+ *     reads the records' timestamps and nothing else.
+ *   complete: 1 only when no transfer was ever evicted (any shard) and every post that entered a sum
+ *     found its pending transfer resident; otherwise 0.
+ *   timestamp == 2^64-1 returns TBGPU_STATUS_OK with count = matched = 0.  n == 0 returns
+ *     TBGPU_STATUS_OK and writes nothing.  n > TBGPU_LOOKUP_AT_MAX, or a NULL ids, out or result with
+ *     n > 0, is TBGPU_STATUS_INVALID and writes nothing.  After any failing status the result names
+ *     no record.
+ *   The call contract of tbgpu_get_account_transfers: synchronous, drains a pending
+ *     tbgpu_commit_device_async first, a read that changes nothing (commit_timestamp, balances, log,
+ *     index, stats, the write-back snapshot), works on an engine a device panic stopped, allocates
+ *     nothing after tbgpu_init, legal beside an asynchronous write-back.
+ *   A node engine has the same contract: every home shard scans its own log on its own device and
+ *     stream, side by side, reading a post's pending transfer on the home shard of its pending_id;
+ *     each account's record, and whether it existed at T, come from its owner shard only; the host
+ *     adds the shards' sums. */
+#define TBGPU_LOOKUP_AT_MAX 8191u   /* one lookup_accounts body */
+int tbgpu_lookup_accounts_at(tbgpu_t* engine, uint64_t timestamp,
+                             const void* ids /* n x {lo, hi} */, uint32_t n,
+                             void* out, uint32_t out_cap_records,
+                             tbgpu_query_result* result);
 
 /* The replica writes StateMachine.commit_timestamp itself: the header timestamp after every commit
  * (src/vsr/replica.zig:3664-3665) and the checkpoint's value on open / state sync.  The wrapper

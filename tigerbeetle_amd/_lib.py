@@ -199,6 +199,7 @@ SIGNATURES = [
     ("tbgpu_bench_query_many_tiles", ctypes.c_int, [_P, _U32]),
     ("tbgpu_get_account_balances", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_get_change_events", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
+    ("tbgpu_lookup_accounts_at", ctypes.c_int, [_P, _U64, _P, _U32, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_query_transfers", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_query_accounts", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_bench_query_keys_max", ctypes.c_int, [_P, _U32]),

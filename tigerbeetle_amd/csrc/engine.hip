@@ -37,6 +37,7 @@
 #include "k_query_filter.h"
 #include "k_balances.h"
 #include "k_change_events.h"
+#include "k_asof.h"
 #include "checksum.h"
 
 static thread_local std::string g_err;

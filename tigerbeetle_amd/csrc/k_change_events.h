@@ -76,6 +76,47 @@ __device__ static inline u32 tb_change_probe(const u32* s_set, u32 mask, const u
     return CHANGE_NONE;
 }
 
+// The same over a workgroup's narrowed copy of the entries (tb_change_lds_entry): {3-bit tag, index + 1}
+// in 16 bits, for sets whose indices stay below 8,191.  One occupied slot in eight passes the tag and
+// pays the read of the full id.
+__device__ static inline u32 tb_change_probe(const u16* s_set, u32 mask, const u64* ids, u64 lo, u64 hi) {
+    const u64 h = tb_change_hash(lo, hi);
+    const u32 tag = (u32)(h >> 61);
+    u32 s = (u32)h & mask;
+    for (u32 i = 0; i <= mask; i++) {
+        const u32 e = s_set[s];
+        if (e == 0) return CHANGE_NONE;
+        if ((e >> 13) == tag) {
+            const u32 index = (e & 0x1FFFu) - 1;
+            if (ids[2 * (u64)index] == lo && ids[2 * (u64)index + 1] == hi) return index;
+        }
+        s = (s + 1) & mask;
+    }
+    return CHANGE_NONE;
+}
+
+// An entry of the set as a workgroup keeps it in LDS: as it is, or narrowed to the top three bits of
+// its tag and its index + 1 (at most 8,191, never zero for an entry that is not).
+template <typename ENTRY>
+__device__ static inline ENTRY tb_change_lds_entry(u32 e) {
+    if (sizeof(ENTRY) == 4) return (ENTRY)e;
+    return (ENTRY)(e ? (e >> 29) << 13 | (e & 0x1FFFu) : 0);
+}
+
+// CACHED bins: the LDS bin that holds `index`'s sums in this workgroup, claimed at its first add — one
+// of the two slots the index hashes to — or CHANGE_NONE when other indices hold both (the add goes to
+// HBM).  tags: [bins] the index each LDS bin holds, CHANGE_NONE while free.
+__device__ static inline u32 tb_change_bin_claim(u32* tags, u32 bins, u32 index) {
+    u32 s = index % bins;
+#pragma unroll
+    for (u32 k = 0; k < 2; k++) {
+        const u32 old = atomicCAS(&tags[s], CHANGE_NONE, index);
+        if (old == CHANGE_NONE || old == index) return s;
+        s = ((index * 0x9E3779B1u) >> 7) % bins;
+    }
+    return CHANGE_NONE;
+}
+
 // Lane `from`'s value (any lane's own when `from` is itself).
 __device__ static inline u128 tb_shfl128(u128 v, u32 from) {
     const u64 lo = __shfl((unsigned long long)tb_lo(v), (int)from);
@@ -109,17 +150,27 @@ __global__ __launch_bounds__(QUERY_THREADS) void tb_change_gather(NodeTablesArgs
 // first, then the flag slot at bins + n_accounts * 8 — all zeroed on the stream before the launch.
 // Workgroup b scans tiles [b, b + 1) * CHANGE_TILES of CHANGE_THREADS positions.  Dynamic LDS: the
 // set's mask + 1 entries, then lds_bins (tb_change_lds_bins) bins of 64 B.
+// get_change_events is <u32, false>: the LDS bins are those of the page's first accounts.
+// lookup_accounts_at (k_asof.h), whose request order says nothing about hotness, is CACHED: exactly
+// lds_bins_max LDS bins, each claimed by the first index that adds to it (tb_change_bin_claim), their
+// tags behind them in LDS; and ENTRY u16 where the set would otherwise take all 64 KB.
+template <typename ENTRY, bool CACHED>
 __global__ __launch_bounds__(CHANGE_THREADS) void tb_change_effects(NodeTablesArgs N, u32 self, u64 n, u64 t_last, const u32* set,
                                                                    u32 mask, const u64* ids, u32 n_accounts, u64* bins,
                                                                    u32 lds_bins_max) {
-    extern __shared__ __attribute__((aligned(16))) u32 s_set[];  // mask + 1 entries
-    u64* s_bins = (u64*)(s_set + mask + 1);                      // the bins of the first accounts of the page
+    extern __shared__ __attribute__((aligned(16))) u8 s_lds[];
+    ENTRY* s_set = (ENTRY*)s_lds;            // mask + 1 entries
+    u64* s_bins = (u64*)(s_set + mask + 1);  // the bins of the first accounts of the page, or the claimed ones
     const Tables& T = N.T[self];
     const u32 lane = threadIdx.x & 63;
     u64* flags = bins + (u64)n_accounts * BALANCE_SLOT_WORDS;
-    const u32 lds_bins = n_accounts < lds_bins_max ? n_accounts : lds_bins_max;
-    for (u32 i = threadIdx.x; i <= mask; i += CHANGE_THREADS) s_set[i] = set[i];
+    const u32 lds_bins = CACHED || n_accounts >= lds_bins_max ? lds_bins_max : n_accounts;
+    u32* s_tags = (u32*)(s_bins + lds_bins * BALANCE_SLOT_WORDS);  // CACHED: the index each LDS bin holds
+    for (u32 i = threadIdx.x; i <= mask; i += CHANGE_THREADS) s_set[i] = tb_change_lds_entry<ENTRY>(set[i]);
     for (u32 i = threadIdx.x; i < lds_bins * BALANCE_SLOT_WORDS; i += CHANGE_THREADS) s_bins[i] = 0;
+    if (CACHED) {
+        for (u32 i = threadIdx.x; i < lds_bins; i += CHANGE_THREADS) s_tags[i] = CHANGE_NONE;
+    }
     __syncthreads();
     for (u32 t = 0; t < CHANGE_TILES; t++) {
         const u64 tile0 = ((u64)blockIdx.x * CHANGE_TILES + t) * CHANGE_THREADS, pos = tile0 + threadIdx.x;
@@ -195,8 +246,10 @@ __global__ __launch_bounds__(CHANGE_THREADS) void tb_change_effects(NodeTablesAr
                     }
                 }
             }
-            if (adds && my < lds_bins) {
-                u64* dst = s_bins + my * BALANCE_SLOT_WORDS + 4 * side;
+            u32 at = my;  // the index's LDS bin, where it has one
+            if (CACHED && adds) at = tb_change_bin_claim(s_tags, lds_bins, my);
+            if (adds && at < lds_bins) {
+                u64* dst = s_bins + at * BALANCE_SLOT_WORDS + 4 * side;
                 tb_atomic_add128(dst, v0);
                 tb_atomic_add128(dst + 2, v1);
             } else if (adds) {
@@ -209,6 +262,8 @@ __global__ __launch_bounds__(CHANGE_THREADS) void tb_change_effects(NodeTablesAr
     // The workgroup's LDS bins go to HBM: a thread per 128-bit word, the untouched ones skipped.
     __syncthreads();
     for (u32 i = threadIdx.x; i < lds_bins * 4; i += CHANGE_THREADS) {
-        tb_atomic_add128(bins + 2 * (u64)i, tb_u128(s_bins[2 * i], s_bins[2 * i + 1]));
+        const u32 index = CACHED ? s_tags[i >> 2] : i >> 2;
+        if (CACHED && index == CHANGE_NONE) continue;
+        tb_atomic_add128(bins + (u64)index * BALANCE_SLOT_WORDS + 2 * (i & 3), tb_u128(s_bins[2 * i], s_bins[2 * i + 1]));
     }
 }

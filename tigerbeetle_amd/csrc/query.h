@@ -1,6 +1,6 @@
 // query.h — the host side of the queries (include/tbgpu.h): get_account_transfers and its batched form
-// get_account_transfers_many, get_account_balances, query_transfers, query_accounts and
-// get_change_events; their buffers, made at tbgpu_init, and their entry points.  Included by engine.hip after the engine's own helpers and before node.h.
+// get_account_transfers_many, get_account_balances, query_transfers, query_accounts,
+// get_change_events and lookup_accounts_at; their buffers, made at tbgpu_init, and their entry points.  Included by engine.hip after the engine's own helpers and before node.h.
 //
 // Every query is written once, over a list of engines (QueryCall): the one engine, or a node's shards.
 // A transfer lives on its home shard only and an account is answered by its owner only, so every
@@ -110,6 +110,24 @@ struct QueryManyBufs {
     u64 n = 0;                       // one batch in flight between query_many_enqueue and _collect
 };
 
+// tbgpu_lookup_accounts_at (k_asof.h): the request's ids, the set built from them, the bins, the
+// accounts' records and found flags, the answer and the result words; made by query_init and shared
+// with nothing.  Every word a query reads is a word it wrote, so tbgpu_reset clears none of them.
+struct LookupAtBufs {
+    u64* d_ids = nullptr;      // [ASOF_IDS_MAX][2] the request
+    u64* h_ids = nullptr;      // pinned: the caller's ids on their way up (a node copies them into every shard's)
+    u32* d_set = nullptr;      // [CHANGE_SET_SLOTS_MAX] the set's entries
+    u64* d_bins = nullptr;     // [ASOF_IDS_MAX + 1][BALANCE_SLOT_WORDS] the bins by request position, then the flag slot
+    u8* d_accounts = nullptr;  // [ASOF_IDS_MAX] the records as the owners hold them
+    u32* d_found = nullptr;    // [ASOF_IDS_MAX] 1: the position yields a record
+    u8* d_out = nullptr;       // [ASOF_IDS_MAX] the answer's records (one engine)
+    u64* d_res = nullptr;      // [ASOF_RES_WORDS]
+    u64* h_res = nullptr;      // pinned mirror
+    u64* h_bins = nullptr;     // pinned mirrors, read by a node's host only: it adds the shards' bins
+    u8* h_accounts = nullptr;
+    u32* h_found = nullptr;
+};
+
 // One engine's query buffers (tbgpu::qs), in the order query_init makes them.
 struct QueryState {
     QueryBufs q;
@@ -117,6 +135,7 @@ struct QueryState {
     AccountQueryBufs qa;
     ChangeBufs qc;
     QueryManyBufs qm;
+    LookupAtBufs ql;
 };
 
 // Called by engine_init on the engine's device, after every other buffer.  The buffers go into the
@@ -195,6 +214,22 @@ static int query_init(tbgpu* E) {
         HIPCK(tbHostMalloc(E->own, &M.h_res, QM_RES_WORDS * 8, hipHostMallocDefault));
         HIPCK(tbHostMalloc(E->own, &M.h_stage, (u64)QUERY_MANY_STAGE * 128, hipHostMallocDefault));
         HIPCK(tbMalloc(E->own, &M.d_out, (u64)QUERY_MANY_FILTERS * BATCH_EVENTS_MAX * 128));
+    }
+    {  // tbgpu_lookup_accounts_at: the ids, the set, the bins, the accounts, the answer, the result words
+        LookupAtBufs& L = E->qs->ql;
+        const u64 ni = ASOF_IDS_MAX, bin_bytes = (ni + 1) * BALANCE_SLOT_WORDS * 8;
+        HIPCK(tbMalloc(E->own, &L.d_ids, ni * 16));
+        HIPCK(tbHostMalloc(E->own, &L.h_ids, ni * 16, hipHostMallocDefault));
+        HIPCK(tbMalloc(E->own, &L.d_set, (u64)CHANGE_SET_SLOTS_MAX * 4));
+        HIPCK(tbMalloc(E->own, &L.d_bins, bin_bytes));
+        HIPCK(tbMalloc(E->own, &L.d_accounts, ni * 128));
+        HIPCK(tbMalloc(E->own, &L.d_found, ni * 4));
+        HIPCK(tbMalloc(E->own, &L.d_out, ni * 128));
+        HIPCK(tbMalloc(E->own, &L.d_res, ASOF_RES_WORDS * 8));
+        HIPCK(tbHostMalloc(E->own, &L.h_res, ASOF_RES_WORDS * 8, hipHostMallocDefault));
+        HIPCK(tbHostMalloc(E->own, &L.h_bins, bin_bytes, hipHostMallocDefault));
+        HIPCK(tbHostMalloc(E->own, &L.h_accounts, ni * 128, hipHostMallocDefault));
+        HIPCK(tbHostMalloc(E->own, &L.h_found, ni * 4, hipHostMallocDefault));
     }
     return TBGPU_STATUS_OK;
 }
@@ -998,7 +1033,7 @@ static int change_events_finish(tbgpu* const* Es, u32 world, const u8* rows, u32
         HIPCK(hipMemsetAsync(D.d_bins, 0, bin_bytes, E->stream));
         const u64 n = E->log_next, per = (u64)CHANGE_THREADS * CHANGE_TILES, nb = (n + per - 1) / per;
         if (nb) {
-            hipLaunchKernelGGL(tb_change_effects, dim3((unsigned)nb), dim3(CHANGE_THREADS),
+            hipLaunchKernelGGL((tb_change_effects<u32, false>), dim3((unsigned)nb), dim3(CHANGE_THREADS),
                                (size_t)slots * 4 + (size_t)lds_bins * BALANCE_SLOT_WORDS * 8, E->stream, NT, d, n, t_last,
                                (const u32*)D.d_set, mask, (const u64*)D.d_ids, na, D.d_bins, lds_bins);
             HIPCK(hipGetLastError());
@@ -1061,4 +1096,146 @@ extern "C" int tbgpu_get_change_events(tbgpu_t* E, const tbgpu_change_events_fil
     result->count = 0;
     if (st == TBGPU_STATUS_OK && m) st = change_events_finish(c.Es, c.world, rows, m, (u8*)out, result);
     return query_end(result, st);
+}
+
+// ---- lookup_accounts_at (k_asof.h, include/tbgpu.h) -----------------------------------------------
+// One engine: ids up, set and bins zeroed, gather -> tb_change_effects -> emit on the engine stream,
+// the result words back; one wait; then the answer's count * 128 bytes.  The set has
+// get_change_events' slots for as many accounts as the request has ids (tb_change_set_slots); a
+// workgroup of the scan keeps it in LDS as it is up to 4,096 ids (at most 8,192 slots) and narrowed to
+// 16-bit entries above (16,384 slots), either way beside ASOF_LDS_BINS claimed bins.
+// T = 0 asks for the records as they are: no set, no scan.
+// A node: every shard gathers (each builds the same set: an id's index is its smallest request
+// position, whatever the order of the inserts; the records come from the owners' tables, as
+// tb_change_gather reads them) and scans its own log on its own device and stream, side by side; the
+// host adds the shards' bins and writes the records.
+static int lookup_at_enqueue(tbgpu* E, const NodeTablesArgs& NT, u32 self, u32 n, u64 T, bool scan, bool emit, u32 cap) {
+    LookupAtBufs& L = E->qs->ql;
+    HIPCK(hipSetDevice(E->device));
+    const u32 slots = tb_change_set_slots(n), mask = slots - 1;
+    const bool narrow = slots > CHANGE_LDS_BINS_SLOTS_MAX;  // 16-bit entries in LDS: the bins keep their room
+    const u64 bin_bytes = ((u64)n + 1) * BALANCE_SLOT_WORDS * 8;
+    const unsigned nb_ids = (n + QUERY_THREADS - 1) / QUERY_THREADS;
+    HIPCK(hipMemcpyAsync(L.d_ids, L.h_ids, (u64)n * 16, hipMemcpyHostToDevice, E->stream));
+    if (scan) {
+        HIPCK(hipMemsetAsync(L.d_set, 0, (u64)slots * 4, E->stream));
+        HIPCK(hipMemsetAsync(L.d_bins, 0, bin_bytes, E->stream));
+    }
+    const bool store = emit || self == 0;  // a node reads the first shard's records only
+    hipLaunchKernelGGL(tb_asof_gather, dim3(nb_ids), dim3(QUERY_THREADS), 0, E->stream, NT, (const u64*)L.d_ids, n, T,
+                       store ? L.d_accounts : nullptr, store ? L.d_found : nullptr, scan ? L.d_set : nullptr, mask);
+    HIPCK(hipGetLastError());
+    const u64 records = E->log_next, per = (u64)CHANGE_THREADS * CHANGE_TILES, nb = (records + per - 1) / per;
+    if (scan && nb) {
+        const size_t lds = (size_t)slots * (narrow ? 2 : 4) + (size_t)ASOF_LDS_BINS * (BALANCE_SLOT_WORDS * 8 + 4);
+        if (narrow) {
+            hipLaunchKernelGGL((tb_change_effects<u16, true>), dim3((unsigned)nb), dim3(CHANGE_THREADS), lds, E->stream, NT, self,
+                               records, T, (const u32*)L.d_set, mask, (const u64*)L.d_ids, n, L.d_bins, ASOF_LDS_BINS);
+        } else {
+            hipLaunchKernelGGL((tb_change_effects<u32, true>), dim3((unsigned)nb), dim3(CHANGE_THREADS), lds, E->stream, NT, self,
+                               records, T, (const u32*)L.d_set, mask, (const u64*)L.d_ids, n, L.d_bins, ASOF_LDS_BINS);
+        }
+        HIPCK(hipGetLastError());
+    }
+    if (emit) {
+        hipLaunchKernelGGL(tb_asof_emit, dim3(nb_ids), dim3(QUERY_THREADS), 0, E->stream, (const u64*)L.d_ids, n,
+                           (const u8*)L.d_accounts, (const u32*)L.d_found, scan ? (const u32*)L.d_set : nullptr, mask,
+                           scan ? (const u64*)L.d_bins : nullptr, cap, L.d_out, L.d_res);
+        HIPCK(hipGetLastError());
+        HIPCK(hipMemcpyAsync(L.h_res, L.d_res, ASOF_RES_WORDS * 8, hipMemcpyDeviceToHost, E->stream));
+        return TBGPU_STATUS_OK;
+    }
+    if (scan) HIPCK(hipMemcpyAsync(L.h_bins, L.d_bins, bin_bytes, hipMemcpyDeviceToHost, E->stream));
+    if (self == 0) {
+        HIPCK(hipMemcpyAsync(L.h_accounts, L.d_accounts, (u64)n * 128, hipMemcpyDeviceToHost, E->stream));
+        HIPCK(hipMemcpyAsync(L.h_found, L.d_found, (u64)n * 4, hipMemcpyDeviceToHost, E->stream));
+    }
+    return TBGPU_STATUS_OK;
+}
+
+// A node's answer from its shards' pinned mirrors: the found positions in request order, each with the
+// balances less every shard's bin of its id (the bin of the smallest position that names the id).
+static void lookup_at_node_records(const QueryCall& c, u32 n, bool scan, u32 cap, u8* out, tbgpu_query_result* result) {
+    const LookupAtBufs& L = c.Es[0]->qs->ql;
+    std::vector<u32> index(n);
+    if (scan) {
+        std::vector<u32> order(n);
+        std::iota(order.begin(), order.end(), 0u);
+        auto id_of = [&](u32 i) { return std::make_pair(L.h_ids[2 * (u64)i + 1], L.h_ids[2 * (u64)i]); };
+        std::sort(order.begin(), order.end(), [&](u32 a, u32 b) { return id_of(a) != id_of(b) ? id_of(a) < id_of(b) : a < b; });
+        for (u32 j = 0; j < n; j++) index[order[j]] = j && id_of(order[j - 1]) == id_of(order[j]) ? index[order[j - 1]] : order[j];
+    }
+    u32 m = 0, written = 0;
+    for (u32 i = 0; i < n; i++) {
+        if (!L.h_found[i]) continue;
+        if (m++ >= cap) continue;
+        u8* rec = out + (u64)written++ * 128;
+        memcpy(rec, L.h_accounts + (u64)i * 128, 128);
+        if (!scan) continue;
+        u128 bal[4];
+        memcpy(bal, rec + 16, sizeof bal);
+        for (u32 d = 0; d < c.world; d++) {
+            const u128* bins = (const u128*)c.Es[d]->qs->ql.h_bins + (u64)index[i] * 4;
+            for (u32 col = 0; col < 4; col++) bal[col] -= bins[col];
+        }
+        memcpy(rec + 16, bal, sizeof bal);
+    }
+    if (scan) {
+        for (u32 d = 0; d < c.world; d++) {
+            if (c.Es[d]->qs->ql.h_bins[(u64)n * BALANCE_SLOT_WORDS + CHANGE_FLAG_ORPHAN]) result->complete = 0;
+        }
+    }
+    result->count = written;
+    result->matched = m;
+}
+
+extern "C" int tbgpu_lookup_accounts_at(tbgpu_t* E, uint64_t timestamp, const void* ids, uint32_t n, void* out,
+                                        uint32_t out_cap_records, tbgpu_query_result* result) {
+    API_ENTER(E, false);
+    if (n > TBGPU_LOOKUP_AT_MAX) return fail(TBGPU_STATUS_INVALID, "lookup_accounts_at: %u ids (at most %u)", n, TBGPU_LOOKUP_AT_MAX);
+    if (n == 0) return TBGPU_STATUS_OK;
+    if (!ids || !out || !result) return fail(TBGPU_STATUS_INVALID, "lookup_accounts_at: NULL ids, out or result");
+    QueryCall c;
+    result->count = 0;
+    result->matched = 0;
+    result->complete = query_engines(E, true, &c);
+    if (timestamp == ~0ULL) return TBGPU_STATUS_OK;
+    const bool scan = timestamp != 0, one = c.world == 1;
+    NodeTablesArgs NT{};
+    NT.world = c.world;
+    for (u32 d = 0; d < c.world; d++) NT.T[d] = c.Es[d]->T;
+    // Every engine is drained before any is asked: a gather reads the owners' tables and a scan its
+    // posts' pending transfers on their homes.
+    for (u32 d = 0; d < c.world; d++) {
+        HIPCK(hipSetDevice(c.Es[d]->device));
+        if (c.Es[d]->pending) {
+            const int st = engine_sync(c.Es[d]);
+            if (st) return query_end(result, st);
+        }
+    }
+    memcpy(c.Es[0]->qs->ql.h_ids, ids, (u64)n * 16);
+    // Without a scan nothing is summed: a node's first shard gathers alone.
+    const u32 asked = scan ? c.world : 1;
+    int st = query_side_by_side(c.Es, asked, [&](u32 d) -> int {
+        if (d) memcpy(c.Es[d]->qs->ql.h_ids, c.Es[0]->qs->ql.h_ids, (u64)n * 16);
+        return lookup_at_enqueue(c.Es[d], NT, d, n, timestamp, scan, one, out_cap_records);
+    });
+    if (st) return query_end(result, st);
+    if (!one) {
+        lookup_at_node_records(c, n, scan, out_cap_records, (u8*)out, result);
+        return TBGPU_STATUS_OK;
+    }
+    tbgpu* S = c.Es[0];
+    const LookupAtBufs& L = S->qs->ql;
+    const u64 matched = L.h_res[ASOF_RES_MATCHED];
+    const u32 m = (u32)std::min<u64>(matched, out_cap_records);
+    if (matched > n) return query_end(result, fail(TBGPU_STATUS_PANIC, "lookup_accounts_at: %llu records for %u ids", (unsigned long long)matched, n));
+    if (m) {
+        HIPCK(hipMemcpyAsync(out, L.d_out, (u64)m * 128, hipMemcpyDeviceToHost, S->stream));
+        HIPCK(hipStreamSynchronize(S->stream));
+    }
+    if (L.h_res[ASOF_RES_ORPHAN]) result->complete = 0;
+    result->count = m;
+    result->matched = matched;
+    return TBGPU_STATUS_OK;
 }

@@ -307,6 +307,13 @@ tbgpu_query_result StateMachine::get_change_events(const tbgpu_change_events_fil
     return r;
 }
 
+tbgpu_query_result StateMachine::lookup_accounts_at(uint64_t timestamp, const void* ids, uint32_t n, void* out,
+                                                    uint32_t out_cap_records) {
+    tbgpu_query_result r{};
+    check(tbgpu_lookup_accounts_at(engine_, timestamp, ids, n, out, out_cap_records, &r), "lookup_accounts_at");
+    return r;
+}
+
 tbgpu_query_result StateMachine::query_transfers(const tbgpu_query_filter& filter, void* out, uint32_t out_cap_records) {
     tbgpu_query_result r{};
     check(tbgpu_query_transfers(engine_, &filter, out, out_cap_records, &r), "query_transfers");

@@ -255,6 +255,14 @@ public:
     // account the table lacks (its block is zero).
     tbgpu_query_result get_change_events(const tbgpu_change_events_filter& filter, void* out, uint32_t out_cap_events);
 
+    // The accounts as they stood at a timestamp (tbgpu_lookup_accounts_at; a read, and no reference
+    // operation behind it): one 128-byte record per id the table holds, in request order, with the
+    // balances less the effects of every resident transfer newer than `timestamp`; an account created
+    // after it is skipped.  ids: n x {lo, hi}, at most TBGPU_LOOKUP_AT_MAX.  timestamp 0: now.
+    // result.complete == 0: transfers were evicted or a summed post had lost its pending transfer.
+    tbgpu_query_result lookup_accounts_at(uint64_t timestamp, const void* ids, uint32_t n, void* out,
+                                          uint32_t out_cap_records);
+
     // The field-filter queries (tbgpu_query_transfers / tbgpu_query_accounts; reads, not commits): the
     // resident transfers, or the accounts, whose user_data_128 / user_data_64 / user_data_32 / ledger /
     // code equal the filter's non-zero fields, by timestamp (newest first under TBGPU_QUERY_REVERSED),

@@ -307,7 +307,9 @@ std::string run_table(tb::StateMachine& sm, const std::string& text) {
 // --query-many (tests/test_gpu_query_many_cpp.py): the prepares ending in {0, 0, n * 64, n
 // tbgpu_account_filter}, answered by get_account_transfers_many; <answer.bin> receives, per filter,
 // the 16-byte tbgpu_query_result and then its records.
-enum QueryKind { ACCOUNT_TRANSFERS, ACCOUNT_BALANCES, QUERY_TRANSFERS, QUERY_ACCOUNTS, CHANGE_EVENTS, ACCOUNT_TRANSFERS_MANY };
+// --query-accounts-at (tests/test_gpu_lookup_at_cpp.py): the prepares ending in {0, 0, 8 + n * 16, a u64
+// timestamp and n ids}, answered by lookup_accounts_at (the records are accounts).
+enum QueryKind { ACCOUNT_TRANSFERS, ACCOUNT_BALANCES, QUERY_TRANSFERS, QUERY_ACCOUNTS, CHANGE_EVENTS, ACCOUNT_TRANSFERS_MANY, ACCOUNTS_AT };
 
 int run_query(tb::StateMachine& sm, QueryKind kind, const char* in_path, const char* out_path) {
     std::ifstream in(in_path, std::ios::binary);
@@ -354,6 +356,21 @@ int run_query(tb::StateMachine& sm, QueryKind kind, const char* in_path, const c
         }
         return o ? 0 : 2;
     }
+    if (kind == ACCOUNTS_AT) {
+        const size_t n = body.size() / 16;
+        if (body.size() % 16 != 8 || n > TBGPU_LOOKUP_AT_MAX) {
+            fprintf(stderr, "%s: a timestamp and at most %u ids of 16 bytes\n", in_path, TBGPU_LOOKUP_AT_MAX);
+            return 2;
+        }
+        uint64_t timestamp = 0;
+        memcpy(&timestamp, body.data(), 8);
+        std::vector<uint8_t> out((size_t)TBGPU_LOOKUP_AT_MAX * 128);
+        const tbgpu_query_result r = sm.lookup_accounts_at(timestamp, body.data() + 8, (uint32_t)n, out.data(), TBGPU_LOOKUP_AT_MAX);
+        std::ofstream o(out_path, std::ios::binary);
+        o.write((const char*)&r, sizeof(r)).write((const char*)out.data(), (size_t)r.count * 128);
+        printf("query: %u of %llu records, complete %u\n", r.count, (unsigned long long)r.matched, r.complete);
+        return o ? 0 : 2;
+    }
     if (body.size() != sizeof(f)) {
         fprintf(stderr, "%s: a filter is %zu bytes\n", in_path, sizeof(f));
         return 2;
@@ -381,8 +398,9 @@ int main(int argc, char** argv) {
     const bool balances = argc > 1 && std::string(argv[1]) == "--query-balances";
     const bool changes = argc > 1 && std::string(argv[1]) == "--query-change-events";
     const bool many = argc > 1 && std::string(argv[1]) == "--query-many";
-    const bool query = fields || balances || changes || many || (argc > 1 && std::string(argv[1]) == "--query");
-    QueryKind kind = balances ? ACCOUNT_BALANCES : changes ? CHANGE_EVENTS : many ? ACCOUNT_TRANSFERS_MANY : ACCOUNT_TRANSFERS;
+    const bool at = argc > 1 && std::string(argv[1]) == "--query-accounts-at";
+    const bool query = fields || balances || changes || many || at || (argc > 1 && std::string(argv[1]) == "--query");
+    QueryKind kind = balances ? ACCOUNT_BALANCES : changes ? CHANGE_EVENTS : many ? ACCOUNT_TRANSFERS_MANY : at ? ACCOUNTS_AT : ACCOUNT_TRANSFERS;
     const char* self = argv[0];
     if (fields && argc > 2) {
         const std::string which = argv[2];
@@ -396,8 +414,9 @@ int main(int argc, char** argv) {
                 "       %s --query-many <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-balances <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-change-events <prepares.bin> <answer.bin> [device]\n"
+                "       %s --query-accounts-at <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-fields <transfers|accounts> <prepares.bin> <answer.bin> [device]\n",
-                self, self, self, self, self, self);
+                self, self, self, self, self, self, self);
         return 2;
     }
     if (query) {

@@ -340,6 +340,38 @@ class Engine:
         _lib.check(self.lib.tbgpu_get_change_events(self.h, src, out.ctypes.data, cap, ctypes.byref(res)))
         return out[:res.count], int(res.matched), bool(res.complete)
 
+    LOOKUP_AT_MAX = 8191  # TBGPU_LOOKUP_AT_MAX
+
+    def lookup_accounts_at(self, ids, timestamp, out_cap_records=None):
+        """The accounts `ids` as they stood at `timestamp` (tbgpu_lookup_accounts_at): one record per id
+        the table holds, in request order, a repeated id once per occurrence, with the balances less
+        the effects of every resident transfer newer than `timestamp`; an account created after it is
+        skipped.  timestamp 0 means now (lookup_accounts' bytes, no scan).  Returns (records ndarray
+        of ACCOUNT_DTYPE, matched, complete); `complete` is False once the engine has evicted
+        transfers or a post in a sum had lost its pending transfer."""
+        ids = [int(i) for i in ids]
+        if len(ids) > self.LOOKUP_AT_MAX:
+            raise ValueError("at most %d ids in one call" % self.LOOKUP_AT_MAX)
+        body = b"".join(i.to_bytes(16, "little") for i in ids)
+        return self.lookup_accounts_at_raw(body, timestamp, out_cap_records)
+
+    def lookup_accounts_at_raw(self, id_bytes, timestamp, out_cap_records=None):
+        """lookup_accounts_at from the ids' bytes, 16 each ({lo, hi}, little-endian)."""
+        id_bytes = bytes(id_bytes)
+        if len(id_bytes) % 16 != 0:
+            raise ValueError("an id is 16 bytes")
+        n = len(id_bytes) // 16
+        if n > self.LOOKUP_AT_MAX:
+            raise ValueError("at most %d ids in one call" % self.LOOKUP_AT_MAX)
+        if n == 0:  # the library returns at once and leaves its result alone
+            return np.zeros(0, dtype=ACCOUNT_DTYPE), 0, True
+        cap = n if out_cap_records is None else int(out_cap_records)
+        out = np.zeros(max(cap, 1), dtype=ACCOUNT_DTYPE)
+        res = _lib.tbgpu_query_result()
+        src = ctypes.create_string_buffer(id_bytes, len(id_bytes))
+        _lib.check(self.lib.tbgpu_lookup_accounts_at(self.h, int(timestamp), src, n, out.ctypes.data, cap, ctypes.byref(res)))
+        return out[:res.count], int(res.matched), bool(res.complete)
+
     @staticmethod
     def query_filter(user_data_128=0, user_data_64=0, user_data_32=0, ledger=0, code=0, *, reversed=False,
                      timestamp_min=0, timestamp_max=0, limit=8190):
@@ -708,6 +740,10 @@ class StateMachine:
     def get_change_events(self, **filter):
         """The change stream (Engine.get_change_events): a read, not a commit."""
         return self.engine.get_change_events(**filter)
+
+    def lookup_accounts_at(self, ids, timestamp, out_cap_records=None):
+        """The accounts as they stood at a timestamp (Engine.lookup_accounts_at): a read, not a commit."""
+        return self.engine.lookup_accounts_at(ids, timestamp, out_cap_records)
 
     def query_transfers(self, **filter):
         """The field-filter query over transfers (Engine.query_transfers): a read, not a commit."""

@@ -1,7 +1,7 @@
 """The account-filter scan (tbgpu_get_account_transfers, csrc/k_query.h) over a 16M-transfer log (2 GB)
 against a device-to-device copy of the same log range, in one process.
 
-usage: python tools/gpu/query_scan.py [transfers] [runs] [--only account|fields|balances|change_events|many]
+usage: python tools/gpu/query_scan.py [transfers] [runs] [--only account|fields|balances|change_events|many|asof]
 
 The log is built by the device generator, committed in place (the way tools/gpu/device_pass.py builds
 a pass): once with uniform C2 ids, where the queried account is a cold one (a few dozen matches), and
@@ -32,6 +32,13 @@ into buffers made once — for 1, 8 and 64 cold filters on distinct accounts of 
 newest first, and 64 filters of the Zipf log that include its hottest account, beside the copy of the
 log and one single cold query of the same run; 64 x that single query's median is the yardstick.  It
 also times the 64 cold filters with chunks of 8, 16, 32 and 64 tiles.
+
+`--only asof` (tbgpu_lookup_accounts_at) times the C call alone, into buffers made once, on
+both logs, beside get_change_events' oldest page and query_transfers with the same window in the same
+process: a request of that page's distinct accounts (at most 5,460: the scan reads what the page's
+second scan reads) and one of 8,191 ids, each with T older than every transfer (the whole log is newer)
+and T newer than every transfer (the scan reads timestamps only), and the 8,191 ids with T = 0 (no
+scan).  The yardstick is the page's second pass, get_change_events less query_transfers.
 """
 import json
 import os
@@ -316,8 +323,81 @@ def measure_many():
     return out
 
 
+def measure_asof():
+    """lookup_accounts_at beside get_change_events' oldest page, on both logs, in one process."""
+    import ctypes
+
+    from tigerbeetle_amd import _lib
+    os.environ["TBGPU_QUERY_COOP"] = "0"
+    e = Engine(Options(accounts_max=n_acct, transfers_max=n_xfer, pass_events_max=pb * batch, pass_batches_max=pb))
+    a_lens = batches(n_acct, batch)
+    a_ts, t = timestamps(a_lens, 1_000_000_000)
+    acct = e.alloc(n_acct * 128)
+    e.generate_accounts(acct, 0, n_acct, seed=42)
+    res = e.alloc(max(n_acct, n_xfer) * 8)
+    rb = e.alloc((n_xfer // batch + 2) * 4)
+    e.commit_device_async(128, a_ts, a_lens, acct, res, rb)
+    e.sync()
+    h_out = np.zeros(Engine.LOOKUP_AT_MAX, dtype=ACCOUNT_DTYPE)
+    h_res = _lib.tbgpu_query_result()
+
+    def raw_at(ids, T):
+        body = b"".join(i.to_bytes(16, "little") for i in ids)
+        src = ctypes.create_string_buffer(body, len(body))
+        return lambda: _lib.check(e.lib.tbgpu_lookup_accounts_at(e.h, T, src, len(ids), h_out.ctypes.data, len(ids), ctypes.byref(h_res)))
+
+    out = {}
+    for name, kind in (("uniform", "c2"), ("zipf", "c3")):
+        if name != "uniform":
+            e.reset_transfers()
+        log = e.log_window(n_xfer)
+        e.generate_transfers(log, 0, n_xfer, n_acct, seed=42, kind=KINDS[kind])
+        e.sync()
+        x_lens = batches(n_xfer, batch)
+        x_ts, t = timestamps(x_lens, t + 10)
+        e.commit_device_async(129, x_ts, x_lens, log, res, rb)
+        e.sync()
+        recs, matched, complete = e.query_transfers(limit=2730)
+        events, c_matched, c_complete = e.get_change_events(limit=2730)
+        assert complete and c_complete and len(events) == len(recs) == 2730
+        newest, _, _ = e.query_transfers(reversed=True, limit=1)
+        t_old, t_new = int(recs["timestamp"][0]) - 1, int(newest["timestamp"][0])
+        page_ids = []
+        for f in ("debit_account_id", "credit_account_id"):
+            page_ids += [int(lo) | (int(hi) << 64) for lo, hi in zip(recs[f + "_lo"].tolist(), recs[f + "_hi"].tolist())]
+        page_ids = list(dict.fromkeys(page_ids))
+        # 8,191 ids: the page's accounts first, then distinct accounts of the log's middle.
+        sample = e.to_host(log + (n_xfer // 2) * 128, min(n_xfer // 2, 1 << 16) * 128).view(TRANSFER_DTYPE)
+        more = [int(lo) | (int(hi) << 64) for lo, hi in zip(sample["debit_account_id_lo"].tolist(), sample["debit_account_id_hi"].tolist())]
+        full = list(dict.fromkeys(page_ids + more))[:Engine.LOOKUP_AT_MAX]
+        assert len(full) == Engine.LOOKUP_AT_MAX
+        # The page's last event is its two accounts at its timestamp; T newer than everything is now.
+        last = events[-1]
+        pair = [int(last["transfer"][f + "_lo"]) | (int(last["transfer"][f + "_hi"]) << 64) for f in ("debit_account_id", "credit_account_id")]
+        got, _, at_complete = e.lookup_accounts_at(pair, int(last["transfer"]["timestamp"]))
+        assert at_complete and got[0].tobytes() == last["debit_account"].tobytes() and got[1].tobytes() == last["credit_account"].tobytes()
+        now, now_matched, _ = e.lookup_accounts_at(full, 0)
+        assert now_matched == len(full) and e.lookup_accounts_at(full, t_new)[0].tobytes() == now.tobytes()
+        then, _, _ = e.lookup_accounts_at(full, t_old)
+        assert then.tobytes() != now.tobytes()
+        q_med, q_lo, q_hi = timed(e, lambda: e.query_transfers(limit=2730))
+        c_med, c_lo, c_hi = timed(e, lambda: e.get_change_events(limit=2730))
+        second = c_med - q_med
+        out["%s_change_events_oldest_page" % name] = row(c_med, c_lo, c_hi, distinct_accounts=len(page_ids),
+                                                         query_transfers_ms=round(q_med, 4), query_transfers_min_ms=round(q_lo, 4),
+                                                         query_transfers_max_ms=round(q_hi, 4), second_pass_ms=round(second, 4))
+        for leg, ids, T in (("page_ids_t_old", page_ids, t_old), ("page_ids_t_new", page_ids, t_new),
+                            ("8191_ids_t_old", full, t_old), ("8191_ids_t_new", full, t_new), ("8191_ids_now", full, 0)):
+            med, lo_ms, hi_ms = timed(e, raw_at(ids, T))
+            out["%s_asof_%s" % (name, leg)] = row(med, lo_ms, hi_ms, ids=len(ids), over_second_pass=round(med / second, 2))
+    e.close()
+    return out
+
+
 result = dict(transfers=n_xfer, log_bytes=n_xfer * 128, runs=runs, warmups=WARMUPS)
-if only == "many":
+if only == "asof":
+    result["asof"] = measure_asof()
+elif only == "many":
     result["many"] = measure_many()
 elif only == "balances":
     result["balances"] = measure(False, balances=True)
@@ -328,6 +408,6 @@ elif only != "fields":
     for shape in ("lane_per_record", "cooperative"):
         r = result[shape]
         r["bar_query_le_copy"] = all(v["ms"] <= r["copy_d2d"]["ms"] for k, v in r.items() if k != "copy_d2d")
-if only not in ("account", "balances", "change_events", "many"):
+if only not in ("account", "balances", "change_events", "many", "asof"):
     result["field_filters"] = measure_fields()
 print(json.dumps(result))

@@ -664,6 +664,37 @@ pub fn StateMachineType(
             self.registered_messages.putAssumeCapacity(address, {});
         }
 
+        /// The accounts `ids` as they stood at `timestamp` (tbgpu_lookup_accounts_at; 0 means now): a
+        /// read, with no operation in this reference's enum, so nothing in commit() dispatches to it
+        /// (INTEGRATION.md, "Accounts as of a timestamp"). One 128-byte record per id the engine
+        /// holds and that existed then, in request order, into `output`; returns the bytes written.
+        /// `complete` is false once transfers were evicted or a summed post had lost its pending
+        /// transfer: the caller then merges with the forest.
+        pub fn lookup_accounts_at(
+            self: *StateMachine,
+            timestamp: u64,
+            ids: []const u128,
+            output: []align(16) u8,
+            complete: *bool,
+        ) usize {
+            assert(ids.len <= tbgpu.TBGPU_LOOKUP_AT_MAX);
+            var result: tbgpu.tbgpu_query_result = undefined;
+            result.count = 0;
+            result.complete = 1;
+            result.matched = 0;
+            check(tbgpu.tbgpu_lookup_accounts_at(
+                self.engine,
+                timestamp,
+                ids.ptr,
+                @intCast(ids.len),
+                output.ptr,
+                @intCast(output.len / @sizeOf(Account)),
+                &result,
+            ));
+            complete.* = result.complete != 0;
+            return @as(usize, result.count) * @sizeOf(Account);
+        }
+
         pub fn compact(self: *StateMachine, callback: *const fn (*StateMachine) void, op: u64) void {
             assert(self.compact_callback == null);
             assert(self.checkpoint_callback == null);
