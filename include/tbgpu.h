@@ -23,6 +23,7 @@
  *                                                             derived from the log, nothing stored)
  *   (later references: get_change_events)                  tbgpu_get_change_events (likewise)
  *   (no reference: accounts as of a timestamp)             tbgpu_lookup_accounts_at (likewise)
+ *   (no reference: a trial balance per ledger)             tbgpu_get_ledger_balances (likewise)
  *   `setup` action of the table tests (:1398-1407)         tbgpu_test_set_balances (test only)
  *   StateMachine.commit_timestamp field (:251)             tbgpu_commit_timestamp
  *
@@ -555,6 +556,69 @@ int tbgpu_lookup_accounts_at(tbgpu_t* engine, uint64_t timestamp,
                              const void* ids /* n x {lo, hi} */, uint32_t n,
                              void* out, uint32_t out_cap_records,
                              tbgpu_query_result* result);
+
+/* get_ledger_balances: a trial balance per ledger as of a timestamp the caller names — what a close
+ * or a reconciliation asks first: does each ledger balance, and what were its totals at T.  No
+ * reference has an operation for it; nothing is stored at commit, and the answer is one scan of the
+ * account table (every account carries its ledger) plus, for T != 0, one scan of the log's records
+ * newer than T (every record carries its own ledger).  An entry point of its own, as above; this
+ * comment is its specification.
+ *   Rows: one row per requested position, in request order, always.  A ledger no account carries
+ *     yields a zero row (accounts = 0, ledger set); a repeated ledger is answered once per
+ *     occurrence.  matched = n and count = min(n, out_cap_rows); bytes past count rows are not
+ *     written.
+ *   Sums, for a requested ledger L != 0 and T = timestamp, per column modulo 2^128:
+ *       column(L, T) = the sum of current(a).column over every live account a with a.ledger == L
+ *                      (those created after T included)
+ *                      - the summed effects of every live resident record r with r.ledger == L and
+ *                        r.timestamp strictly above T,
+ *     with the effect table, the P rule and the liveness rule of tbgpu_get_account_balances (a post
+ *     whose pending transfer is not resident is summed with P = its own amount).  A record's effect is
+ *     subtracted from the debit columns once and from the credit columns once.  It is the record's own
+ *     ledger field that assigns it to a row; no account is looked up from the log (a committed record's
+ *     two accounts always share its ledger, and a post or void stores its pending transfer's).
+ *   Anchor: the current balances.  After eviction of an old prefix, tbgpu_load_accounts or
+ *     tbgpu_test_set_balances the answer follows this definition, not the ledger's past.  On an engine
+ *     that saw none of those, a row equals the per-ledger sum of tbgpu_lookup_accounts_at over every
+ *     account at T (accounts younger than T contribute zero), and debits_* == credits_* in every row
+ *     at every T.
+ *   Ledger 0: no account can carry it, so a requested 0 means every ledger together: that row sums
+ *     every live account and every live resident record newer than T.  At T = 0 it is
+ *     tbgpu_bench_ledger_summary's four sums and its account count.
+ *   accounts: the live accounts of L whose creation timestamp is <= T; all of them when T = 0; over
+ *     every ledger for L = 0.
+ *   timestamp == 0 means now: no log is scanned.  A T at or above every resident record's timestamp
+ *     gives the same sums, and its scan reads the records' timestamps and nothing else.
+ *     timestamp == 2^64-1 returns TBGPU_STATUS_OK with count = matched = 0.
+ *   n == 0 returns TBGPU_STATUS_OK and writes nothing.  n > TBGPU_LEDGERS_MAX, or a NULL ledgers, out
+ *     or result with n > 0, is TBGPU_STATUS_INVALID and writes nothing.  After any failing status the
+ *     result names no row.
+ *   complete: tbgpu_lookup_accounts_at's rule — 1 only when no transfer was ever evicted (any shard)
+ *     and no post without its resident pending transfer entered a sum.  An orphan post of a ledger
+ *     nobody asked for, with 0 not asked either, enters no sum.
+ *   The call contract of tbgpu_get_account_transfers: synchronous, drains a pending
+ *     tbgpu_commit_device_async first, a read that changes nothing, works on an engine a device panic
+ *     stopped, allocates nothing after tbgpu_init, legal beside an asynchronous write-back.
+ *   A node engine has the same contract: each shard sums the accounts it owns (a home's imported
+ *     copies and the sequencer's loaded copies never count) and scans its own log on its own device
+ *     and stream, side by side, reading a post's pending amount on the home of its pending_id; the
+ *     host adds the shards' sums.
+ *   TBGPU_LEDGERS_MAX is 1,024 so that a workgroup's LDS — the requested ledgers as a set with twice
+ *     as many slots, and a few hundred claimed bins — stays well within 64 KB, with room for a second
+ *     workgroup on the compute unit. */
+#define TBGPU_LEDGERS_MAX 1024u
+typedef struct tbgpu_ledger_balance {      /* 128 bytes, little-endian, no padding */
+    uint64_t debits_pending_lo,  debits_pending_hi;    /* the first 64 bytes: tbgpu_account_balance's */
+    uint64_t debits_posted_lo,   debits_posted_hi;
+    uint64_t credits_pending_lo, credits_pending_hi;
+    uint64_t credits_posted_lo,  credits_posted_hi;
+    uint64_t accounts;                     /* accounts of the ledger that existed at T */
+    uint32_t ledger;
+    uint8_t  reserved[52];                 /* zero */
+} tbgpu_ledger_balance;
+int tbgpu_get_ledger_balances(tbgpu_t* engine, uint64_t timestamp,
+                              const uint32_t* ledgers, uint32_t n,
+                              void* out, uint32_t out_cap_rows, tbgpu_query_result* result);
 
 /* The replica writes StateMachine.commit_timestamp itself: the header timestamp after every commit
  * (src/vsr/replica.zig:3664-3665) and the checkpoint's value on open / state sync.  The wrapper

@@ -76,6 +76,17 @@ class tbgpu_change_event(ctypes.Structure):
 CHANGE_EVENTS_MAX = 2730  # TBGPU_CHANGE_EVENTS_MAX
 
 
+class tbgpu_ledger_balance(ctypes.Structure):
+    _fields_ = [("debits_pending_lo", ctypes.c_uint64), ("debits_pending_hi", ctypes.c_uint64),
+                ("debits_posted_lo", ctypes.c_uint64), ("debits_posted_hi", ctypes.c_uint64),
+                ("credits_pending_lo", ctypes.c_uint64), ("credits_pending_hi", ctypes.c_uint64),
+                ("credits_posted_lo", ctypes.c_uint64), ("credits_posted_hi", ctypes.c_uint64),
+                ("accounts", ctypes.c_uint64), ("ledger", ctypes.c_uint32), ("reserved", ctypes.c_uint8 * 52)]
+
+
+LEDGERS_MAX = 1024  # TBGPU_LEDGERS_MAX
+
+
 class tbgpu_stats(ctypes.Structure):
     _fields_ = [
         ("passes", ctypes.c_uint64),
@@ -200,6 +211,7 @@ SIGNATURES = [
     ("tbgpu_get_account_balances", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_get_change_events", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_lookup_accounts_at", ctypes.c_int, [_P, _U64, _P, _U32, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
+    ("tbgpu_get_ledger_balances", ctypes.c_int, [_P, _U64, _P, _U32, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_query_transfers", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_query_accounts", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_bench_query_keys_max", ctypes.c_int, [_P, _U32]),

@@ -38,6 +38,7 @@
 #include "k_balances.h"
 #include "k_change_events.h"
 #include "k_asof.h"
+#include "k_ledgers.h"
 #include "checksum.h"
 
 static thread_local std::string g_err;

@@ -1,6 +1,6 @@
 // query.h — the host side of the queries (include/tbgpu.h): get_account_transfers and its batched form
 // get_account_transfers_many, get_account_balances, query_transfers, query_accounts,
-// get_change_events and lookup_accounts_at; their buffers, made at tbgpu_init, and their entry points.  Included by engine.hip after the engine's own helpers and before node.h.
+// get_change_events, lookup_accounts_at and get_ledger_balances; their buffers, made at tbgpu_init, and their entry points.  Included by engine.hip after the engine's own helpers and before node.h.
 //
 // Every query is written once, over a list of engines (QueryCall): the one engine, or a node's shards.
 // A transfer lives on its home shard only and an account is answered by its owner only, so every
@@ -128,6 +128,15 @@ struct LookupAtBufs {
     u32* h_found = nullptr;
 };
 
+// tbgpu_get_ledger_balances (k_ledgers.h): the ledger set and the bins, on the device and pinned; made
+// by query_init and shared with nothing.  The host builds the set and writes the rows.
+struct LedgerBufs {
+    u32* d_set = nullptr;   // [LEDGER_SET_SLOTS_MAX] the set's entries
+    u32* h_set = nullptr;   // pinned: the host builds it here (a node copies it into every shard's)
+    u64* d_bins = nullptr;  // [LEDGER_BINS(LEDGER_SET_SLOTS_MAX)][LEDGER_BIN_WORDS]
+    u64* h_bins = nullptr;  // pinned mirror
+};
+
 // One engine's query buffers (tbgpu::qs), in the order query_init makes them.
 struct QueryState {
     QueryBufs q;
@@ -136,6 +145,7 @@ struct QueryState {
     ChangeBufs qc;
     QueryManyBufs qm;
     LookupAtBufs ql;
+    LedgerBufs qg;
 };
 
 // Called by engine_init on the engine's device, after every other buffer.  The buffers go into the
@@ -230,6 +240,14 @@ static int query_init(tbgpu* E) {
         HIPCK(tbHostMalloc(E->own, &L.h_bins, bin_bytes, hipHostMallocDefault));
         HIPCK(tbHostMalloc(E->own, &L.h_accounts, ni * 128, hipHostMallocDefault));
         HIPCK(tbHostMalloc(E->own, &L.h_found, ni * 4, hipHostMallocDefault));
+    }
+    {  // tbgpu_get_ledger_balances: the set and the bins
+        LedgerBufs& G = E->qs->qg;
+        const u64 bin_bytes = LEDGER_BINS(LEDGER_SET_SLOTS_MAX) * LEDGER_BIN_WORDS * 8;
+        HIPCK(tbMalloc(E->own, &G.d_set, (u64)LEDGER_SET_SLOTS_MAX * 4));
+        HIPCK(tbHostMalloc(E->own, &G.h_set, (u64)LEDGER_SET_SLOTS_MAX * 4, hipHostMallocDefault));
+        HIPCK(tbMalloc(E->own, &G.d_bins, bin_bytes));
+        HIPCK(tbHostMalloc(E->own, &G.h_bins, bin_bytes, hipHostMallocDefault));
     }
     return TBGPU_STATUS_OK;
 }
@@ -1237,5 +1255,103 @@ extern "C" int tbgpu_lookup_accounts_at(tbgpu_t* E, uint64_t timestamp, const vo
     if (L.h_res[ASOF_RES_ORPHAN]) result->complete = 0;
     result->count = m;
     result->matched = matched;
+    return TBGPU_STATUS_OK;
+}
+
+// ---- get_ledger_balances (k_ledgers.h, include/tbgpu.h) -------------------------------------------
+// The host builds the set of the request's distinct non-zero ledgers in the first engine's pinned
+// buffer; every engine takes it up, zeroes its bins and runs the table scan and, for T != 0, the log
+// scan on its own stream, side by side; the bins come back pinned, the host adds the engines' and
+// writes the rows.  A ledger's bin is its slot in the set; bin `slots` is every ledger together.
+static int ledgers_enqueue(tbgpu* E, const NodeTablesArgs& NT, u32 self, u32 slots, u64 T, u32 all) {
+    LedgerBufs& G = E->qs->qg;
+    HIPCK(hipSetDevice(E->device));
+    const u32 mask = slots - 1;
+    const u64 bin_bytes = LEDGER_BINS(slots) * LEDGER_BIN_WORDS * 8;
+    HIPCK(hipMemcpyAsync(G.d_set, G.h_set, (u64)slots * 4, hipMemcpyHostToDevice, E->stream));
+    HIPCK(hipMemsetAsync(G.d_bins, 0, bin_bytes, E->stream));
+    const u64 per_table = (u64)LEDGER_THREADS * LEDGER_TABLE_TILES, nb_table = (E->account_cap + per_table - 1) / per_table;
+    hipLaunchKernelGGL(tb_ledger_accounts, dim3((unsigned)nb_table), dim3(LEDGER_THREADS), tb_ledger_lds_bytes(slots, LEDGER_TABLE_WORDS),
+                       E->stream, E->T, E->account_cap, NT.world, self, T, (const u32*)G.d_set, mask, all, G.d_bins);
+    HIPCK(hipGetLastError());
+    const u64 records = E->log_next, per_log = (u64)LEDGER_THREADS * LEDGER_LOG_TILES, nb_log = (records + per_log - 1) / per_log;
+    if (T != 0 && nb_log) {
+        hipLaunchKernelGGL(tb_ledger_effects, dim3((unsigned)nb_log), dim3(LEDGER_THREADS), tb_ledger_lds_bytes(slots, LEDGER_LOG_WORDS),
+                           E->stream, NT, self, records, T, (const u32*)G.d_set, mask, all, G.d_bins);
+        HIPCK(hipGetLastError());
+    }
+    HIPCK(hipMemcpyAsync(G.h_bins, G.d_bins, bin_bytes, hipMemcpyDeviceToHost, E->stream));
+    return TBGPU_STATUS_OK;
+}
+
+// The rows from the engines' pinned bins: request position i's row is its ledger's bin (ledger 0: bin
+// `slots`) summed over the engines, the accounts' sums less the newer records' effects on either side.
+static void ledgers_rows(const QueryCall& c, const u32* ledgers, u32 n, u32 slots, u32 cap, u8* out, tbgpu_query_result* result) {
+    const u32* set = c.Es[0]->qs->qg.h_set;
+    const u32 rows = std::min(n, cap);
+    for (u32 i = 0; i < rows; i++) {
+        const u32 bin = ledgers[i] ? tb_ledger_probe(set, slots - 1, ledgers[i]) : slots;
+        u128 sums[4] = {0, 0, 0, 0}, effects[2] = {0, 0};
+        u64 accounts = 0;
+        for (u32 d = 0; d < c.world; d++) {
+            const u64* b = c.Es[d]->qs->qg.h_bins + (u64)bin * LEDGER_BIN_WORDS;
+            for (u32 col = 0; col < 4; col++) sums[col] += tb_u128(b[2 * col], b[2 * col + 1]);
+            for (u32 e = 0; e < 2; e++) effects[e] += tb_u128(b[LEDGER_BIN_EFFECTS + 2 * e], b[LEDGER_BIN_EFFECTS + 2 * e + 1]);
+            accounts += b[LEDGER_BIN_COUNT];
+        }
+        tbgpu_ledger_balance row{};
+        u64* w = &row.debits_pending_lo;
+        for (u32 col = 0; col < 4; col++) {
+            const u128 v = sums[col] - effects[col & 1];
+            w[2 * col] = tb_lo(v), w[2 * col + 1] = tb_hi(v);
+        }
+        row.accounts = accounts;
+        row.ledger = ledgers[i];
+        memcpy(out + (u64)i * sizeof row, &row, sizeof row);
+    }
+    for (u32 d = 0; d < c.world; d++) {
+        if (c.Es[d]->qs->qg.h_bins[((u64)slots + 1) * LEDGER_BIN_WORDS + CHANGE_FLAG_ORPHAN]) result->complete = 0;
+    }
+    result->count = rows;
+    result->matched = n;
+}
+
+extern "C" int tbgpu_get_ledger_balances(tbgpu_t* E, uint64_t timestamp, const uint32_t* ledgers, uint32_t n, void* out,
+                                         uint32_t out_cap_rows, tbgpu_query_result* result) {
+    static_assert(sizeof(tbgpu_ledger_balance) == 128, "a row is 128 bytes");
+    API_ENTER(E, false);
+    if (n > TBGPU_LEDGERS_MAX) return fail(TBGPU_STATUS_INVALID, "get_ledger_balances: %u ledgers (at most %u)", n, TBGPU_LEDGERS_MAX);
+    if (n == 0) return TBGPU_STATUS_OK;
+    if (!ledgers || !out || !result) return fail(TBGPU_STATUS_INVALID, "get_ledger_balances: NULL ledgers, out or result");
+    QueryCall c;
+    result->count = 0;
+    result->matched = 0;
+    result->complete = query_engines(E, true, &c);
+    if (timestamp == ~0ULL) return TBGPU_STATUS_OK;
+    NodeTablesArgs NT{};
+    NT.world = c.world;
+    for (u32 d = 0; d < c.world; d++) NT.T[d] = c.Es[d]->T;
+    // Every engine is drained before any is asked: a scan reads its posts' pending transfers on their homes.
+    for (u32 d = 0; d < c.world; d++) {
+        HIPCK(hipSetDevice(c.Es[d]->device));
+        if (c.Es[d]->pending) {
+            const int st = engine_sync(c.Es[d]);
+            if (st) return query_end(result, st);
+        }
+    }
+    u32* set = c.Es[0]->qs->qg.h_set;
+    u32 all = 0;
+    const u32 slots = tb_ledger_set_slots(n);  // (sized by the positions: at most half full whatever repeats)
+    memset(set, 0, (u64)slots * 4);
+    for (u32 i = 0; i < n; i++) {
+        if (ledgers[i]) tb_ledger_insert(set, slots - 1, ledgers[i]);
+        else all = 1;
+    }
+    const int st = query_side_by_side(c.Es, c.world, [&](u32 d) -> int {
+        if (d) memcpy(c.Es[d]->qs->qg.h_set, set, (u64)slots * 4);
+        return ledgers_enqueue(c.Es[d], NT, d, slots, timestamp, all);
+    });
+    if (st) return query_end(result, st);
+    ledgers_rows(c, ledgers, n, slots, out_cap_rows, (u8*)out, result);
     return TBGPU_STATUS_OK;
 }

@@ -314,6 +314,13 @@ tbgpu_query_result StateMachine::lookup_accounts_at(uint64_t timestamp, const vo
     return r;
 }
 
+tbgpu_query_result StateMachine::get_ledger_balances(uint64_t timestamp, const uint32_t* ledgers, uint32_t n, void* out,
+                                                     uint32_t out_cap_rows) {
+    tbgpu_query_result r{};
+    check(tbgpu_get_ledger_balances(engine_, timestamp, ledgers, n, out, out_cap_rows, &r), "get_ledger_balances");
+    return r;
+}
+
 tbgpu_query_result StateMachine::query_transfers(const tbgpu_query_filter& filter, void* out, uint32_t out_cap_records) {
     tbgpu_query_result r{};
     check(tbgpu_query_transfers(engine_, &filter, out, out_cap_records, &r), "query_transfers");

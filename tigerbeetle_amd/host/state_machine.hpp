@@ -263,6 +263,15 @@ public:
     tbgpu_query_result lookup_accounts_at(uint64_t timestamp, const void* ids, uint32_t n, void* out,
                                           uint32_t out_cap_records);
 
+    // A trial balance per ledger as of a timestamp (tbgpu_get_ledger_balances; a read, and no reference
+    // operation behind it): one 128-byte tbgpu_ledger_balance per requested position, in request
+    // order — the four balances summed over the ledger's accounts, less the effects of every resident
+    // transfer of the ledger newer than `timestamp`, and the accounts that existed then.  Ledger 0:
+    // every ledger together.  ledgers: n x u32, at most TBGPU_LEDGERS_MAX.  timestamp 0: now.
+    // result.complete == 0: transfers were evicted or a summed post had lost its pending transfer.
+    tbgpu_query_result get_ledger_balances(uint64_t timestamp, const uint32_t* ledgers, uint32_t n, void* out,
+                                           uint32_t out_cap_rows);
+
     // The field-filter queries (tbgpu_query_transfers / tbgpu_query_accounts; reads, not commits): the
     // resident transfers, or the accounts, whose user_data_128 / user_data_64 / user_data_32 / ledger /
     // code equal the filter's non-zero fields, by timestamp (newest first under TBGPU_QUERY_REVERSED),

@@ -309,7 +309,10 @@ std::string run_table(tb::StateMachine& sm, const std::string& text) {
 // the 16-byte tbgpu_query_result and then its records.
 // --query-accounts-at (tests/test_gpu_lookup_at_cpp.py): the prepares ending in {0, 0, 8 + n * 16, a u64
 // timestamp and n ids}, answered by lookup_accounts_at (the records are accounts).
-enum QueryKind { ACCOUNT_TRANSFERS, ACCOUNT_BALANCES, QUERY_TRANSFERS, QUERY_ACCOUNTS, CHANGE_EVENTS, ACCOUNT_TRANSFERS_MANY, ACCOUNTS_AT };
+// --query-ledgers (tests/test_gpu_ledger_balances_cpp.py): the prepares ending in {0, 0, 8 + n * 4, a u64
+// timestamp and n u32 ledgers}, answered by get_ledger_balances (the records are tbgpu_ledger_balance rows).
+enum QueryKind { ACCOUNT_TRANSFERS, ACCOUNT_BALANCES, QUERY_TRANSFERS, QUERY_ACCOUNTS, CHANGE_EVENTS, ACCOUNT_TRANSFERS_MANY, ACCOUNTS_AT,
+                 LEDGER_BALANCES };
 
 int run_query(tb::StateMachine& sm, QueryKind kind, const char* in_path, const char* out_path) {
     std::ifstream in(in_path, std::ios::binary);
@@ -371,6 +374,23 @@ int run_query(tb::StateMachine& sm, QueryKind kind, const char* in_path, const c
         printf("query: %u of %llu records, complete %u\n", r.count, (unsigned long long)r.matched, r.complete);
         return o ? 0 : 2;
     }
+    if (kind == LEDGER_BALANCES) {
+        const size_t n = body.size() / 4 - 2;
+        if (body.size() < 8 || body.size() % 4 || n > TBGPU_LEDGERS_MAX) {
+            fprintf(stderr, "%s: a timestamp and at most %u ledgers of 4 bytes\n", in_path, TBGPU_LEDGERS_MAX);
+            return 2;
+        }
+        uint64_t timestamp = 0;
+        memcpy(&timestamp, body.data(), 8);
+        std::vector<uint32_t> ledgers(n);
+        memcpy(ledgers.data(), body.data() + 8, n * 4);
+        std::vector<uint8_t> out((size_t)TBGPU_LEDGERS_MAX * sizeof(tbgpu_ledger_balance));
+        const tbgpu_query_result r = sm.get_ledger_balances(timestamp, ledgers.data(), (uint32_t)n, out.data(), TBGPU_LEDGERS_MAX);
+        std::ofstream o(out_path, std::ios::binary);
+        o.write((const char*)&r, sizeof(r)).write((const char*)out.data(), (size_t)r.count * sizeof(tbgpu_ledger_balance));
+        printf("query: %u of %llu rows, complete %u\n", r.count, (unsigned long long)r.matched, r.complete);
+        return o ? 0 : 2;
+    }
     if (body.size() != sizeof(f)) {
         fprintf(stderr, "%s: a filter is %zu bytes\n", in_path, sizeof(f));
         return 2;
@@ -399,8 +419,9 @@ int main(int argc, char** argv) {
     const bool changes = argc > 1 && std::string(argv[1]) == "--query-change-events";
     const bool many = argc > 1 && std::string(argv[1]) == "--query-many";
     const bool at = argc > 1 && std::string(argv[1]) == "--query-accounts-at";
-    const bool query = fields || balances || changes || many || at || (argc > 1 && std::string(argv[1]) == "--query");
-    QueryKind kind = balances ? ACCOUNT_BALANCES : changes ? CHANGE_EVENTS : many ? ACCOUNT_TRANSFERS_MANY : at ? ACCOUNTS_AT : ACCOUNT_TRANSFERS;
+    const bool ledgers = argc > 1 && std::string(argv[1]) == "--query-ledgers";
+    const bool query = fields || balances || changes || many || at || ledgers || (argc > 1 && std::string(argv[1]) == "--query");
+    QueryKind kind = balances ? ACCOUNT_BALANCES : changes ? CHANGE_EVENTS : many ? ACCOUNT_TRANSFERS_MANY : at ? ACCOUNTS_AT : ledgers ? LEDGER_BALANCES : ACCOUNT_TRANSFERS;
     const char* self = argv[0];
     if (fields && argc > 2) {
         const std::string which = argv[2];
@@ -415,8 +436,9 @@ int main(int argc, char** argv) {
                 "       %s --query-balances <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-change-events <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-accounts-at <prepares.bin> <answer.bin> [device]\n"
+                "       %s --query-ledgers <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-fields <transfers|accounts> <prepares.bin> <answer.bin> [device]\n",
-                self, self, self, self, self, self, self);
+                self, self, self, self, self, self, self, self);
         return 2;
     }
     if (query) {

@@ -23,7 +23,7 @@ import numpy as np
 
 from . import _lib
 from .types import (ACCOUNT_BALANCE_DTYPE, ACCOUNT_DTYPE, ACCOUNT_FILTER_DTYPE, BATCH_MAX, CHANGE_EVENT_DTYPE, CHANGE_EVENTS_FILTER_DTYPE,
-                    CHANGE_EVENTS_MAX, FILTER_CREDITS, FILTER_DEBITS, FILTER_REVERSED, pack_change_events_filter, QUERY_FILTER_DTYPE, QUERY_REVERSED, TRANSFER_DTYPE, U64_MAX, Operation)
+                    CHANGE_EVENTS_MAX, LEDGER_BALANCE_DTYPE, LEDGERS_MAX, FILTER_CREDITS, FILTER_DEBITS, FILTER_REVERSED, pack_change_events_filter, QUERY_FILTER_DTYPE, QUERY_REVERSED, TRANSFER_DTYPE, U64_MAX, Operation)
 
 
 @dataclass
@@ -370,6 +370,39 @@ class Engine:
         res = _lib.tbgpu_query_result()
         src = ctypes.create_string_buffer(id_bytes, len(id_bytes))
         _lib.check(self.lib.tbgpu_lookup_accounts_at(self.h, int(timestamp), src, n, out.ctypes.data, cap, ctypes.byref(res)))
+        return out[:res.count], int(res.matched), bool(res.complete)
+
+    LEDGERS_MAX = LEDGERS_MAX  # TBGPU_LEDGERS_MAX
+
+    def get_ledger_balances(self, ledgers, timestamp=0, out_cap_rows=None):
+        """A trial balance per ledger as of `timestamp` (tbgpu_get_ledger_balances; 0 means now): one
+        row per requested position, in request order — the four balances summed over the ledger's
+        accounts, less the effects of every resident transfer of the ledger newer than `timestamp`,
+        and the accounts that existed then.  Ledger 0 asks for every ledger together.  Returns (rows
+        ndarray of LEDGER_BALANCE_DTYPE, matched, complete); `complete` is False once the engine has
+        evicted transfers or a post in a sum had lost its pending transfer."""
+        ledgers = [int(x) for x in ledgers]
+        if len(ledgers) > self.LEDGERS_MAX:
+            raise ValueError("at most %d ledgers in one call" % self.LEDGERS_MAX)
+        if any(x < 0 or x >> 32 for x in ledgers):
+            raise ValueError("a ledger is 32 bits")
+        return self.get_ledger_balances_raw(np.array(ledgers, dtype="<u4").tobytes(), timestamp, out_cap_rows)
+
+    def get_ledger_balances_raw(self, ledger_bytes, timestamp=0, out_cap_rows=None):
+        """get_ledger_balances from the ledgers' bytes, 4 each (little-endian)."""
+        ledger_bytes = bytes(ledger_bytes)
+        if len(ledger_bytes) % 4 != 0:
+            raise ValueError("a ledger is 4 bytes")
+        n = len(ledger_bytes) // 4
+        if n > self.LEDGERS_MAX:
+            raise ValueError("at most %d ledgers in one call" % self.LEDGERS_MAX)
+        if n == 0:  # the library returns at once and leaves its result alone
+            return np.zeros(0, dtype=LEDGER_BALANCE_DTYPE), 0, True
+        cap = n if out_cap_rows is None else int(out_cap_rows)
+        out = np.zeros(max(cap, 1), dtype=LEDGER_BALANCE_DTYPE)
+        res = _lib.tbgpu_query_result()
+        src = ctypes.create_string_buffer(ledger_bytes, len(ledger_bytes))
+        _lib.check(self.lib.tbgpu_get_ledger_balances(self.h, int(timestamp), src, n, out.ctypes.data, cap, ctypes.byref(res)))
         return out[:res.count], int(res.matched), bool(res.complete)
 
     @staticmethod
@@ -744,6 +777,10 @@ class StateMachine:
     def lookup_accounts_at(self, ids, timestamp, out_cap_records=None):
         """The accounts as they stood at a timestamp (Engine.lookup_accounts_at): a read, not a commit."""
         return self.engine.lookup_accounts_at(ids, timestamp, out_cap_records)
+
+    def get_ledger_balances(self, ledgers, timestamp=0, out_cap_rows=None):
+        """A trial balance per ledger as of a timestamp (Engine.get_ledger_balances): a read, not a commit."""
+        return self.engine.get_ledger_balances(ledgers, timestamp, out_cap_rows)
 
     def query_transfers(self, **filter):
         """The field-filter query over transfers (Engine.query_transfers): a read, not a commit."""

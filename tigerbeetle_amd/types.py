@@ -114,6 +114,13 @@ ACCOUNT_BALANCE_DTYPE = np.dtype(
     + [("timestamp", "<u8"), ("reserved", "u1", (56,))])
 assert ACCOUNT_BALANCE_DTYPE.itemsize == 128
 
+# tbgpu_ledger_balance (include/tbgpu.h tbgpu_get_ledger_balances): 128 bytes, no padding.
+LEDGER_BALANCE_DTYPE = np.dtype(
+    _u128("debits_pending") + _u128("debits_posted") + _u128("credits_pending") + _u128("credits_posted")
+    + [("accounts", "<u8"), ("ledger", "<u4"), ("reserved", "u1", (52,))])
+assert LEDGER_BALANCE_DTYPE.itemsize == 128
+LEDGERS_MAX = 1024
+
 # tbgpu_query_filter (include/tbgpu.h tbgpu_query_transfers / tbgpu_query_accounts): 64 bytes, no padding.
 QUERY_FILTER_DTYPE = np.dtype(
     _u128("user_data_128") + [("user_data_64", "<u8"), ("user_data_32", "<u4"), ("ledger", "<u4"), ("code", "<u2"),

@@ -1,7 +1,7 @@
 """The account-filter scan (tbgpu_get_account_transfers, csrc/k_query.h) over a 16M-transfer log (2 GB)
 against a device-to-device copy of the same log range, in one process.
 
-usage: python tools/gpu/query_scan.py [transfers] [runs] [--only account|fields|balances|change_events|many|asof]
+usage: python tools/gpu/query_scan.py [transfers] [runs] [--only account|fields|balances|change_events|many|asof|ledgers]
 
 The log is built by the device generator, committed in place (the way tools/gpu/device_pass.py builds
 a pass): once with uniform C2 ids, where the queried account is a cold one (a few dozen matches), and
@@ -39,6 +39,15 @@ process: a request of that page's distinct accounts (at most 5,460: the scan rea
 second scan reads) and one of 8,191 ids, each with T older than every transfer (the whole log is newer)
 and T newer than every transfer (the scan reads timestamps only), and the 8,191 ids with T = 0 (no
 scan).  The yardstick is the page's second pass, get_change_events less query_transfers.
+
+`--only ledgers` (tbgpu_get_ledger_balances) times the C call alone, into buffers made once,
+on the uniform log and its one-ledger table: T = 0 with 1 and with 1,024 requested ledgers (the table
+scan alone), T newer than every transfer (the log scan reads timestamps only), T at the log's middle
+and T older than every transfer.  The yardsticks run in the same process: query_accounts with a
+ledger-only all-match filter and a device-to-device copy of the bytes the table scan reads (32 B a slot
+and 64 B a live account); query_transfers with an all-zero filter, timestamp_min = T + 1 and limit 1,
+which takes the same liveness probe on every record of the window.  Then, on a second engine without
+a log, the same table with its accounts spread over 2 and over 1,024 ledgers, every ledger asked.
 """
 import json
 import os
@@ -394,9 +403,110 @@ def measure_asof():
     return out
 
 
+def measure_ledgers():
+    """get_ledger_balances beside query_accounts, query_transfers and the copies, in one process."""
+    import ctypes
+
+    from tigerbeetle_amd import _lib
+    from tigerbeetle_amd.types import LEDGER_BALANCE_DTYPE
+    os.environ["TBGPU_QUERY_COOP"] = "0"
+    h_out = np.zeros(Engine.LEDGERS_MAX, dtype=LEDGER_BALANCE_DTYPE)
+    h_res = _lib.tbgpu_query_result()
+
+    def raw(e, ledgers, T):
+        body = np.array(ledgers, dtype="<u4").tobytes()
+        src = ctypes.create_string_buffer(body, len(body))
+        return lambda: _lib.check(e.lib.tbgpu_get_ledger_balances(e.h, T, src, len(ledgers), h_out.ctypes.data, len(ledgers), ctypes.byref(h_res)))
+
+    out = {}
+    e = Engine(Options(accounts_max=n_acct, transfers_max=n_xfer, pass_events_max=pb * batch, pass_batches_max=pb))
+    a_lens = batches(n_acct, batch)
+    a_ts, t = timestamps(a_lens, 1_000_000_000)
+    acct = e.alloc(n_acct * 128)
+    e.generate_accounts(acct, 0, n_acct, seed=42)
+    res = e.alloc(max(n_acct, n_xfer) * 8)
+    rb = e.alloc((n_xfer // batch + 2) * 4)
+    e.commit_device_async(128, a_ts, a_lens, acct, res, rb)
+    e.sync()
+    spare = e.alloc(n_xfer * 128)
+    log = e.log_window(n_xfer)
+    e.generate_transfers(log, 0, n_xfer, n_acct, seed=42, kind=KINDS["c2"])
+    e.sync()
+    x_lens = batches(n_xfer, batch)
+    x_ts, t = timestamps(x_lens, t + 10)
+    e.commit_device_async(129, x_ts, x_lens, log, res, rb)
+    e.sync()
+    oldest, _, _ = e.query_transfers(limit=1)
+    newest, _, _ = e.query_transfers(reversed=True, limit=1)
+    t_old, t_new = int(oldest["timestamp"][0]) - 1, int(newest["timestamp"][0])
+    t_mid = (t_old + t_new) // 2
+    many = [2] + list(range(1000, 1000 + Engine.LEDGERS_MAX - 1))
+    # What is timed is right: the every-ledger row is the summary, and every T balances.
+    summary = e.ledger_summary()
+    for T in (0, t_new, t_mid, t_old):
+        rows, matched, complete = e.get_ledger_balances([2, 0, 9], T)
+        assert matched == 3 and complete and rows[0].tobytes()[:72] == rows[1].tobytes()[:72] and not rows[2]["accounts"]
+        for c in ("pending", "posted"):
+            assert rows["debits_%s_lo" % c][0] == rows["credits_%s_lo" % c][0] and rows["debits_%s_hi" % c][0] == rows["credits_%s_hi" % c][0]
+        if T in (0, t_new):
+            assert int(rows["accounts"][1]) == summary["accounts"] == n_acct
+            assert int(rows["debits_posted_lo"][1]) | int(rows["debits_posted_hi"][1]) << 64 == summary["debits_posted"]
+        if T == t_old:
+            assert not rows["debits_posted_lo"][0] and not rows["debits_pending_lo"][0]
+    slots = e.stats()["account_table_bytes"] // 132  # hot 32 + balances 64 + cold 32 + mark 4 per slot
+    table_bytes = slots * 32 + n_acct * 64
+    med, lo_ms, hi_ms = timed(e, lambda: e.copy_device_async(spare, log, table_bytes))
+    out["copy_table_d2d"] = copy_table = row(med, lo_ms, hi_ms, bytes=table_bytes, slots=slots)
+    med, lo_ms, hi_ms = timed(e, lambda: e.copy_device_async(spare, log, n_xfer * 128))
+    out["copy_log_d2d"] = row(med, lo_ms, hi_ms, bytes=n_xfer * 128)
+    recs, matched, _ = e.query_accounts(ledger=2, limit=8190)
+    assert matched == n_acct
+    med, lo_ms, hi_ms = timed(e, lambda: e.query_accounts(ledger=2, limit=8190))
+    out["query_accounts_all_match"] = qa = row(med, lo_ms, hi_ms, matched=matched, table_scans=e.query_select_scans() + 2)
+    for name, ledgers in (("now_1_ledger", [2]), ("now_1024_ledgers", many)):
+        med, lo_ms, hi_ms = timed(e, raw(e, ledgers, 0))
+        out[name] = now = row(med, lo_ms, hi_ms, ledgers=len(ledgers), over_query_accounts=round(med / qa["ms"], 2),
+                              over_copy_table=round(med / copy_table["ms"], 2))
+        if len(ledgers) == 1:
+            now_1 = now
+    for name, T in (("t_new", t_new), ("t_mid", t_mid), ("t_old", t_old)):
+        _, q_matched, _ = e.query_transfers(timestamp_min=T + 1, limit=1)
+        q_med, q_lo, q_hi = timed(e, lambda: e.query_transfers(timestamp_min=T + 1, limit=1))
+        for req, ledgers in (("1_ledger", [2]), ("1024_ledgers", many), ("ledger_0", [0])):
+            med, lo_ms, hi_ms = timed(e, raw(e, ledgers, T))
+            scan = med - now_1["ms"]  # the log scan's share: the call less the table scan
+            out["%s_%s" % (name, req)] = row(med, lo_ms, hi_ms, ledgers=len(ledgers), newer_records=q_matched,
+                                             query_transfers_ms=round(q_med, 4), query_transfers_min_ms=round(q_lo, 4),
+                                             query_transfers_max_ms=round(q_hi, 4), log_scan_ms=round(scan, 4),
+                                             log_scan_over_query_transfers=round(scan / q_med, 2))
+    e.close()
+    # The same table with its accounts over 2 and over 1,024 ledgers, no log.
+    for name, n_ledgers in (("table_2_ledgers", 2), ("table_1024_ledgers", Engine.LEDGERS_MAX)):
+        e = Engine(Options(accounts_max=n_acct, transfers_max=1 << 14, pass_events_max=pb * batch, pass_batches_max=pb))
+        acct = e.alloc(n_acct * 128)
+        e.generate_accounts(acct, 0, n_acct, seed=42)
+        e.sync()
+        host = e.to_host(acct, n_acct * 128).view(ACCOUNT_DTYPE)
+        host["ledger"] = 1 + np.arange(n_acct) % n_ledgers
+        e.to_device(acct, host)
+        res = e.alloc(n_acct * 8)
+        rb = e.alloc((n_acct // batch + 2) * 4)
+        e.commit_device_async(128, a_ts, a_lens, acct, res, rb)
+        e.sync()
+        ledgers = list(range(1, n_ledgers + 1))
+        rows, _, _ = e.get_ledger_balances(ledgers + [0], 0) if n_ledgers < Engine.LEDGERS_MAX else e.get_ledger_balances(ledgers, 0)
+        assert int(rows["accounts"][:n_ledgers].sum()) == n_acct and int(rows["accounts"].min()) >= n_acct // n_ledgers
+        med, lo_ms, hi_ms = timed(e, raw(e, ledgers, 0))
+        out[name] = row(med, lo_ms, hi_ms, ledgers=n_ledgers, over_one_ledger_table=round(med / now_1["ms"], 2))
+        e.close()
+    return out
+
+
 result = dict(transfers=n_xfer, log_bytes=n_xfer * 128, runs=runs, warmups=WARMUPS)
 if only == "asof":
     result["asof"] = measure_asof()
+elif only == "ledgers":
+    result["ledgers"] = measure_ledgers()
 elif only == "many":
     result["many"] = measure_many()
 elif only == "balances":
@@ -408,6 +518,6 @@ elif only != "fields":
     for shape in ("lane_per_record", "cooperative"):
         r = result[shape]
         r["bar_query_le_copy"] = all(v["ms"] <= r["copy_d2d"]["ms"] for k, v in r.items() if k != "copy_d2d")
-if only not in ("account", "balances", "change_events", "many", "asof"):
+if only not in ("account", "balances", "change_events", "many", "asof", "ledgers"):
     result["field_filters"] = measure_fields()
 print(json.dumps(result))

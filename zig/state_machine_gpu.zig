@@ -695,6 +695,37 @@ pub fn StateMachineType(
             return @as(usize, result.count) * @sizeOf(Account);
         }
 
+        /// A trial balance per ledger as of `timestamp` (tbgpu_get_ledger_balances; 0 means now): a
+        /// read, with no operation in this reference's enum, so nothing in commit() dispatches to it
+        /// (INTEGRATION.md, "A trial balance per ledger"). One 128-byte tbgpu_ledger_balance per
+        /// requested position, in request order, into `output`; ledger 0 asks for every ledger
+        /// together. Returns the bytes written. `complete` is false once transfers were evicted or
+        /// a summed post had lost its pending transfer.
+        pub fn get_ledger_balances(
+            self: *StateMachine,
+            timestamp: u64,
+            ledgers: []const u32,
+            output: []align(16) u8,
+            complete: *bool,
+        ) usize {
+            assert(ledgers.len <= tbgpu.TBGPU_LEDGERS_MAX);
+            var result: tbgpu.tbgpu_query_result = undefined;
+            result.count = 0;
+            result.complete = 1;
+            result.matched = 0;
+            check(tbgpu.tbgpu_get_ledger_balances(
+                self.engine,
+                timestamp,
+                ledgers.ptr,
+                @intCast(ledgers.len),
+                output.ptr,
+                @intCast(output.len / @sizeOf(tbgpu.tbgpu_ledger_balance)),
+                &result,
+            ));
+            complete.* = result.complete != 0;
+            return @as(usize, result.count) * @sizeOf(tbgpu.tbgpu_ledger_balance);
+        }
+
         pub fn compact(self: *StateMachine, callback: *const fn (*StateMachine) void, op: u64) void {
             assert(self.compact_callback == null);
             assert(self.checkpoint_callback == null);
