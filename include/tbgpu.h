@@ -24,6 +24,7 @@
  *   (later references: get_change_events)                  tbgpu_get_change_events (likewise)
  *   (no reference: accounts as of a timestamp)             tbgpu_lookup_accounts_at (likewise)
  *   (no reference: a trial balance per ledger)             tbgpu_get_ledger_balances (likewise)
+ *   (no reference: pending transfers with their state)     tbgpu_get_pending_transfers (likewise)
  *   `setup` action of the table tests (:1398-1407)         tbgpu_test_set_balances (test only)
  *   StateMachine.commit_timestamp field (:251)             tbgpu_commit_timestamp
  *
@@ -619,6 +620,75 @@ typedef struct tbgpu_ledger_balance {      /* 128 bytes, little-endian, no paddi
 int tbgpu_get_ledger_balances(tbgpu_t* engine, uint64_t timestamp,
                               const uint32_t* ledgers, uint32_t n,
                               void* out, uint32_t out_cap_rows, tbgpu_query_result* result);
+
+/* get_pending_transfers: the two-phase transfers of a window with their state — which holds are
+ * outstanding, and what became of the others.  lookup_transfers returns a pending record unchanged
+ * whether it is open, was posted, was voided or has timed out; this call says which, and hands back
+ * the post or void record with it.  No reference has an operation for it; nothing is stored at commit,
+ * the answer is a scan of the log under a third predicate and, when a returned row is resolved, one
+ * more scan that joins the resolving records.  An entry point of its own, as above; this comment is
+ * its specification.
+ *   What matches: a live resident record (tbgpu_get_account_transfers' liveness rule: the id index
+ *     holds its id at that log position) whose flags carry `pending`, whose timestamp lies in
+ *     [timestamp_min, timestamp_max] (0 leaves that end open), whose account — if account_id != 0 —
+ *     sits on a wanted side (DEBITS / CREDITS, as in tbgpu_get_account_transfers), and whose state is
+ *     among the requested TBGPU_PENDING_* bits.  With account_id 0 the side bits are ignored.
+ *   State of a pending record p, as the commit path decides it for a post or void that arrives at
+ *     timestamp `now`: the posted groove says posted -> POSTED; it says voided -> VOIDED; otherwise, if
+ *     p.timeout != 0 and p.timestamp + p.timeout * 10^9 <= now -> EXPIRED (the sum is taken in u64 and
+ *     saturates at 2^64-1: a wrapped sum never expires); otherwise -> OPEN.  `now` is only the clock
+ *     for expiry: posted and voided are always the engine's current state.  now == 0 means
+ *     tbgpu_commit_timestamp (a node: the node's own).  The engine never expires a pending transfer by
+ *     itself, so an EXPIRED row's amount still stands in its accounts' *_pending balances.
+ *   What is returned: the first k = min(limit, out_cap_rows, TBGPU_PENDING_ROWS_MAX) matches by the
+ *     pending record's timestamp, ascending, or newest first under REVERSED, whatever order the log
+ *     holds them in.  Row i is 256 bytes: the pending record (the bytes lookup_transfers returns) and
+ *     its resolution; out_states[i] holds the single TBGPU_PENDING_* bit of row i.  `matched` counts
+ *     every match.  Bytes past `count` rows and states are not written.
+ *   Resolution: for a returned POSTED or VOIDED row, the live resident record with the post or void
+ *     flag (and not `pending`) whose pending_id equals the row's id; commits produce at most one.  It
+ *     may sit anywhere later in the log, and on a node on another shard (a post lives on the home of
+ *     its own id).  All zero for OPEN and EXPIRED rows, and for a resolved row whose resolving record
+ *     is not resident (it was evicted, or the pending transfer was loaded by tbgpu_load_transfers with
+ *     a posted state and nothing else).
+ *   complete: 1 only when no transfer was ever evicted (any shard) and every returned POSTED / VOIDED
+ *     row found its resolution.
+ *   Invalid filters are never a status: account_id 2^128-1, a non-zero account_id with neither DEBITS
+ *     nor CREDITS, no TBGPU_PENDING_* bit, an unknown flag bit, a non-zero reserved byte,
+ *     timestamp_min, timestamp_max or now equal to 2^64-1, a non-zero timestamp_max below
+ *     timestamp_min, limit 0 — each returns TBGPU_STATUS_OK with count = matched = 0.  A NULL filter,
+ *     out_rows, out_states or result is TBGPU_STATUS_INVALID.  After a failing status the result names
+ *     no row.
+ *   The call contract of tbgpu_get_account_transfers: synchronous, drains a pending
+ *     tbgpu_commit_device_async first, a read that changes nothing (commit_timestamp, balances, log,
+ *     index, the posted groove, stats, the write-back snapshot), works on an engine a device panic
+ *     stopped, allocates nothing after tbgpu_init, legal beside an asynchronous write-back.
+ *   A node engine has the same contract: every home shard selects from its own log (a pending
+ *     transfer's posted state lives on its home), the host merges the shards' rows by timestamp under
+ *     the limit, and every shard then scans its own log for the merged rows' resolutions, side by side. */
+#define TBGPU_PENDING_OPEN     (1u << 4)  /* unresolved, not expired at `now` */
+#define TBGPU_PENDING_EXPIRED  (1u << 5)  /* unresolved, expired at `now` */
+#define TBGPU_PENDING_POSTED   (1u << 6)
+#define TBGPU_PENDING_VOIDED   (1u << 7)
+#define TBGPU_PENDING_ROWS_MAX 4095u      /* 256 B rows in one message body: 4095*256 <= 8191*128 */
+
+typedef struct tbgpu_pending_filter {   /* 64 bytes, little-endian, no padding */
+    uint64_t account_id_lo, account_id_hi; /* 0 (both words): any account */
+    uint64_t timestamp_min, timestamp_max; /* window on the PENDING record's timestamp; 0 = open */
+    uint64_t now;                          /* the clock for expiry; 0 = commit_timestamp */
+    uint32_t limit;
+    uint32_t flags;   /* TBGPU_FILTER_DEBITS | _CREDITS | _REVERSED (same bit values) | TBGPU_PENDING_* */
+    uint8_t  reserved[16];                 /* must be zero */
+} tbgpu_pending_filter;
+
+typedef struct tbgpu_pending_row {      /* 256 bytes */
+    uint8_t pending[128];     /* the bytes lookup_transfers returns for the pending transfer */
+    uint8_t resolution[128];  /* the post or void record that resolved it; all zero if none is resident */
+} tbgpu_pending_row;
+
+int tbgpu_get_pending_transfers(tbgpu_t* engine, const tbgpu_pending_filter* filter,
+                                void* out_rows, uint8_t* out_states, uint32_t out_cap_rows,
+                                tbgpu_query_result* result);
 
 /* The replica writes StateMachine.commit_timestamp itself: the header timestamp after every commit
  * (src/vsr/replica.zig:3664-3665) and the checkpoint's value on open / state sync.  The wrapper

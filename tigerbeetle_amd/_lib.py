@@ -87,6 +87,19 @@ class tbgpu_ledger_balance(ctypes.Structure):
 LEDGERS_MAX = 1024  # TBGPU_LEDGERS_MAX
 
 
+class tbgpu_pending_filter(ctypes.Structure):
+    _fields_ = [("account_id_lo", ctypes.c_uint64), ("account_id_hi", ctypes.c_uint64),
+                ("timestamp_min", ctypes.c_uint64), ("timestamp_max", ctypes.c_uint64), ("now", ctypes.c_uint64),
+                ("limit", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint8 * 16)]
+
+
+class tbgpu_pending_row(ctypes.Structure):
+    _fields_ = [("pending", ctypes.c_uint8 * 128), ("resolution", ctypes.c_uint8 * 128)]
+
+
+PENDING_ROWS_MAX = 4095  # TBGPU_PENDING_ROWS_MAX
+
+
 class tbgpu_stats(ctypes.Structure):
     _fields_ = [
         ("passes", ctypes.c_uint64),
@@ -212,6 +225,7 @@ SIGNATURES = [
     ("tbgpu_get_change_events", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_lookup_accounts_at", ctypes.c_int, [_P, _U64, _P, _U32, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_get_ledger_balances", ctypes.c_int, [_P, _U64, _P, _U32, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
+    ("tbgpu_get_pending_transfers", ctypes.c_int, [_P, _P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_query_transfers", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_query_accounts", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_bench_query_keys_max", ctypes.c_int, [_P, _U32]),

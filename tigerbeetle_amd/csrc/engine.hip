@@ -39,6 +39,7 @@
 #include "k_change_events.h"
 #include "k_asof.h"
 #include "k_ledgers.h"
+#include "k_pending.h"
 #include "checksum.h"
 
 static thread_local std::string g_err;

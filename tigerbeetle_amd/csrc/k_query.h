@@ -61,15 +61,84 @@ struct QueryFieldFilter {
     }
 };
 
+// get_pending_transfers (k_pending.h): the records whose flags say `pending`, with an account on a
+// wanted side if one is named, whose state at `now` is among the wanted ones.  The state bits are
+// TBGPU_PENDING_* (include/tbgpu.h).
+#define PENDING_OPEN (1u << 4)
+#define PENDING_EXPIRED (1u << 5)
+#define PENDING_POSTED (1u << 6)
+#define PENDING_VOIDED (1u << 7)
+#define PENDING_STATES (PENDING_OPEN | PENDING_EXPIRED | PENDING_POSTED | PENDING_VOIDED)
+
+struct QueryPendingFields {
+    u64 ts;
+    u32 timeout, flags;
+};
+
+struct QueryPendingFilter {
+    typedef QueryPendingFields Fields;
+    u64 id_lo, id_hi;    // 0 (both words): any account
+    u64 ts_min, ts_max;  // as above
+    u64 now;             // the clock for expiry
+    u32 debits, credits;
+    u32 want;            // PENDING_* bits
+    u8* states;          // [k] the kept rows' state, written by the kernel that writes the row
+    // The state a post or void arriving at `now` would find (k_validate.h, after its amount checks): the
+    // posted byte at the record's own position, then the timeout.  The expiry is a u64 sum that
+    // saturates: a wrapped one never expires.
+    __device__ u32 state(const QueryPendingFields& f, const u8* xposted, u64 pos) const {
+        const u8 st = xposted[pos];
+        if (st == POSTED_POSTED) return PENDING_POSTED;
+        if (st == POSTED_VOIDED) return PENDING_VOIDED;
+        if (f.timeout) {
+            u64 expiry = f.ts + (u64)f.timeout * 1000000000ULL;
+            if (expiry < f.ts) expiry = ~0ULL;
+            if (expiry <= now) return PENDING_EXPIRED;
+        }
+        return PENDING_OPEN;
+    }
+    // Called for a record inside the window: the account ids (chunks 1-2) are read only when an
+    // account is named, the posted byte only for a pending record that passed it.
+    __device__ bool pass(const QueryPendingFields& f, const Tables& T, u64 pos) const {
+        if (!(f.flags & TF_PENDING)) return false;
+        if ((id_lo | id_hi) != 0) {
+            const ulonglong2* c = (const ulonglong2*)&T.xlog[pos];
+            bool side = false;
+            if (debits) {
+                const ulonglong2 d = c[1];
+                side = d.x == id_lo && d.y == id_hi;
+            }
+            if (!side && credits) {
+                const ulonglong2 cr = c[2];
+                side = cr.x == id_lo && cr.y == id_hi;
+            }
+            if (!side) return false;
+        }
+        return (state(f, T.xposted, pos) & want) != 0;
+    }
+};
+
 // The 40 bytes the test needs of the record at `pos`: both account ids (bytes 16-47) and the
 // timestamp (byte 120).  COOP = false: the lane reads its own record (two 16-B loads and one 8-B
 // load, 128 B apart from its neighbours').  COOP = true: the wave reads chunks 1, 2 and 7 of its 64
 // records with neighbouring lanes on neighbouring chunks and hands them over through LDS.
 // The field filter reads chunks 5, 6 and 7 — user_data_128; user_data_64, user_data_32; ledger, code
 // and the timestamp, the last word of chunk 7 — three 16-B loads per lane, lane-per-record only.
+// The pending filter reads chunks 6 and 7 — the timeout; the flags and the timestamp — two 16-B loads
+// per lane, lane-per-record only; what else it needs it reads in its test (QueryPendingFilter::pass).
 template <bool COOP, typename F>
 __device__ static inline typename F::Fields tb_query_fields(const Tables& T, u64 tile0, u64 n, u64* s_raw) {
-    if constexpr (std::is_same<F, QueryFieldFilter>::value) {
+    if constexpr (std::is_same<F, QueryPendingFilter>::value) {
+        static_assert(!COOP, "the pending filter has no cooperative load shape");
+        QueryPendingFields v{0, 0, 0};
+        const u64 pos = tile0 + threadIdx.x;
+        if (pos < n) {
+            const ulonglong2* c = (const ulonglong2*)&T.xlog[pos];
+            const ulonglong2 b = c[6], d = c[7];
+            v.timeout = (u32)(b.y >> 32), v.flags = (u32)(d.x >> 48), v.ts = d.y;
+        }
+        return v;
+    } else if constexpr (std::is_same<F, QueryFieldFilter>::value) {
         static_assert(!COOP, "the field filter has no cooperative load shape");
         QueryFieldVals v{0, 0, 0, 0, 0, 0, 0};
         const u64 pos = tile0 + threadIdx.x;
@@ -116,7 +185,11 @@ __device__ static inline typename F::Fields tb_query_fields(const Tables& T, u64
 template <typename F>
 __device__ static inline bool tb_query_hit(const Tables& T, const F& flt, u64 pos, u64 n, const typename F::Fields& f) {
     if (pos >= n || f.ts == 0 || f.ts < flt.ts_min || f.ts > flt.ts_max) return false;
-    if (!flt.pass(f)) return false;
+    if constexpr (std::is_same<F, QueryPendingFilter>::value) {
+        if (!flt.pass(f, T, pos)) return false;
+    } else {
+        if (!flt.pass(f)) return false;
+    }
     const u64* idw = (const u64*)&T.xlog[pos];
     const u64 lo = idw[0], hi = idw[1];
     if (tb_id_reserved(lo, hi)) return false;
@@ -247,7 +320,10 @@ __global__ __launch_bounds__(QUERY_THREADS) void tb_query_scatter(Tables T, F fl
     const u64 rank = b0 + tb_query_tile_rank(hit, s_cnt);
     if (!hit || rank < lo || rank >= hi) return;
     const u64 dst = reversed ? total - 1 - rank : rank;
-    if (dst < k) *(Transfer*)(out + dst * 128) = T.xlog[pos];
+    if (dst < k) {
+        *(Transfer*)(out + dst * 128) = T.xlog[pos];
+        if constexpr (std::is_same<F, QueryPendingFilter>::value) flt.states[dst] = (u8)flt.state(f, T.xposted, pos);
+    }
 }
 
 // Unordered log, one round: the matches of tiles [wg0, wg0 + gridDim.x) as {timestamp, position}

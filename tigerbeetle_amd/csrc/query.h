@@ -1,6 +1,6 @@
 // query.h — the host side of the queries (include/tbgpu.h): get_account_transfers and its batched form
 // get_account_transfers_many, get_account_balances, query_transfers, query_accounts,
-// get_change_events, lookup_accounts_at and get_ledger_balances; their buffers, made at tbgpu_init, and their entry points.  Included by engine.hip after the engine's own helpers and before node.h.
+// get_change_events, lookup_accounts_at, get_ledger_balances and get_pending_transfers; their buffers, made at tbgpu_init, and their entry points.  Included by engine.hip after the engine's own helpers and before node.h.
 //
 // Every query is written once, over a list of engines (QueryCall): the one engine, or a node's shards.
 // A transfer lives on its home shard only and an account is answered by its owner only, so every
@@ -33,6 +33,8 @@ struct QueryBufs {
     QueryFilter F{};
     QueryFieldFilter FF{};   // by_fields: tbgpu_query_transfers' predicate instead
     bool by_fields = false;
+    QueryPendingFilter FP{};  // by_pending: tbgpu_get_pending_transfers' predicate instead
+    bool by_pending = false;
     u32 k = 0;
     bool reversed = false;
     u64 n = 0;
@@ -137,6 +139,22 @@ struct LedgerBufs {
     u64* h_bins = nullptr;  // pinned mirror
 };
 
+// tbgpu_get_pending_transfers (k_pending.h): the kept rows' states, the set of the resolved rows' ids,
+// the ids and the resolution slots, on the device and pinned; made by query_init and shared with
+// nothing.  The rows themselves are chosen through QueryBufs.
+struct PendingBufs {
+    u8* d_states = nullptr;   // [PENDING_ROWS_MAX] the kept rows' states, written with the rows
+    u8* h_states = nullptr;   // pinned mirror
+    u8* h_rows = nullptr;     // pinned [PENDING_ROWS_MAX] this engine's kept records, before they are placed into the rows
+    u32* d_set = nullptr;     // [tb_change_set_slots(PENDING_ROWS_MAX)] the set's entries
+    u32* h_set = nullptr;     // pinned: the host builds it here (a node copies it into every shard's)
+    u64* d_ids = nullptr;     // [PENDING_ROWS_MAX][2] the resolved rows' ids by index
+    u64* h_ids = nullptr;     // pinned, likewise
+    u8* d_slots = nullptr;    // [PENDING_ROWS_MAX] the resolving records by index; zero: none on this engine
+    u8* h_slots = nullptr;    // pinned mirror
+    u32* h_row_of = nullptr;  // pinned [PENDING_ROWS_MAX] the row an index stands for
+};
+
 // One engine's query buffers (tbgpu::qs), in the order query_init makes them.
 struct QueryState {
     QueryBufs q;
@@ -146,6 +164,7 @@ struct QueryState {
     QueryManyBufs qm;
     LookupAtBufs ql;
     LedgerBufs qg;
+    PendingBufs qp;
 };
 
 // Called by engine_init on the engine's device, after every other buffer.  The buffers go into the
@@ -249,6 +268,20 @@ static int query_init(tbgpu* E) {
         HIPCK(tbMalloc(E->own, &G.d_bins, bin_bytes));
         HIPCK(tbHostMalloc(E->own, &G.h_bins, bin_bytes, hipHostMallocDefault));
     }
+    {  // tbgpu_get_pending_transfers: the states, the kept records, the set, the ids, the resolution slots
+        PendingBufs& P = E->qs->qp;
+        const u64 nr = PENDING_ROWS_MAX, set_bytes = (u64)tb_change_set_slots(PENDING_ROWS_MAX) * 4;
+        HIPCK(tbMalloc(E->own, &P.d_states, nr + 1));
+        HIPCK(tbHostMalloc(E->own, &P.h_states, nr + 1, hipHostMallocDefault));
+        HIPCK(tbHostMalloc(E->own, &P.h_rows, nr * 128, hipHostMallocDefault));
+        HIPCK(tbMalloc(E->own, &P.d_set, set_bytes));
+        HIPCK(tbHostMalloc(E->own, &P.h_set, set_bytes, hipHostMallocDefault));
+        HIPCK(tbMalloc(E->own, &P.d_ids, nr * 16));
+        HIPCK(tbHostMalloc(E->own, &P.h_ids, nr * 16, hipHostMallocDefault));
+        HIPCK(tbMalloc(E->own, &P.d_slots, nr * 128));
+        HIPCK(tbHostMalloc(E->own, &P.h_slots, nr * 128, hipHostMallocDefault));
+        HIPCK(tbHostMalloc(E->own, &P.h_row_of, nr * 4, hipHostMallocDefault));
+    }
     return TBGPU_STATUS_OK;
 }
 
@@ -349,8 +382,9 @@ static int query_collect_all(const QueryCall& c, bool reversed, u8* out, tbgpu_q
 // {total, ordered} word); query_collect waits, copies the answer's records, and runs the exact path
 // of a log out of timestamp order when the scan found one.  The stream is drained before (a pending
 // tbgpu_commit_device_async), so log_next is the log's end and nothing writes beside the scan.
-static void query_keep_filter(QueryBufs& Q, const QueryFilter& F) { Q.F = F, Q.by_fields = false; }
-static void query_keep_filter(QueryBufs& Q, const QueryFieldFilter& F) { Q.FF = F, Q.by_fields = true; }
+static void query_keep_filter(QueryBufs& Q, const QueryFilter& F) { Q.F = F, Q.by_fields = false, Q.by_pending = false; }
+static void query_keep_filter(QueryBufs& Q, const QueryFieldFilter& F) { Q.FF = F, Q.by_fields = true, Q.by_pending = false; }
+static void query_keep_filter(QueryBufs& Q, const QueryPendingFilter& F) { Q.FP = F, Q.by_fields = false, Q.by_pending = true; }
 
 template <typename FILTER>
 static int query_enqueue(tbgpu* E, const FILTER& F, u32 k, bool reversed) {
@@ -427,7 +461,10 @@ static int query_collect(tbgpu* E, u8* out, u32* count, u64* matched) {
             const u64 b1 = (u64)(std::upper_bound(Q.h_base + b0, Q.h_base + nb + 1, Q.h_base[b0] + Q.keys_max) - Q.h_base) - 1;
             const u64 keys = Q.h_base[b1] - Q.h_base[b0];
             if (b1 <= b0 || keys > Q.keys_max) return fail(TBGPU_STATUS_PANIC, "query: a round of %llu keys", (unsigned long long)keys);
-            if (Q.by_fields) {
+            if (Q.by_pending) {
+                hipLaunchKernelGGL(tb_query_keys<QueryPendingFilter>, dim3((unsigned)(b1 - b0)), dim3(QUERY_THREADS), 0, E->stream,
+                                   E->T, Q.FP, Q.n, b0, Q.d_counts, Q.d_base, Q.d_keys, (u64)Q.keys_max);
+            } else if (Q.by_fields) {
                 hipLaunchKernelGGL(tb_query_keys<QueryFieldFilter>, dim3((unsigned)(b1 - b0)), dim3(QUERY_THREADS), 0, E->stream,
                                    E->T, Q.FF, Q.n, b0, Q.d_counts, Q.d_base, Q.d_keys, (u64)Q.keys_max);
             } else {
@@ -446,10 +483,16 @@ static int query_collect(tbgpu* E, u8* out, u32* count, u64* matched) {
         if (best.size() != m) return fail(TBGPU_STATUS_PANIC, "query: %zu keys for %u matches", best.size(), m);
         for (u32 i = 0; i < m; i++) Q.h_keys[i] = best[i].second;
         HIPCK(hipMemcpyAsync(Q.d_keys, Q.h_keys, (u64)m * 8, hipMemcpyHostToDevice, E->stream));
-        hipLaunchKernelGGL(tb_query_gather, dim3((m + QUERY_THREADS - 1) / QUERY_THREADS), dim3(QUERY_THREADS), 0, E->stream,
-                           E->T, Q.d_keys, m, Q.n, Q.d_out);
+        if (Q.by_pending) {  // the records and, beside them, their states
+            hipLaunchKernelGGL(tb_pending_gather, dim3((m + QUERY_THREADS - 1) / QUERY_THREADS), dim3(QUERY_THREADS), 0, E->stream,
+                               E->T, Q.FP, (const u64*)Q.d_keys, m, Q.n, Q.d_out);
+        } else {
+            hipLaunchKernelGGL(tb_query_gather, dim3((m + QUERY_THREADS - 1) / QUERY_THREADS), dim3(QUERY_THREADS), 0, E->stream,
+                               E->T, Q.d_keys, m, Q.n, Q.d_out);
+        }
         HIPCK(hipGetLastError());
     }
+    if (Q.by_pending) HIPCK(hipMemcpyAsync(E->qs->qp.h_states, Q.FP.states, m, hipMemcpyDeviceToHost, E->stream));
     HIPCK(hipMemcpyAsync(out, Q.d_out, (u64)m * 128, hipMemcpyDeviceToHost, E->stream));
     HIPCK(hipStreamSynchronize(E->stream));
     *count = m;
@@ -1353,5 +1396,153 @@ extern "C" int tbgpu_get_ledger_balances(tbgpu_t* E, uint64_t timestamp, const u
     });
     if (st) return query_end(result, st);
     ledgers_rows(c, ledgers, n, slots, out_cap_rows, (u8*)out, result);
+    return TBGPU_STATUS_OK;
+}
+
+// ---- get_pending_transfers (k_pending.h, include/tbgpu.h) -----------------------------------------
+// The selection is the log scan under QueryPendingFilter: every listed engine's kept records land in
+// its own pinned h_rows and their states, written on the device beside them, in its h_states; the
+// host places one engine's, or a node's merged by timestamp, into the caller's rows.  Then, only when
+// a placed row is posted or voided, the join: the set of those rows' ids, built in the first engine's
+// pinned buffer (change_set_insert; a node copies it into every shard's), every engine's
+// tb_pending_resolutions over its own log on its own stream, side by side, and the slots into the rows.
+static bool pending_filter_valid(const tbgpu_pending_filter* f) {
+    const u32 sides = TBGPU_FILTER_DEBITS | TBGPU_FILTER_CREDITS;
+    if ((f->account_id_lo & f->account_id_hi) == ~0ULL) return false;
+    if ((f->account_id_lo | f->account_id_hi) != 0 && !(f->flags & sides)) return false;
+    if (!(f->flags & PENDING_STATES)) return false;
+    if (f->flags & ~(sides | TBGPU_FILTER_REVERSED | PENDING_STATES)) return false;
+    if (f->timestamp_min == ~0ULL || f->timestamp_max == ~0ULL || f->now == ~0ULL) return false;
+    if (f->timestamp_max != 0 && f->timestamp_max < f->timestamp_min) return false;
+    if (f->limit == 0) return false;
+    for (u8 b : f->reserved) if (b) return false;
+    return true;
+}
+
+// The first k of the engines' kept records by timestamp (the last k, newest first, under `reversed`)
+// into the rows' pending halves, their states beside them: query_merge with the state carried along.
+static u32 pending_place_rows(const QueryCall& c, const u32* cnt, bool reversed, u8* rows, u8* states) {
+    u32 at[NODE_WORLD_MAX] = {};
+    u32 w = 0;
+    for (; w < c.k; w++) {
+        u32 pick = c.world;
+        u64 best = 0;
+        for (u32 d = 0; d < c.world; d++) {
+            if (at[d] == cnt[d]) continue;
+            const u64 ts = change_row_word(c.Es[d]->qs->qp.h_rows + (u64)at[d] * 128, 15);
+            if (pick == c.world || (reversed ? ts > best : ts < best)) pick = d, best = ts;
+        }
+        if (pick == c.world) break;
+        const PendingBufs& D = c.Es[pick]->qs->qp;
+        memcpy(rows + (u64)w * 256, D.h_rows + (u64)at[pick] * 128, 128);
+        states[w] = D.h_states[at[pick]];
+        at[pick]++;
+    }
+    return w;
+}
+
+// rows: m placed rows with their states.  Fills every row's resolution half; returns through
+// *complete whether every posted or voided row found its resolving record.
+static int pending_resolutions(const QueryCall& c, u32 m, u8* rows, const u8* states, bool* complete) {
+    PendingBufs& P = c.Es[0]->qs->qp;
+    u32 resolved = 0;
+    for (u32 i = 0; i < m; i++) resolved += (states[i] & (PENDING_POSTED | PENDING_VOIDED)) != 0;
+    for (u32 i = 0; i < m; i++) memset(rows + (u64)i * 256 + 128, 0, 128);
+    *complete = true;
+    if (resolved == 0) return TBGPU_STATUS_OK;
+    const u32 slots = tb_change_set_slots(resolved), mask = slots - 1;
+    memset(P.h_set, 0, (u64)slots * 4);
+    u32 nr = 0;
+    u64 ts_floor = ~0ULL;  // the oldest resolved row: nothing at or below it resolves any of them
+    for (u32 i = 0; i < m; i++) {
+        if (!(states[i] & (PENDING_POSTED | PENDING_VOIDED))) continue;
+        const u8* r = rows + (u64)i * 256;
+        P.h_row_of[change_set_insert(P.h_set, mask, P.h_ids, &nr, change_row_word(r, 0), change_row_word(r, 1))] = i;
+        ts_floor = std::min(ts_floor, change_row_word(r, 15));
+    }
+    const int status = query_side_by_side(c.Es, c.world, [&](u32 d) -> int {
+        tbgpu* E = c.Es[d];
+        PendingBufs& D = E->qs->qp;
+        HIPCK(hipSetDevice(E->device));
+        if (d) {
+            memcpy(D.h_set, P.h_set, (u64)slots * 4);
+            memcpy(D.h_ids, P.h_ids, (u64)nr * 16);
+        }
+        HIPCK(hipMemcpyAsync(D.d_set, D.h_set, (u64)slots * 4, hipMemcpyHostToDevice, E->stream));
+        HIPCK(hipMemcpyAsync(D.d_ids, D.h_ids, (u64)nr * 16, hipMemcpyHostToDevice, E->stream));
+        HIPCK(hipMemsetAsync(D.d_slots, 0, (u64)nr * 128, E->stream));
+        const u64 n = E->log_next, per = (u64)PENDING_THREADS * PENDING_TILES, nb = (n + per - 1) / per;
+        if (nb) {
+            hipLaunchKernelGGL(tb_pending_resolutions, dim3((unsigned)nb), dim3(PENDING_THREADS), (size_t)slots * 4, E->stream, E->T, n,
+                               ts_floor, (const u32*)D.d_set, mask, (const u64*)D.d_ids, D.d_slots);
+            HIPCK(hipGetLastError());
+        }
+        HIPCK(hipMemcpyAsync(D.h_slots, D.d_slots, (u64)nr * 128, hipMemcpyDeviceToHost, E->stream));
+        return TBGPU_STATUS_OK;
+    });
+    if (status) return status;
+    // A slot is filled by at most one shard: the home of the resolving record's own id.
+    for (u32 s = 0; s < nr; s++) {
+        bool found = false;
+        for (u32 d = 0; d < c.world && !found; d++) {
+            const u8* rec = c.Es[d]->qs->qp.h_slots + (u64)s * 128;
+            if (change_row_word(rec, 15) == 0) continue;
+            memcpy(rows + (u64)P.h_row_of[s] * 256 + 128, rec, 128);
+            found = true;
+        }
+        if (!found) *complete = false;
+    }
+    return TBGPU_STATUS_OK;
+}
+
+extern "C" int tbgpu_get_pending_transfers(tbgpu_t* E, const tbgpu_pending_filter* filter, void* out_rows, uint8_t* out_states,
+                                           uint32_t out_cap_rows, tbgpu_query_result* result) {
+    static_assert(sizeof(tbgpu_pending_filter) == 64 && sizeof(tbgpu_pending_row) == 256, "the filter is 64 bytes, a row 256");
+    static_assert(PENDING_OPEN == TBGPU_PENDING_OPEN && PENDING_EXPIRED == TBGPU_PENDING_EXPIRED &&
+                  PENDING_POSTED == TBGPU_PENDING_POSTED && PENDING_VOIDED == TBGPU_PENDING_VOIDED &&
+                  PENDING_ROWS_MAX == TBGPU_PENDING_ROWS_MAX, "k_query.h's and k_pending.h's constants are the header's");
+    API_ENTER(E, false);
+    if (!filter || !out_rows || !out_states || !result) {
+        return fail(TBGPU_STATUS_INVALID, "get_pending_transfers: a NULL filter, out_rows, out_states or result");
+    }
+    QueryCall c;
+    result->count = 0;
+    result->matched = 0;
+    result->complete = query_engines(E, true, &c);
+    c.k = std::min<u32>(std::min<u32>(filter->limit, out_cap_rows), PENDING_ROWS_MAX);
+    if (!pending_filter_valid(filter)) return TBGPU_STATUS_OK;
+    const bool reversed = (filter->flags & TBGPU_FILTER_REVERSED) != 0;
+    QueryPendingFilter F{};
+    F.id_lo = filter->account_id_lo;
+    F.id_hi = filter->account_id_hi;
+    F.ts_min = filter->timestamp_min;
+    F.ts_max = filter->timestamp_max ? filter->timestamp_max : ~0ULL;
+    F.now = filter->now ? filter->now : tbgpu_commit_timestamp(E);
+    F.debits = (filter->flags & TBGPU_FILTER_DEBITS) != 0;
+    F.credits = (filter->flags & TBGPU_FILTER_CREDITS) != 0;
+    F.want = filter->flags & PENDING_STATES;
+    for (u32 d = 0; d < c.world; d++) {
+        F.states = c.Es[d]->qs->qp.d_states;
+        const int st = query_enqueue(c.Es[d], F, c.k, reversed);
+        if (st) return query_end(result, st);
+    }
+    // Every engine is waited for, whatever an earlier one returned.
+    u32 cnt[NODE_WORLD_MAX] = {};
+    u64 matched = 0;
+    int status = TBGPU_STATUS_OK;
+    for (u32 d = 0; d < c.world; d++) {
+        u64 m = 0;
+        const int st = query_collect(c.Es[d], c.Es[d]->qs->qp.h_rows, &cnt[d], &m);
+        if (st && status == TBGPU_STATUS_OK) status = st;
+        matched += m;
+    }
+    if (status) return query_end(result, status);
+    const u32 m = pending_place_rows(c, cnt, reversed, (u8*)out_rows, out_states);
+    bool resolved = true;
+    if (m) status = pending_resolutions(c, m, (u8*)out_rows, out_states, &resolved);
+    if (status) return query_end(result, status);
+    if (!resolved) result->complete = 0;
+    result->count = m;
+    result->matched = matched;
     return TBGPU_STATUS_OK;
 }

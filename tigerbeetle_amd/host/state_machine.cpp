@@ -321,6 +321,13 @@ tbgpu_query_result StateMachine::get_ledger_balances(uint64_t timestamp, const u
     return r;
 }
 
+tbgpu_query_result StateMachine::get_pending_transfers(const tbgpu_pending_filter& filter, void* out_rows, uint8_t* out_states,
+                                                       uint32_t out_cap_rows) {
+    tbgpu_query_result r{};
+    check(tbgpu_get_pending_transfers(engine_, &filter, out_rows, out_states, out_cap_rows, &r), "get_pending_transfers");
+    return r;
+}
+
 tbgpu_query_result StateMachine::query_transfers(const tbgpu_query_filter& filter, void* out, uint32_t out_cap_records) {
     tbgpu_query_result r{};
     check(tbgpu_query_transfers(engine_, &filter, out, out_cap_records, &r), "query_transfers");

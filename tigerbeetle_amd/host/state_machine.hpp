@@ -272,6 +272,16 @@ public:
     tbgpu_query_result get_ledger_balances(uint64_t timestamp, const uint32_t* ledgers, uint32_t n, void* out,
                                            uint32_t out_cap_rows);
 
+    // The two-phase transfers of a window with their state (tbgpu_get_pending_transfers; a read, and no
+    // reference operation behind it): the pending transfers whose state at filter.now (0: the commit
+    // timestamp) is among the filter's TBGPU_PENDING_* bits, of one account on the wanted sides or of
+    // any (account id 0), by the pending record's timestamp.  out_rows: tbgpu_pending_row, 256 bytes a
+    // row — the pending transfer and the post or void record that resolved it, zero if none is
+    // resident; out_states: one TBGPU_PENDING_* bit a row.  At most TBGPU_PENDING_ROWS_MAX rows.
+    // result.complete == 0: transfers were evicted or a returned resolved row lacks its resolution.
+    tbgpu_query_result get_pending_transfers(const tbgpu_pending_filter& filter, void* out_rows, uint8_t* out_states,
+                                             uint32_t out_cap_rows);
+
     // The field-filter queries (tbgpu_query_transfers / tbgpu_query_accounts; reads, not commits): the
     // resident transfers, or the accounts, whose user_data_128 / user_data_64 / user_data_32 / ledger /
     // code equal the filter's non-zero fields, by timestamp (newest first under TBGPU_QUERY_REVERSED),

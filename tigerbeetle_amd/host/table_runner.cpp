@@ -311,8 +311,10 @@ std::string run_table(tb::StateMachine& sm, const std::string& text) {
 // timestamp and n ids}, answered by lookup_accounts_at (the records are accounts).
 // --query-ledgers (tests/test_gpu_ledger_balances_cpp.py): the prepares ending in {0, 0, 8 + n * 4, a u64
 // timestamp and n u32 ledgers}, answered by get_ledger_balances (the records are tbgpu_ledger_balance rows).
+// --query-pending (tests/test_gpu_pending_cpp.py): the prepares ending in {0, 0, 64, a tbgpu_pending_filter},
+// answered by get_pending_transfers: the result, the rows (tbgpu_pending_row) and then a state byte a row.
 enum QueryKind { ACCOUNT_TRANSFERS, ACCOUNT_BALANCES, QUERY_TRANSFERS, QUERY_ACCOUNTS, CHANGE_EVENTS, ACCOUNT_TRANSFERS_MANY, ACCOUNTS_AT,
-                 LEDGER_BALANCES };
+                 LEDGER_BALANCES, PENDING_TRANSFERS };
 
 int run_query(tb::StateMachine& sm, QueryKind kind, const char* in_path, const char* out_path) {
     std::ifstream in(in_path, std::ios::binary);
@@ -391,6 +393,21 @@ int run_query(tb::StateMachine& sm, QueryKind kind, const char* in_path, const c
         printf("query: %u of %llu rows, complete %u\n", r.count, (unsigned long long)r.matched, r.complete);
         return o ? 0 : 2;
     }
+    if (kind == PENDING_TRANSFERS) {
+        tbgpu_pending_filter pf;
+        if (body.size() != sizeof(pf)) {
+            fprintf(stderr, "%s: a pending filter is %zu bytes\n", in_path, sizeof(pf));
+            return 2;
+        }
+        memcpy(&pf, body.data(), sizeof(pf));
+        std::vector<uint8_t> rows((size_t)TBGPU_PENDING_ROWS_MAX * sizeof(tbgpu_pending_row)), states(TBGPU_PENDING_ROWS_MAX);
+        const tbgpu_query_result r = sm.get_pending_transfers(pf, rows.data(), states.data(), TBGPU_PENDING_ROWS_MAX);
+        std::ofstream o(out_path, std::ios::binary);
+        o.write((const char*)&r, sizeof(r)).write((const char*)rows.data(), (size_t)r.count * sizeof(tbgpu_pending_row));
+        o.write((const char*)states.data(), r.count);
+        printf("query: %u of %llu rows, complete %u\n", r.count, (unsigned long long)r.matched, r.complete);
+        return o ? 0 : 2;
+    }
     if (body.size() != sizeof(f)) {
         fprintf(stderr, "%s: a filter is %zu bytes\n", in_path, sizeof(f));
         return 2;
@@ -420,8 +437,9 @@ int main(int argc, char** argv) {
     const bool many = argc > 1 && std::string(argv[1]) == "--query-many";
     const bool at = argc > 1 && std::string(argv[1]) == "--query-accounts-at";
     const bool ledgers = argc > 1 && std::string(argv[1]) == "--query-ledgers";
-    const bool query = fields || balances || changes || many || at || ledgers || (argc > 1 && std::string(argv[1]) == "--query");
-    QueryKind kind = balances ? ACCOUNT_BALANCES : changes ? CHANGE_EVENTS : many ? ACCOUNT_TRANSFERS_MANY : at ? ACCOUNTS_AT : ledgers ? LEDGER_BALANCES : ACCOUNT_TRANSFERS;
+    const bool pending = argc > 1 && std::string(argv[1]) == "--query-pending";
+    const bool query = fields || balances || changes || many || at || ledgers || pending || (argc > 1 && std::string(argv[1]) == "--query");
+    QueryKind kind = balances ? ACCOUNT_BALANCES : changes ? CHANGE_EVENTS : many ? ACCOUNT_TRANSFERS_MANY : at ? ACCOUNTS_AT : ledgers ? LEDGER_BALANCES : pending ? PENDING_TRANSFERS : ACCOUNT_TRANSFERS;
     const char* self = argv[0];
     if (fields && argc > 2) {
         const std::string which = argv[2];
@@ -437,8 +455,9 @@ int main(int argc, char** argv) {
                 "       %s --query-change-events <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-accounts-at <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-ledgers <prepares.bin> <answer.bin> [device]\n"
+                "       %s --query-pending <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-fields <transfers|accounts> <prepares.bin> <answer.bin> [device]\n",
-                self, self, self, self, self, self, self, self);
+                self, self, self, self, self, self, self, self, self);
         return 2;
     }
     if (query) {

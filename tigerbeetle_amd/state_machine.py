@@ -23,7 +23,7 @@ import numpy as np
 
 from . import _lib
 from .types import (ACCOUNT_BALANCE_DTYPE, ACCOUNT_DTYPE, ACCOUNT_FILTER_DTYPE, BATCH_MAX, CHANGE_EVENT_DTYPE, CHANGE_EVENTS_FILTER_DTYPE,
-                    CHANGE_EVENTS_MAX, LEDGER_BALANCE_DTYPE, LEDGERS_MAX, FILTER_CREDITS, FILTER_DEBITS, FILTER_REVERSED, pack_change_events_filter, QUERY_FILTER_DTYPE, QUERY_REVERSED, TRANSFER_DTYPE, U64_MAX, Operation)
+                    CHANGE_EVENTS_MAX, LEDGER_BALANCE_DTYPE, LEDGERS_MAX, PENDING_FILTER_DTYPE, PENDING_ROW_DTYPE, PENDING_ROWS_MAX, PENDING_STATES, FILTER_CREDITS, FILTER_DEBITS, FILTER_REVERSED, pack_change_events_filter, QUERY_FILTER_DTYPE, QUERY_REVERSED, TRANSFER_DTYPE, U64_MAX, Operation)
 
 
 @dataclass
@@ -405,6 +405,57 @@ class Engine:
         _lib.check(self.lib.tbgpu_get_ledger_balances(self.h, int(timestamp), src, n, out.ctypes.data, cap, ctypes.byref(res)))
         return out[:res.count], int(res.matched), bool(res.complete)
 
+    PENDING_ROWS_MAX = PENDING_ROWS_MAX  # TBGPU_PENDING_ROWS_MAX
+
+    @staticmethod
+    def pending_filter(account_id=0, states=PENDING_STATES, debits=True, credits=True, reversed=False, timestamp_min=0,
+                       timestamp_max=0, now=0, limit=PENDING_ROWS_MAX):
+        """The 64 bytes of a tbgpu_pending_filter (PENDING_FILTER_DTYPE)."""
+        account_id, states = int(account_id), int(states)
+        if account_id < 0 or account_id >> 128:
+            raise ValueError("an account id is 128 bits")
+        if states & ~PENDING_STATES:
+            raise ValueError("states is a mask of PENDING_OPEN, PENDING_EXPIRED, PENDING_POSTED and PENDING_VOIDED")
+        for name, v in (("timestamp_min", timestamp_min), ("timestamp_max", timestamp_max), ("now", now)):
+            if int(v) < 0 or int(v) >> 64:
+                raise ValueError("%s is 64 bits" % name)
+        if int(limit) < 0 or int(limit) >> 32:
+            raise ValueError("limit is 32 bits")
+        f = np.zeros(1, dtype=PENDING_FILTER_DTYPE)
+        f["account_id_lo"], f["account_id_hi"] = account_id & U64_MAX, account_id >> 64
+        f["timestamp_min"], f["timestamp_max"], f["now"], f["limit"] = timestamp_min, timestamp_max, now, limit
+        f["flags"] = (states | (FILTER_DEBITS if debits else 0) | (FILTER_CREDITS if credits else 0)
+                      | (FILTER_REVERSED if reversed else 0))
+        return f.tobytes()
+
+    def get_pending_transfers(self, account_id=0, *, states=PENDING_STATES, debits=True, credits=True, reversed=False,
+                              timestamp_min=0, timestamp_max=0, now=0, limit=PENDING_ROWS_MAX, out_cap_rows=None):
+        """The resident two-phase transfers with their state (tbgpu_get_pending_transfers): those of
+        `account_id` on the wanted sides (0: any account) whose state at `now` (0: commit_timestamp) is
+        in the mask `states`, by the pending record's timestamp, newest first under `reversed`.
+        Returns (rows ndarray of PENDING_ROW_DTYPE, states ndarray of u8 — one PENDING_* bit a row,
+        matched, complete); a row's `resolution` is the post or void record that resolved it, zero if
+        none is resident; `complete` is False once transfers were evicted or a returned posted or
+        voided row lacks its resolution.  An invalid filter matches nothing."""
+        f = self.pending_filter(account_id, states, debits, credits, reversed, timestamp_min, timestamp_max, now, limit)
+        return self.get_pending_transfers_raw(f, out_cap_rows)
+
+    def get_pending_transfers_raw(self, filter_bytes, out_cap_rows=None):
+        """The same query from the 64 bytes of a tbgpu_pending_filter (PENDING_FILTER_DTYPE)."""
+        filter_bytes = bytes(filter_bytes)
+        if len(filter_bytes) != PENDING_FILTER_DTYPE.itemsize:
+            raise ValueError("a pending filter is %d bytes" % PENDING_FILTER_DTYPE.itemsize)
+        limit = int(np.frombuffer(filter_bytes, dtype=PENDING_FILTER_DTYPE)["limit"][0])
+        cap = min(limit, self.PENDING_ROWS_MAX) if out_cap_rows is None else int(out_cap_rows)
+        if cap < 0 or cap >> 32:
+            raise ValueError("out_cap_rows is 32 bits")
+        rows = np.zeros(max(cap, 1), dtype=PENDING_ROW_DTYPE)
+        states = np.zeros(max(cap, 1), dtype=np.uint8)
+        res = _lib.tbgpu_query_result()
+        src = ctypes.create_string_buffer(filter_bytes, len(filter_bytes))
+        _lib.check(self.lib.tbgpu_get_pending_transfers(self.h, src, rows.ctypes.data, states.ctypes.data, cap, ctypes.byref(res)))
+        return rows[:res.count], states[:res.count], int(res.matched), bool(res.complete)
+
     @staticmethod
     def query_filter(user_data_128=0, user_data_64=0, user_data_32=0, ledger=0, code=0, *, reversed=False,
                      timestamp_min=0, timestamp_max=0, limit=8190):
@@ -781,6 +832,10 @@ class StateMachine:
     def get_ledger_balances(self, ledgers, timestamp=0, out_cap_rows=None):
         """A trial balance per ledger as of a timestamp (Engine.get_ledger_balances): a read, not a commit."""
         return self.engine.get_ledger_balances(ledgers, timestamp, out_cap_rows)
+
+    def get_pending_transfers(self, account_id=0, **filter):
+        """The two-phase transfers with their state (Engine.get_pending_transfers): a read, not a commit."""
+        return self.engine.get_pending_transfers(account_id, **filter)
 
     def query_transfers(self, **filter):
         """The field-filter query over transfers (Engine.query_transfers): a read, not a commit."""

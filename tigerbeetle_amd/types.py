@@ -121,6 +121,17 @@ LEDGER_BALANCE_DTYPE = np.dtype(
 assert LEDGER_BALANCE_DTYPE.itemsize == 128
 LEDGERS_MAX = 1024
 
+# tbgpu_pending_filter and tbgpu_pending_row (include/tbgpu.h tbgpu_get_pending_transfers): 64 and 256
+# bytes, no padding; a row is the pending transfer and the post or void record that resolved it.
+PENDING_FILTER_DTYPE = np.dtype(
+    _u128("account_id") + [("timestamp_min", "<u8"), ("timestamp_max", "<u8"), ("now", "<u8"), ("limit", "<u4"),
+                           ("flags", "<u4"), ("reserved", "u1", (16,))])
+PENDING_ROW_DTYPE = np.dtype([("pending", TRANSFER_DTYPE), ("resolution", TRANSFER_DTYPE)])
+assert PENDING_FILTER_DTYPE.itemsize == 64 and PENDING_ROW_DTYPE.itemsize == 256
+PENDING_OPEN, PENDING_EXPIRED, PENDING_POSTED, PENDING_VOIDED = 1 << 4, 1 << 5, 1 << 6, 1 << 7
+PENDING_STATES = PENDING_OPEN | PENDING_EXPIRED | PENDING_POSTED | PENDING_VOIDED
+PENDING_ROWS_MAX = 4095
+
 # tbgpu_query_filter (include/tbgpu.h tbgpu_query_transfers / tbgpu_query_accounts): 64 bytes, no padding.
 QUERY_FILTER_DTYPE = np.dtype(
     _u128("user_data_128") + [("user_data_64", "<u8"), ("user_data_32", "<u4"), ("ledger", "<u4"), ("code", "<u2"),

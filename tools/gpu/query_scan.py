@@ -1,7 +1,7 @@
 """The account-filter scan (tbgpu_get_account_transfers, csrc/k_query.h) over a 16M-transfer log (2 GB)
 against a device-to-device copy of the same log range, in one process.
 
-usage: python tools/gpu/query_scan.py [transfers] [runs] [--only account|fields|balances|change_events|many|asof|ledgers]
+usage: python tools/gpu/query_scan.py [transfers] [runs] [--only account|fields|balances|change_events|many|asof|ledgers|pending]
 
 The log is built by the device generator, committed in place (the way tools/gpu/device_pass.py builds
 a pass): once with uniform C2 ids, where the queried account is a cold one (a few dozen matches), and
@@ -48,6 +48,14 @@ ledger-only all-match filter and a device-to-device copy of the bytes the table 
 and 64 B a live account); query_transfers with an all-zero filter, timestamp_min = T + 1 and limit 1,
 which takes the same liveness probe on every record of the window.  Then, on a second engine without
 a log, the same table with its accounts spread over 2 and over 1,024 ledgers, every ledger asked.
+
+`--only pending` (tbgpu_get_pending_transfers) fills the log with the C4 shape (chains,
+two-phase transfers with timeouts, 2 s gaps), so that open, expired, posted and voided rows all exist,
+and times the C call alone, into buffers made once, beside query_transfers with an all-zero filter over
+the same window in the same process: the selection alone (any account, OPEN | EXPIRED: no row is
+resolved, so no join runs), any account and all four states, the join with 4,095 resolved rows and with
+one (POSTED | VOIDED, ascending: the whole log is newer than the oldest row; newest first: only the
+log's end is), and one named account.
 """
 import json
 import os
@@ -502,11 +510,89 @@ def measure_ledgers():
     return out
 
 
+def measure_pending():
+    """get_pending_transfers beside query_transfers over the same window, on a C4 log, in one process."""
+    import ctypes
+
+    from tests.harness.configs import SETTINGS
+    from tigerbeetle_amd import _lib
+    from tigerbeetle_amd.types import (PENDING_EXPIRED, PENDING_OPEN, PENDING_POSTED, PENDING_ROW_DTYPE, PENDING_STATES,
+                                       PENDING_VOIDED)
+    os.environ["TBGPU_QUERY_COOP"] = "0"
+    e = Engine(Options(accounts_max=n_acct, transfers_max=n_xfer, pass_events_max=pb * batch, pass_batches_max=pb))
+    a_lens = batches(n_acct, batch)
+    a_ts, t = timestamps(a_lens, 1_000_000_000)
+    acct = e.alloc(n_acct * 128)
+    e.generate_accounts(acct, 0, n_acct, seed=42)
+    res = e.alloc(max(n_acct, n_xfer) * 8)
+    rb = e.alloc((n_xfer // batch + 2) * 4)
+    e.commit_device_async(128, a_ts, a_lens, acct, res, rb)
+    e.sync()
+    log = e.log_window(n_xfer)
+    e.generate_transfers(log, 0, n_xfer, n_acct, seed=42, kind=KINDS["c4"])
+    e.sync()
+    x_lens = batches(n_xfer, batch)
+    x_ts, t = timestamps(x_lens, t + 10, gap_every=SETTINGS["c4"]["gap_every"])
+    e.commit_device_async(129, x_ts, x_lens, log, res, rb)
+    e.sync()
+    h_rows = np.zeros(Engine.PENDING_ROWS_MAX, dtype=PENDING_ROW_DTYPE)
+    h_states = np.zeros(Engine.PENDING_ROWS_MAX, dtype=np.uint8)
+    h_recs = np.zeros(8190, dtype=TRANSFER_DTYPE)
+    h_res = _lib.tbgpu_query_result()
+
+    def raw(**filter):
+        f = Engine.pending_filter(**filter)
+        src = ctypes.create_string_buffer(f, len(f))
+        return lambda: _lib.check(e.lib.tbgpu_get_pending_transfers(e.h, src, h_rows.ctypes.data, h_states.ctypes.data,
+                                                                    Engine.PENDING_ROWS_MAX, ctypes.byref(h_res)))
+
+    def raw_query(**filter):
+        f = Engine.query_filter(**filter)
+        src = ctypes.create_string_buffer(f, len(f))
+        return lambda: _lib.check(e.lib.tbgpu_query_transfers(e.h, src, h_recs.ctypes.data, 8190, ctypes.byref(h_res)))
+
+    out = {}
+    resolved, unresolved = PENDING_POSTED | PENDING_VOIDED, PENDING_OPEN | PENDING_EXPIRED
+    counts = {}
+    for name, bit in (("open", PENDING_OPEN), ("expired", PENDING_EXPIRED), ("posted", PENDING_POSTED), ("voided", PENDING_VOIDED)):
+        rows, states, counts[name], complete = e.get_pending_transfers(states=bit, limit=1)
+        assert complete and counts[name] > 0 and states.tolist() == [bit]
+    out["rows_by_state"] = counts
+    # What is timed is right where it can be said without a checker: ordered, resolved by its own id.
+    for rev in (False, True):
+        rows, states, matched, complete = e.get_pending_transfers(reversed=rev)
+        ts = rows["pending"]["timestamp"].astype(np.int64)
+        assert complete and matched == sum(counts.values()) and np.all(np.diff(ts) < 0 if rev else np.diff(ts) > 0)
+        hit = (states & resolved) != 0
+        assert hit.any() and (rows["resolution"]["pending_id_lo"][hit] == rows["pending"]["id_lo"][hit]).all()
+        assert not rows["resolution"]["timestamp"][~hit].any()
+    q_med, q_lo, q_hi = timed(e, raw_query(limit=4095))
+    out["query_transfers_all_zero"] = row(q_med, q_lo, q_hi, bytes_per_record=48)
+    s_med, s_lo, s_hi = timed(e, raw(states=unresolved))
+    out["selection_open_expired"] = row(s_med, s_lo, s_hi, bytes_per_record=32, over_query_transfers=round(s_med / q_med, 2))
+    for name, flt in (("all_states_ascending", dict()), ("all_states_reversed", dict(reversed=True)),
+                      ("join_4095_ascending", dict(states=resolved)), ("join_4095_reversed", dict(states=resolved, reversed=True)),
+                      ("join_1_ascending", dict(states=resolved, limit=1)), ("join_1_reversed", dict(states=resolved, limit=1, reversed=True))):
+        rows, states, matched, _ = e.get_pending_transfers(**flt)
+        med, lo_ms, hi_ms = timed(e, raw(**flt))
+        out[name] = row(med, lo_ms, hi_ms, matched=matched, rows=len(rows), resolved_rows=int(((states & resolved) != 0).sum()),
+                        less_selection_ms=round(med - s_med, 4), over_query_transfers=round(med / q_med, 2))
+    sample = e.to_host(log + (n_xfer // 2) * 128, 128).view(TRANSFER_DTYPE)
+    account = int(sample["debit_account_id_lo"][0]) | int(sample["debit_account_id_hi"][0]) << 64
+    rows, states, matched, _ = e.get_pending_transfers(account)
+    med, lo_ms, hi_ms = timed(e, raw(account_id=account))
+    out["one_account_all_states"] = row(med, lo_ms, hi_ms, matched=matched, over_query_transfers=round(med / q_med, 2))
+    e.close()
+    return out
+
+
 result = dict(transfers=n_xfer, log_bytes=n_xfer * 128, runs=runs, warmups=WARMUPS)
 if only == "asof":
     result["asof"] = measure_asof()
 elif only == "ledgers":
     result["ledgers"] = measure_ledgers()
+elif only == "pending":
+    result["pending"] = measure_pending()
 elif only == "many":
     result["many"] = measure_many()
 elif only == "balances":
@@ -518,6 +604,6 @@ elif only != "fields":
     for shape in ("lane_per_record", "cooperative"):
         r = result[shape]
         r["bar_query_le_copy"] = all(v["ms"] <= r["copy_d2d"]["ms"] for k, v in r.items() if k != "copy_d2d")
-if only not in ("account", "balances", "change_events", "many", "asof", "ledgers"):
+if only not in ("account", "balances", "change_events", "many", "asof", "ledgers", "pending"):
     result["field_filters"] = measure_fields()
 print(json.dumps(result))

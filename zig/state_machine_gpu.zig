@@ -726,6 +726,37 @@ pub fn StateMachineType(
             return @as(usize, result.count) * @sizeOf(tbgpu.tbgpu_ledger_balance);
         }
 
+        /// The two-phase transfers of a window with their state (tbgpu_get_pending_transfers): a
+        /// read, with no operation in this reference's enum, so nothing in commit() dispatches to it
+        /// (INTEGRATION.md, "Pending transfers and their state"). One 256-byte tbgpu_pending_row per
+        /// match into `output` — the pending transfer, then the post or void record that resolved
+        /// it, zero if none is resident — and its single TBGPU_PENDING_* bit into `states`. Returns
+        /// the rows written. `complete` is false once transfers were evicted or a returned posted
+        /// or voided row lacks its resolution.
+        pub fn get_pending_transfers(
+            self: *StateMachine,
+            filter: *const tbgpu.tbgpu_pending_filter,
+            output: []align(16) u8,
+            states: []u8,
+            complete: *bool,
+        ) usize {
+            var result: tbgpu.tbgpu_query_result = undefined;
+            result.count = 0;
+            result.complete = 1;
+            result.matched = 0;
+            const room = @min(output.len / @sizeOf(tbgpu.tbgpu_pending_row), states.len);
+            check(tbgpu.tbgpu_get_pending_transfers(
+                self.engine,
+                filter,
+                output.ptr,
+                states.ptr,
+                @intCast(@min(room, tbgpu.TBGPU_PENDING_ROWS_MAX)),
+                &result,
+            ));
+            complete.* = result.complete != 0;
+            return result.count;
+        }
+
         pub fn compact(self: *StateMachine, callback: *const fn (*StateMachine) void, op: u64) void {
             assert(self.compact_callback == null);
             assert(self.checkpoint_callback == null);
