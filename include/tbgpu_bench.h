@@ -107,6 +107,12 @@ int tbgpu_bench_checkpoint_mark(tbgpu_t* engine);
  * GPU's HBM).  Owned by the node: never tbgpu_deinit it, and commit only through the node. */
 int tbgpu_bench_node_shard(tbgpu_t* engine, uint32_t shard, tbgpu_t** out);
 
+/* A node engine's import gate on shard d, read with the engine drained: out = {the foreign accounts
+ * shard d holds imported (live), the imports its table has room for, the flushes its gate has
+ * flagged since init}.  The gate flushes every import before a routed sub-pass of n events when
+ * live + 2 n would pass the room; a shard whose room is the whole ledger never flushes. */
+int tbgpu_bench_node_imports(tbgpu_t* engine, uint32_t shard, uint64_t out[3]);
+
 /* Device memory helpers for callers without a device allocator (ctypes users). */
 int tbgpu_device_alloc(tbgpu_t* engine, uint64_t bytes, void** out);
 int tbgpu_device_free(tbgpu_t* engine, void* ptr);

@@ -27,10 +27,27 @@ def account_id(i):
 def make_scenario(seed, *, n_accounts=64, n_account_batches=2, n_transfer_batches=8, batch_len=(1, 200),
                   p_limit=0.1, p_linked=0.1, p_pending=0.2, p_post_void=0.2, p_balancing=0.05,
                   p_dup=0.05, p_invalid=0.05, p_timeout=0.5, id_space=None, near_overflow=False, p_huge=0.0,
-                  ledgers=(1, 2), start_ts=10**12):
+                  ledgers=(1, 2), start_ts=10**12, transfer_id_of=None, account_id_of=None):
+    """transfer_id_of / account_id_of (default: identity) rename every transfer id (`id`, `pending_id`) and
+    every account id where an event is packed — tests/harness/node_ids.IdPlan places them on chosen
+    shards of a node; the random stream, and so the scenario's shape, does not depend on them."""
     rng = random.Random(seed)
     sc = Scenario()
     ts = start_ts
+    map_tid = transfer_id_of or (lambda i: i)
+    map_aid = account_id_of or (lambda i: i)
+
+    def packed_account(ev):
+        return pack_account(**dict(ev, id=map_aid(ev["id"])))
+
+    def packed_transfer(ev):
+        ev = dict(ev, id=map_tid(ev["id"]))
+        if "pending_id" in ev:
+            ev["pending_id"] = map_tid(ev["pending_id"])
+        for side in ("debit_account_id", "credit_account_id"):
+            if side in ev:
+                ev[side] = map_aid(ev[side])
+        return pack_transfer(**ev)
 
     # -- accounts ----------------------------------------------------------------------------
     acct_idx = list(range(n_accounts))
@@ -60,12 +77,12 @@ def make_scenario(seed, *, n_accounts=64, n_account_batches=2, n_transfer_batche
                     ev["flags"] |= 0x8
                 else:
                     ev["timestamp"] = 5
-            events.append(pack_account(**ev))
+            events.append(packed_account(ev))
             if rng.random() < p_dup:  # duplicate (maybe with different fields)
                 ev2 = dict(ev)
                 if rng.random() < 0.5:
                     ev2["code"] = ev["code"] + 1
-                events.append(pack_account(**ev2))
+                events.append(packed_account(ev2))
             created.append((i, ev["ledger"]))
         if not events:
             continue
@@ -76,7 +93,7 @@ def make_scenario(seed, *, n_accounts=64, n_account_batches=2, n_transfer_batche
         for i in rng.sample(range(n_accounts), k=max(1, n_accounts // 8)):
             big = U128_MAX - rng.randrange(0, 1 << 20)
             dp = rng.choice([0, rng.randrange(1 << 10)])
-            sc.steps.append(("setup", account_id(i), dp, big - dp - rng.randrange(1 << 10),
+            sc.steps.append(("setup", map_aid(account_id(i)), dp, big - dp - rng.randrange(1 << 10),
                              0, rng.randrange(1 << 30)))
 
     # -- transfers ---------------------------------------------------------------------------
@@ -142,7 +159,7 @@ def make_scenario(seed, *, n_accounts=64, n_account_batches=2, n_transfer_batche
                 else:
                     ev["id"] = 0
             all_ids.append(ev["id"])
-            events.append(pack_transfer(**ev))
+            events.append(packed_transfer(ev))
         gap = rng.choice([0, 0, 0, NS, 3 * NS, 60 * NS])
         ts += 1 + gap + len(events)
         sc.steps.append(("commit", 129, ts, events))

@@ -59,8 +59,8 @@ def test_node_client_answers(scenario, node_factory):
 
 @pytest.mark.parametrize("shards", [2, 3])
 def test_node_imports_persist_until_accounts_change(shards, node_factory):
-    """A home keeps the foreign accounts it imported for the next passes (k_node.h tb_node_import),
-    the tombstones of ids no owner held included, and flushes them before any account is inserted:
+    """A home keeps the foreign accounts it imported for the next passes (k_node.h tb_node_import;
+    an id no owner holds takes no entry), and flushes them before any account is inserted:
     transfers naming missing accounts, then those accounts created, then transfers naming them again
     (and passes re-reading the kept imports) answer as the oracle does; the ledger summary, read with
     the imports still in the tables, counts each account once and finds no stray balance."""
@@ -100,7 +100,7 @@ def test_node_imports_persist_until_accounts_change(shards, node_factory):
     old, late = np.arange(1, 201), np.arange(500, 541)
     both(128, accounts(old))
     both(128, accounts(old + 1000))
-    for _ in range(3):  # the late accounts do not exist yet: account_not_found, their tombstones kept
+    for _ in range(3):  # the late accounts do not exist yet: account_not_found, no entry taken
         assert both(129, transfers(2000, np.concatenate([old, late]), old)) != b""
     led = engine.ledger_summary()
     assert led["accounts"] == 400 and led["stray"] == 0, led

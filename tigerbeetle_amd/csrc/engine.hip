@@ -597,6 +597,7 @@ static int node_api_get_stats(TbNode* N, tbgpu_stats* s);
 static void node_reset_stats(TbNode* N);
 static u32 node_world(TbNode* N);
 static tbgpu* node_engine(TbNode* N, u32 d);
+static int node_api_imports(TbNode* N, u32 d, u64 out[3]);
 static int node_api_register_host(TbNode* N, void* ptr, u64 bytes);
 static int node_api_unregister_host(TbNode* N, void* ptr);
 static int node_fetch(TbNode* N, bool accounts, const u64* ids, u32 n, u8* out, u8* found);
@@ -1040,7 +1041,7 @@ static int enqueue_call(tbgpu* E, u8 op, u32 nb, const u64* h_off, const u8* eve
         // inline_meta: a one-prepare call's metadata, written into E->meta by this first kernel.
         u64* meta_dst = inline_meta && b0 == 0 ? (u64*)d_off : nullptr;
         ImportGate gate{};
-        if (imp && n > 0) gate = ImportGate{imp->count, imp->room, 0, imp->flag};
+        if (imp && n > 0) gate = ImportGate{imp->count, imp->room, imp->gated ? 2 * n : 0, imp->flag};
         hipLaunchKernelGGL(tb_pass_clear, dim3(clear_grid), dim3(256), 0, E->stream, E->dedup, E->dedup_cap, E->sum_shards,
                            E->g, E->epoch, E->dedup_force ? 1u : 0u, E->leg_tot, E->leg_buckets, meta_dst,
                            inline_meta ? inline_meta[0] : 0, inline_meta ? inline_meta[1] : 0, inline_meta ? inline_meta[2] : 0,
@@ -1053,8 +1054,8 @@ static int enqueue_call(tbgpu* E, u8 op, u32 nb, const u64* h_off, const u8* eve
 
         if (imp && n > 0) {  // a node home: the foreign accounts this sub-pass names, from their owners
             const u32 ig = (u32)std::min<u64>(4096, (n + 255) / 256);
-            // The imports of earlier passes stay, unless they passed the room (the gate in
-            // tb_pass_clear above).
+            // The imports of earlier passes stay, unless with this sub-pass's two per event they
+            // would pass the room (the gate in tb_pass_clear above).
             hipLaunchKernelGGL(tb_node_import_flush, dim3((u32)std::min<u64>(1024, (E->account_cap + 255) / 256)), dim3(256), 0,
                                E->stream, E->T, E->account_cap, imp->N.world, imp->self, (const u32*)imp->flag);
             hipLaunchKernelGGL(tb_node_import, dim3(ig), dim3(256), 0, E->stream, E->T, imp->N, events_dev + P.e0 * 128, n,
@@ -2437,6 +2438,12 @@ extern "C" int tbgpu_bench_node_shard(tbgpu_t* E, uint32_t shard, tbgpu_t** out)
     if (!E->node || shard >= node_world(E->node)) return fail(TBGPU_STATUS_INVALID, "not a node shard");
     *out = node_engine(E->node, shard);
     return TBGPU_STATUS_OK;
+}
+
+extern "C" int tbgpu_bench_node_imports(tbgpu_t* E, uint32_t shard, uint64_t out[3]) {
+    API_ENTER(E, false);
+    if (!E->node || shard >= node_world(E->node)) return fail(TBGPU_STATUS_INVALID, "not a node shard");
+    return node_api_imports(E->node, shard, out);
 }
 
 extern "C" int tbgpu_bench_walk_merge_max(tbgpu_t* E, uint32_t segments) {

@@ -243,7 +243,8 @@ __device__ static inline bool tb_import_one(const Tables& H, const NodeTablesArg
     AccountHot a;
     u32 os = TB_NOT_FOUND;
     bool looked = false;
-    for (u64 k = 0; k <= H.account_mask; k++) {
+    u64 k = 0;
+    for (; k <= H.account_mask; k++) {
         // Plain (cached) reads: a stale one costs a failed CAS (which returns the truth) or a
         // duplicate entry, never a wrong one.
         u64* tw = &H.acct_hot[pos].timestamp;
@@ -268,6 +269,7 @@ __device__ static inline bool tb_import_one(const Tables& H, const NodeTablesArg
         }
         pos = (pos + 1) & H.account_mask;
     }
+    if (k > H.account_mask) tb_panic(H.g, PANIC_TABLE_FULL);  // neither the id nor a free slot (the gate keeps room)
     if (slot == TB_NOT_FOUND) return false;
     AccountHot* h = &H.acct_hot[slot];
     os_of[slot] = os;  // the owner's slot, for this pass's owner legs
@@ -342,8 +344,10 @@ __global__ __launch_bounds__(256) void tb_node_import_flush(Tables H, u64 cap, u
 struct NodeImport {
     NodeTablesArgs N;
     u32 self;
-    u64* count;    // the shard's live imports (persistent across passes)
+    u64* count;    // the shard's live imports (persistent across passes), then the gate's flushes
     u64 room;      // imports the table has room for (2 x a sub-pass's events at most)
+    bool gated;    // the room is smaller than the ledger: the gate counts each sub-pass's two per event
+                   // (false: every account of the ledger fits, the imports never need a flush)
     u32* flag;     // tb_pass_clear's gate -> tb_node_import_flush
     u32* os_of;    // [account_cap] imported slot -> the account's slot on its owner
     u64* leg_counts = nullptr;  // the home's per-owner leg counts, zeroed by the sub-pass's tb_pass_clear

@@ -98,8 +98,9 @@ struct NodeDev {
     // Partitioned account records: the foreign accounts a routed sub-pass imports (k_node.h
     // tb_node_import), and the replicated limit-account bitmap.
     u32* imp_flag = nullptr;   // tb_pass_clear's import gate -> tb_node_import_flush
-    u64* imp_count = nullptr;  // live imports (they stay across passes)
+    u64* imp_count = nullptr;  // [0] live imports (they stay across passes), [1] the gate's flushes since init
     u64 imp_cap = 0;           // the table's import room
+    bool imp_gated = false;    // the room is smaller than the ledger (else the gate never flushes)
     u32* imp_os = nullptr;  // [account_cap] an imported slot's slot on the account's owner (owner legs)
     u64* limbits = nullptr;
     u64 limmask = 0;             // bits - 1
@@ -444,9 +445,10 @@ static int node_init(TbNode* N, const tbgpu_config* config) {
         HIPCK(tbEventCreateWithFlags(D.E->own, &D.ev_pre, hipEventDisableTiming));
         HIPCK(tbEventCreateWithFlags(D.E->own, &D.ev_xwb, hipEventDisableTiming));
         D.imp_cap = import_room;
+        D.imp_gated = import_room < config->accounts_max;
         HIPCK(tbMalloc(D.E->own, &D.imp_flag, 4));
-        HIPCK(tbMalloc(D.E->own, &D.imp_count, 8));
-        HIPCK(hipMemset(D.imp_count, 0, 8));
+        HIPCK(tbMalloc(D.E->own, &D.imp_count, 16));
+        HIPCK(hipMemset(D.imp_count, 0, 16));
         HIPCK(tbMalloc(D.E->own, &D.imp_os, D.E->account_cap * 4));
         // 16 bits per account of the ledger: a false positive (which only sequences an event) is at
         // most 1 in 16 even when every account is limited.
@@ -957,6 +959,7 @@ static int node_home_one(TbNode* N, u32 h, void* ctx) {
             imp.self = h;
             imp.count = D.imp_count;
             imp.room = D.imp_cap;
+            imp.gated = D.imp_gated;
             imp.flag = D.imp_flag;
             imp.os_of = D.imp_os;
             imp.leg_counts = D.leg_counts;
@@ -2012,6 +2015,19 @@ static int node_api_transfers_in(TbNode* N, const void* records, const u8* state
 static u64 node_commit_ts(TbNode* N) { return N->commit_ts; }
 static u32 node_world(TbNode* N) { return N->world; }
 static tbgpu* node_engine(TbNode* N, u32 d) { return N->D[d].E; }
+
+// Shard d's import gate, read with the node drained: {live imports, room, gate flushes since init}.
+static int node_api_imports(TbNode* N, u32 d, u64 out[3]) {
+    const int st = node_sync(N);
+    if (st) return st;
+    u64 w[2];
+    NCK(hipSetDevice(N->D[d].device));
+    NCK(hipMemcpy(w, N->D[d].imp_count, 16, hipMemcpyDeviceToHost));
+    out[0] = w[0];
+    out[1] = N->D[d].imp_cap;
+    out[2] = w[1];
+    return TBGPU_STATUS_OK;
+}
 
 static int node_api_set_commit_timestamp(TbNode* N, u64 timestamp) {
     const int st = node_sync(N);

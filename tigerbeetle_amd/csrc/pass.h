@@ -392,10 +392,10 @@ __device__ static inline void tb_dedup_mark(const PassArgs& P) {
 // zero_b (optional): counters of the caller zeroed here instead of by a copy each (a node home's leg
 // counts, k_node.h).  imp (optional): a node home's import gate (k_node.h tb_node_import_flush):
 // when its live imports plus what this sub-pass may add would pass the room, flag the flush and
-// restart the count.
+// restart the count.  count[1] counts the flushes the gate flagged (tbgpu_bench_node_imports).
 struct ImportGate {
     u64* count;
-    u64 room, need;
+    u64 room, need;  // need: the sub-pass's worst case, two per event (0: the room is the whole ledger)
     u32* flag;
 };
 __global__ __launch_bounds__(256) void tb_pass_clear(u64* dedup, u64 cap, u64* sum_shards, const Globals* g, u32 epoch,
@@ -407,7 +407,10 @@ __global__ __launch_bounds__(256) void tb_pass_clear(u64* dedup, u64 cap, u64* s
     if (imp.count && blockIdx.x == 0 && threadIdx.x == 0) {
         const bool full = *imp.count + imp.need > imp.room;
         *imp.flag = full ? 1u : 0u;
-        if (full) *imp.count = 0;
+        if (full) {
+            imp.count[0] = 0;
+            imp.count[1]++;
+        }
     }
     if (zero_b && blockIdx.x == 0 && threadIdx.x < zero_b_n) zero_b[threadIdx.x] = 0;
     if (kclock && blockIdx.x == 0) {

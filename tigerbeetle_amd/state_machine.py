@@ -615,6 +615,13 @@ class Engine:
         view.close = lambda: None
         return view
 
+    def node_imports(self, d):
+        """{"live", "room", "flushes"} of a node engine's import gate on shard d, read with the engine
+        drained (tbgpu_bench_node_imports)."""
+        out = (ctypes.c_uint64 * 3)()
+        _lib.check(self.lib.tbgpu_bench_node_imports(self.h, int(d), out))
+        return dict(live=int(out[0]), room=int(out[1]), flushes=int(out[2]))
+
     def walk_merge_max(self, segments):
         """Heavy segments the limit-check sweep walks merged on one wave at most (0: a wave each)."""
         _lib.check(self.lib.tbgpu_bench_walk_merge_max(self.h, int(segments)))
