@@ -25,6 +25,7 @@
  *   (no reference: accounts as of a timestamp)             tbgpu_lookup_accounts_at (likewise)
  *   (no reference: a trial balance per ledger)             tbgpu_get_ledger_balances (likewise)
  *   (no reference: pending transfers with their state)     tbgpu_get_pending_transfers (likewise)
+ *   (no reference: account statements over a period)       tbgpu_get_account_statements (likewise)
  *   `setup` action of the table tests (:1398-1407)         tbgpu_test_set_balances (test only)
  *   StateMachine.commit_timestamp field (:251)             tbgpu_commit_timestamp
  *
@@ -689,6 +690,70 @@ typedef struct tbgpu_pending_row {      /* 256 bytes */
 int tbgpu_get_pending_transfers(tbgpu_t* engine, const tbgpu_pending_filter* filter,
                                 void* out_rows, uint8_t* out_states, uint32_t out_cap_rows,
                                 tbgpu_query_result* result);
+
+/* get_account_statements: a statement header for each account the caller names, over a period the
+ * caller names — the balances at the period's start, the balances at its end, what moved in between
+ * (gross debits and credits, holds placed and released) and how many transfers there were.  No
+ * reference has an operation for it.  Two tbgpu_lookup_accounts_at calls give the two balances in two
+ * scans and their difference only the net; this call derives all of it in one scan of the log in HBM,
+ * whatever the number of ids, and stores nothing at commit.  An entry point of its own, as above;
+ * this comment is its specification.
+ *   The period is (t_open, t_close], so consecutive statements tile: the next t_open is this
+ *     t_close.  0 leaves that end open: t_open == 0 means from before every record (read literally,
+ *     not as "now"), t_close == 0 means up to now.
+ *   Which rows: tbgpu_lookup_accounts_at's rules with T = t_close — one 256-byte row per requested
+ *     id that its owner's account table holds, in request order.  Absent ids and the reserved ids (0,
+ *     2^128-1) are skipped; a repeated id is answered once per occurrence; an account whose own
+ *     timestamp is above a non-zero t_close is skipped.  `matched` is the number of ids that yield a
+ *     row; count = min(matched, out_cap_rows), the first ones in request order; bytes past count rows
+ *     are not written.
+ *   The sums are taken over every live resident record r that names the account (liveness:
+ *     tbgpu_get_account_transfers' rule), on the debit side where the account is r's debit account,
+ *     on the credit side where it is r's credit account; a loaded record that names it on both counts
+ *     on both.  P and the orphan rule are tbgpu_get_account_balances': a void's P is its own amount,
+ *     and a post whose pending transfer is not resident uses P = its own amount and drops `complete`.
+ *     A record in the period (t_open < r.timestamp, and r.timestamp <= t_close when t_close != 0)
+ *     adds one to its side's debit_transfers or credit_transfers, and by kind
+ *         pending      *_pending_in  += amount
+ *         post         *_pending_out += P,  *_posted_in += amount
+ *         void         *_pending_out += P
+ *         any other    *_posted_in   += amount
+ *     closing = current(a) - the effects of the records above t_close (tbgpu_lookup_accounts_at's
+ *     sum; for t_close == 0 nothing is above it), and
+ *         opening.x_pending = closing.x_pending - x_pending_in + x_pending_out
+ *         opening.x_posted  = closing.x_posted  - x_posted_in
+ *     all of it per column modulo 2^128.  So `closing` is tbgpu_lookup_accounts_at's balances at
+ *     t_close, `opening` is that call's formula at t_open, and the identities hold exactly.  The
+ *     anchor is the current balance: the answers stay exact after eviction of an old prefix, after
+ *     tbgpu_load_accounts and after tbgpu_test_set_balances; periods that reach behind such a step
+ *     follow this definition, not the ledger's past.  An account created inside the period gets its
+ *     `opening` by the definition too: zero on an engine that saw none of those steps.
+ *   complete: tbgpu_lookup_accounts_at's rule — 1 only when no transfer was ever evicted (any shard)
+ *     and every post that entered a sum found its pending transfer resident; otherwise 0.
+ *   t_open or t_close equal to 2^64-1, or a non-zero t_close below t_open, returns TBGPU_STATUS_OK
+ *     with count = matched = 0.  n == 0 returns TBGPU_STATUS_OK and writes nothing.
+ *     n > TBGPU_STATEMENTS_MAX, or a NULL ids, out or result with n > 0, is TBGPU_STATUS_INVALID and
+ *     writes nothing.  After any failing status the result names no row.
+ *   The call contract of tbgpu_get_account_transfers: synchronous, drains a pending
+ *     tbgpu_commit_device_async first, a read that changes nothing (commit_timestamp, balances, log,
+ *     index, posted groove, stats, the write-back snapshot), works on an engine a device panic
+ *     stopped, allocates nothing after tbgpu_init, legal beside an asynchronous write-back.
+ *   A node engine has the same contract: every home shard scans its own log on its own device and
+ *     stream, side by side, reading a post's pending transfer on the home shard of its pending_id;
+ *     each account's record, and whether it existed at t_close, come from its owner shard only; the
+ *     host adds the shards' sums. */
+#define TBGPU_STATEMENTS_MAX 4095u   /* 256 B rows in one message body: 4095*256 <= 8191*128 */
+typedef struct tbgpu_account_statement {   /* 256 bytes, little-endian, no padding */
+    uint64_t id_lo, id_hi;
+    uint64_t opening[8];   /* debits_pending, debits_posted, credits_pending, credits_posted: lo, hi each */
+    uint64_t closing[8];   /* likewise */
+    uint64_t debits_pending_in[2],  debits_pending_out[2],  debits_posted_in[2];
+    uint64_t credits_pending_in[2], credits_pending_out[2], credits_posted_in[2];
+    uint64_t debit_transfers, credit_transfers;
+} tbgpu_account_statement;
+int tbgpu_get_account_statements(tbgpu_t* engine, uint64_t t_open, uint64_t t_close,
+                                 const void* ids /* n x {lo, hi} */, uint32_t n,
+                                 void* out, uint32_t out_cap_rows, tbgpu_query_result* result);
 
 /* The replica writes StateMachine.commit_timestamp itself: the header timestamp after every commit
  * (src/vsr/replica.zig:3664-3665) and the checkpoint's value on open / state sync.  The wrapper

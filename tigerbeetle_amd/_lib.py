@@ -100,6 +100,18 @@ class tbgpu_pending_row(ctypes.Structure):
 PENDING_ROWS_MAX = 4095  # TBGPU_PENDING_ROWS_MAX
 
 
+class tbgpu_account_statement(ctypes.Structure):
+    _fields_ = [("id_lo", ctypes.c_uint64), ("id_hi", ctypes.c_uint64),
+                ("opening", ctypes.c_uint64 * 8), ("closing", ctypes.c_uint64 * 8),
+                ("debits_pending_in", ctypes.c_uint64 * 2), ("debits_pending_out", ctypes.c_uint64 * 2),
+                ("debits_posted_in", ctypes.c_uint64 * 2), ("credits_pending_in", ctypes.c_uint64 * 2),
+                ("credits_pending_out", ctypes.c_uint64 * 2), ("credits_posted_in", ctypes.c_uint64 * 2),
+                ("debit_transfers", ctypes.c_uint64), ("credit_transfers", ctypes.c_uint64)]
+
+
+STATEMENTS_MAX = 4095  # TBGPU_STATEMENTS_MAX
+
+
 class tbgpu_stats(ctypes.Structure):
     _fields_ = [
         ("passes", ctypes.c_uint64),
@@ -226,6 +238,7 @@ SIGNATURES = [
     ("tbgpu_lookup_accounts_at", ctypes.c_int, [_P, _U64, _P, _U32, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_get_ledger_balances", ctypes.c_int, [_P, _U64, _P, _U32, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_get_pending_transfers", ctypes.c_int, [_P, _P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
+    ("tbgpu_get_account_statements", ctypes.c_int, [_P, _U64, _U64, _P, _U32, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_query_transfers", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_query_accounts", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_bench_query_keys_max", ctypes.c_int, [_P, _U32]),

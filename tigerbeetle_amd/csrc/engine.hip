@@ -38,6 +38,7 @@
 #include "k_balances.h"
 #include "k_change_events.h"
 #include "k_asof.h"
+#include "k_statement.h"
 #include "k_ledgers.h"
 #include "k_pending.h"
 #include "checksum.h"

@@ -1,6 +1,7 @@
 // query.h — the host side of the queries (include/tbgpu.h): get_account_transfers and its batched form
 // get_account_transfers_many, get_account_balances, query_transfers, query_accounts,
-// get_change_events, lookup_accounts_at, get_ledger_balances and get_pending_transfers; their buffers, made at tbgpu_init, and their entry points.  Included by engine.hip after the engine's own helpers and before node.h.
+// get_change_events, lookup_accounts_at, get_ledger_balances, get_pending_transfers and
+// get_account_statements; their buffers, made at tbgpu_init, and their entry points.  Included by engine.hip after the engine's own helpers and before node.h.
 //
 // Every query is written once, over a list of engines (QueryCall): the one engine, or a node's shards.
 // A transfer lives on its home shard only and an account is answered by its owner only, so every
@@ -155,6 +156,26 @@ struct PendingBufs {
     u32* h_row_of = nullptr;  // pinned [PENDING_ROWS_MAX] the row an index stands for
 };
 
+// tbgpu_get_account_statements (k_statement.h): lookup_accounts_at's buffers at this call's sizes — the
+// request's ids, the set, the bins of STATEMENT_BIN_WORDS, the accounts' records and found flags, the
+// answer's rows and the result words; made by query_init and shared with nothing.  Every word a query
+// reads is a word it wrote, so tbgpu_reset clears none of them.
+struct StatementBufs {
+    u64* d_ids = nullptr;      // [STATEMENT_IDS_MAX][2] the request
+    u64* h_ids = nullptr;      // pinned: the caller's ids on their way up (a node copies them into every shard's)
+    u32* d_set = nullptr;      // [tb_change_set_slots(STATEMENT_IDS_MAX)] the set's entries
+    u64* d_bins = nullptr;     // [STATEMENT_IDS_MAX][STATEMENT_BIN_WORDS] the bins by request position, then the flag word
+    u8* d_accounts = nullptr;  // [STATEMENT_IDS_MAX] the records as the owners hold them
+    u32* d_found = nullptr;    // [STATEMENT_IDS_MAX] 1: the position yields a row
+    u8* d_out = nullptr;       // [STATEMENT_IDS_MAX] the answer's rows (one engine)
+    u64* d_res = nullptr;      // [STATEMENT_RES_WORDS]
+    u64* h_res = nullptr;      // pinned mirror
+    u64* h_bins = nullptr;     // pinned mirrors, read by a node's host only: it adds the shards' bins
+    u8* h_accounts = nullptr;
+    u32* h_found = nullptr;
+};
+#define STATEMENT_BIN_BYTES(n) (((u64)(n) * STATEMENT_BIN_WORDS + 1) * 8)
+
 // One engine's query buffers (tbgpu::qs), in the order query_init makes them.
 struct QueryState {
     QueryBufs q;
@@ -165,6 +186,7 @@ struct QueryState {
     LookupAtBufs ql;
     LedgerBufs qg;
     PendingBufs qp;
+    StatementBufs qt;
 };
 
 // Called by engine_init on the engine's device, after every other buffer.  The buffers go into the
@@ -281,6 +303,22 @@ static int query_init(tbgpu* E) {
         HIPCK(tbMalloc(E->own, &P.d_slots, nr * 128));
         HIPCK(tbHostMalloc(E->own, &P.h_slots, nr * 128, hipHostMallocDefault));
         HIPCK(tbHostMalloc(E->own, &P.h_row_of, nr * 4, hipHostMallocDefault));
+    }
+    {  // tbgpu_get_account_statements: the ids, the set, the bins, the accounts, the rows, the result words
+        StatementBufs& S = E->qs->qt;
+        const u64 ni = STATEMENT_IDS_MAX, bin_bytes = STATEMENT_BIN_BYTES(ni);
+        HIPCK(tbMalloc(E->own, &S.d_ids, ni * 16));
+        HIPCK(tbHostMalloc(E->own, &S.h_ids, ni * 16, hipHostMallocDefault));
+        HIPCK(tbMalloc(E->own, &S.d_set, (u64)tb_change_set_slots(STATEMENT_IDS_MAX) * 4));
+        HIPCK(tbMalloc(E->own, &S.d_bins, bin_bytes));
+        HIPCK(tbMalloc(E->own, &S.d_accounts, ni * 128));
+        HIPCK(tbMalloc(E->own, &S.d_found, ni * 4));
+        HIPCK(tbMalloc(E->own, &S.d_out, ni * STATEMENT_ROW_BYTES));
+        HIPCK(tbMalloc(E->own, &S.d_res, STATEMENT_RES_WORDS * 8));
+        HIPCK(tbHostMalloc(E->own, &S.h_res, STATEMENT_RES_WORDS * 8, hipHostMallocDefault));
+        HIPCK(tbHostMalloc(E->own, &S.h_bins, bin_bytes, hipHostMallocDefault));
+        HIPCK(tbHostMalloc(E->own, &S.h_accounts, ni * 128, hipHostMallocDefault));
+        HIPCK(tbHostMalloc(E->own, &S.h_found, ni * 4, hipHostMallocDefault));
     }
     return TBGPU_STATUS_OK;
 }
@@ -1296,6 +1334,145 @@ extern "C" int tbgpu_lookup_accounts_at(tbgpu_t* E, uint64_t timestamp, const vo
         HIPCK(hipStreamSynchronize(S->stream));
     }
     if (L.h_res[ASOF_RES_ORPHAN]) result->complete = 0;
+    result->count = m;
+    result->matched = matched;
+    return TBGPU_STATUS_OK;
+}
+
+// ---- get_account_statements (k_statement.h, include/tbgpu.h) --------------------------------------
+// lookup_accounts_at's shape with T = t_close and a scan of its own.  One engine: ids up, set and bins
+// zeroed, tb_asof_gather -> tb_statement_effects -> tb_statement_emit on the engine stream, the result
+// words back; one wait; then the answer's count * 256 bytes.  The scan always runs: t_close = 0 has
+// nothing above it, but the period's sums are the log's.  The set has at most 8,192 slots and stays
+// 32-bit in LDS beside STATEMENT_LDS_BINS claimed bins.
+// A node: every shard gathers (each builds the same set) and scans its own log on its own device and
+// stream, side by side; the host adds the shards' bins and writes the rows (tb_statement_row).
+static int statements_enqueue(tbgpu* E, const NodeTablesArgs& NT, u32 self, u32 n, u64 t_open, u64 t_close, bool emit, u32 cap) {
+    StatementBufs& S = E->qs->qt;
+    HIPCK(hipSetDevice(E->device));
+    const u32 slots = tb_change_set_slots(n), mask = slots - 1;
+    const u64 bin_bytes = STATEMENT_BIN_BYTES(n);
+    const unsigned nb_ids = (n + QUERY_THREADS - 1) / QUERY_THREADS;
+    HIPCK(hipMemcpyAsync(S.d_ids, S.h_ids, (u64)n * 16, hipMemcpyHostToDevice, E->stream));
+    HIPCK(hipMemsetAsync(S.d_set, 0, (u64)slots * 4, E->stream));
+    HIPCK(hipMemsetAsync(S.d_bins, 0, bin_bytes, E->stream));
+    const bool store = emit || self == 0;  // a node reads the first shard's records only
+    hipLaunchKernelGGL(tb_asof_gather, dim3(nb_ids), dim3(QUERY_THREADS), 0, E->stream, NT, (const u64*)S.d_ids, n, t_close,
+                       store ? S.d_accounts : nullptr, store ? S.d_found : nullptr, S.d_set, mask);
+    HIPCK(hipGetLastError());
+    const u64 records = E->log_next, per = (u64)CHANGE_THREADS * CHANGE_TILES, nb = (records + per - 1) / per;
+    if (nb) {
+        const size_t lds = (size_t)slots * 4 + (size_t)STATEMENT_LDS_BINS * (STATEMENT_BIN_WORDS * 8 + 4);
+        hipLaunchKernelGGL(tb_statement_effects, dim3((unsigned)nb), dim3(CHANGE_THREADS), lds, E->stream, NT, self, records, t_open,
+                           t_close, (const u32*)S.d_set, mask, (const u64*)S.d_ids, n, S.d_bins);
+        HIPCK(hipGetLastError());
+    }
+    if (emit) {
+        hipLaunchKernelGGL(tb_statement_emit, dim3(nb_ids), dim3(QUERY_THREADS), 0, E->stream, (const u64*)S.d_ids, n,
+                           (const u8*)S.d_accounts, (const u32*)S.d_found, (const u32*)S.d_set, mask, (const u64*)S.d_bins, cap,
+                           S.d_out, S.d_res);
+        HIPCK(hipGetLastError());
+        HIPCK(hipMemcpyAsync(S.h_res, S.d_res, STATEMENT_RES_WORDS * 8, hipMemcpyDeviceToHost, E->stream));
+        return TBGPU_STATUS_OK;
+    }
+    HIPCK(hipMemcpyAsync(S.h_bins, S.d_bins, bin_bytes, hipMemcpyDeviceToHost, E->stream));
+    if (self == 0) {
+        HIPCK(hipMemcpyAsync(S.h_accounts, S.d_accounts, (u64)n * 128, hipMemcpyDeviceToHost, E->stream));
+        HIPCK(hipMemcpyAsync(S.h_found, S.d_found, (u64)n * 4, hipMemcpyDeviceToHost, E->stream));
+    }
+    return TBGPU_STATUS_OK;
+}
+
+// A node's answer from its shards' pinned mirrors: the found positions in request order, each from
+// its record and the sum of every shard's bin of its id (the bin of the smallest position that names
+// the id).  The bins' words add as the device added them: the 128-bit sums with their carry, the
+// counts as they are.
+static void statements_node_rows(const QueryCall& c, u32 n, u32 cap, u8* out, tbgpu_query_result* result) {
+    const StatementBufs& S = c.Es[0]->qs->qt;
+    std::vector<u32> index(n), order(n);
+    std::iota(order.begin(), order.end(), 0u);
+    auto id_of = [&](u32 i) { return std::make_pair(S.h_ids[2 * (u64)i + 1], S.h_ids[2 * (u64)i]); };
+    std::sort(order.begin(), order.end(), [&](u32 a, u32 b) { return id_of(a) != id_of(b) ? id_of(a) < id_of(b) : a < b; });
+    for (u32 j = 0; j < n; j++) index[order[j]] = j && id_of(order[j - 1]) == id_of(order[j]) ? index[order[j - 1]] : order[j];
+    u32 m = 0, written = 0;
+    for (u32 i = 0; i < n; i++) {
+        if (!S.h_found[i]) continue;
+        if (m++ >= cap) continue;
+        u64 bin[STATEMENT_BIN_WORDS] = {};
+        for (u32 d = 0; d < c.world; d++) {
+            const u64* b = c.Es[d]->qs->qt.h_bins + (u64)index[i] * STATEMENT_BIN_WORDS;
+            for (u32 w = 0; w < STATEMENT_BIN_WORDS;) {
+                const bool count = w >= STATEMENT_ZONE1 && (w - STATEMENT_ZONE1) % STATEMENT_SIDE_WORDS == 6;
+                if (count) {
+                    bin[w] += b[w];
+                    w += 1;
+                } else {
+                    const u128 v = tb_u128(bin[w], bin[w + 1]) + tb_u128(b[w], b[w + 1]);
+                    bin[w] = tb_lo(v), bin[w + 1] = tb_hi(v);
+                    w += 2;
+                }
+            }
+        }
+        u64 row[STATEMENT_ROW_BYTES / 8];
+        tb_statement_row((const u64*)(S.h_accounts + (u64)i * 128), bin, row);
+        memcpy(out + (u64)written++ * STATEMENT_ROW_BYTES, row, sizeof row);
+    }
+    for (u32 d = 0; d < c.world; d++) {
+        if (c.Es[d]->qs->qt.h_bins[(u64)n * STATEMENT_BIN_WORDS]) result->complete = 0;
+    }
+    result->count = written;
+    result->matched = m;
+}
+
+extern "C" int tbgpu_get_account_statements(tbgpu_t* E, uint64_t t_open, uint64_t t_close, const void* ids, uint32_t n, void* out,
+                                            uint32_t out_cap_rows, tbgpu_query_result* result) {
+    static_assert(sizeof(tbgpu_account_statement) == STATEMENT_ROW_BYTES && STATEMENT_IDS_MAX == TBGPU_STATEMENTS_MAX &&
+                      STATEMENT_ZONE1 + 2 * STATEMENT_SIDE_WORDS == STATEMENT_BIN_WORDS,
+                  "k_statement.h's constants are the header's");
+    static_assert((size_t)CHANGE_LDS_BINS_SLOTS_MAX * 4 + (size_t)STATEMENT_LDS_BINS * (STATEMENT_BIN_WORDS * 8 + 4) <= 65536,
+                  "set, bins and tags stay within 64 KB a workgroup");
+    API_ENTER(E, false);
+    if (n > TBGPU_STATEMENTS_MAX) return fail(TBGPU_STATUS_INVALID, "get_account_statements: %u ids (at most %u)", n, TBGPU_STATEMENTS_MAX);
+    if (n == 0) return TBGPU_STATUS_OK;
+    if (!ids || !out || !result) return fail(TBGPU_STATUS_INVALID, "get_account_statements: NULL ids, out or result");
+    QueryCall c;
+    result->count = 0;
+    result->matched = 0;
+    result->complete = query_engines(E, true, &c);
+    if (t_open == ~0ULL || t_close == ~0ULL || (t_close != 0 && t_close < t_open)) return TBGPU_STATUS_OK;
+    const bool one = c.world == 1;
+    NodeTablesArgs NT{};
+    NT.world = c.world;
+    for (u32 d = 0; d < c.world; d++) NT.T[d] = c.Es[d]->T;
+    // Every engine is drained before any is asked: a gather reads the owners' tables and a scan its
+    // posts' pending transfers on their homes.
+    for (u32 d = 0; d < c.world; d++) {
+        HIPCK(hipSetDevice(c.Es[d]->device));
+        if (c.Es[d]->pending) {
+            const int st = engine_sync(c.Es[d]);
+            if (st) return query_end(result, st);
+        }
+    }
+    memcpy(c.Es[0]->qs->qt.h_ids, ids, (u64)n * 16);
+    int st = query_side_by_side(c.Es, c.world, [&](u32 d) -> int {
+        if (d) memcpy(c.Es[d]->qs->qt.h_ids, c.Es[0]->qs->qt.h_ids, (u64)n * 16);
+        return statements_enqueue(c.Es[d], NT, d, n, t_open, t_close, one, out_cap_rows);
+    });
+    if (st) return query_end(result, st);
+    if (!one) {
+        statements_node_rows(c, n, out_cap_rows, (u8*)out, result);
+        return TBGPU_STATUS_OK;
+    }
+    tbgpu* S0 = c.Es[0];
+    const StatementBufs& S = S0->qs->qt;
+    const u64 matched = S.h_res[STATEMENT_RES_MATCHED];
+    const u32 m = (u32)std::min<u64>(matched, out_cap_rows);
+    if (matched > n) return query_end(result, fail(TBGPU_STATUS_PANIC, "get_account_statements: %llu rows for %u ids", (unsigned long long)matched, n));
+    if (m) {
+        HIPCK(hipMemcpyAsync(out, S.d_out, (u64)m * STATEMENT_ROW_BYTES, hipMemcpyDeviceToHost, S0->stream));
+        HIPCK(hipStreamSynchronize(S0->stream));
+    }
+    if (S.h_res[STATEMENT_RES_ORPHAN]) result->complete = 0;
     result->count = m;
     result->matched = matched;
     return TBGPU_STATUS_OK;

@@ -282,6 +282,15 @@ public:
     tbgpu_query_result get_pending_transfers(const tbgpu_pending_filter& filter, void* out_rows, uint8_t* out_states,
                                              uint32_t out_cap_rows);
 
+    // Statement headers over the period (t_open, t_close] (tbgpu_get_account_statements; a read, and no
+    // reference operation behind it): one 256-byte tbgpu_account_statement per id the table holds and
+    // that existed at t_close, in request order — the balances at the period's start and end, the
+    // gross flows in between and the transfer counts, from one scan of the log.  ids: n x {lo, hi},
+    // at most TBGPU_STATEMENTS_MAX.  t_open 0: from before every record; t_close 0: up to now.
+    // result.complete == 0: transfers were evicted or a summed post had lost its pending transfer.
+    tbgpu_query_result get_account_statements(uint64_t t_open, uint64_t t_close, const void* ids, uint32_t n, void* out,
+                                              uint32_t out_cap_rows);
+
     // The field-filter queries (tbgpu_query_transfers / tbgpu_query_accounts; reads, not commits): the
     // resident transfers, or the accounts, whose user_data_128 / user_data_64 / user_data_32 / ledger /
     // code equal the filter's non-zero fields, by timestamp (newest first under TBGPU_QUERY_REVERSED),

@@ -23,7 +23,7 @@ import numpy as np
 
 from . import _lib
 from .types import (ACCOUNT_BALANCE_DTYPE, ACCOUNT_DTYPE, ACCOUNT_FILTER_DTYPE, BATCH_MAX, CHANGE_EVENT_DTYPE, CHANGE_EVENTS_FILTER_DTYPE,
-                    CHANGE_EVENTS_MAX, LEDGER_BALANCE_DTYPE, LEDGERS_MAX, PENDING_FILTER_DTYPE, PENDING_ROW_DTYPE, PENDING_ROWS_MAX, PENDING_STATES, FILTER_CREDITS, FILTER_DEBITS, FILTER_REVERSED, pack_change_events_filter, QUERY_FILTER_DTYPE, QUERY_REVERSED, TRANSFER_DTYPE, U64_MAX, Operation)
+                    CHANGE_EVENTS_MAX, LEDGER_BALANCE_DTYPE, LEDGERS_MAX, PENDING_FILTER_DTYPE, PENDING_ROW_DTYPE, PENDING_ROWS_MAX, PENDING_STATES, STATEMENT_DTYPE, FILTER_CREDITS, FILTER_DEBITS, FILTER_REVERSED, pack_change_events_filter, QUERY_FILTER_DTYPE, QUERY_REVERSED, TRANSFER_DTYPE, U64_MAX, Operation)
 
 
 @dataclass
@@ -456,6 +456,43 @@ class Engine:
         _lib.check(self.lib.tbgpu_get_pending_transfers(self.h, src, rows.ctypes.data, states.ctypes.data, cap, ctypes.byref(res)))
         return rows[:res.count], states[:res.count], int(res.matched), bool(res.complete)
 
+    STATEMENTS_MAX = 4095  # TBGPU_STATEMENTS_MAX
+
+    def get_account_statements(self, ids, t_open, t_close, out_cap_rows=None):
+        """A statement header per account of `ids` over the period (t_open, t_close]
+        (tbgpu_get_account_statements): the balances at its start and at its end, the gross flows in
+        between and the transfer counts, one row per id the table holds and that existed at t_close,
+        in request order, a repeated id once per occurrence.  t_open 0: from before every record;
+        t_close 0: up to now.  Returns (rows ndarray of STATEMENT_DTYPE, matched, complete);
+        `complete` is False once the engine has evicted transfers or a post in a sum had lost its
+        pending transfer.  An invalid period (an end at 2^64-1, a non-zero t_close below t_open)
+        matches nothing."""
+        ids = [int(i) for i in ids]
+        if len(ids) > self.STATEMENTS_MAX:
+            raise ValueError("at most %d ids in one call" % self.STATEMENTS_MAX)
+        body = b"".join(i.to_bytes(16, "little") for i in ids)
+        return self.get_account_statements_raw(body, t_open, t_close, out_cap_rows)
+
+    def get_account_statements_raw(self, id_bytes, t_open, t_close, out_cap_rows=None):
+        """get_account_statements from the ids' bytes, 16 each ({lo, hi}, little-endian)."""
+        id_bytes = bytes(id_bytes)
+        if len(id_bytes) % 16 != 0:
+            raise ValueError("an id is 16 bytes")
+        n = len(id_bytes) // 16
+        if n > self.STATEMENTS_MAX:
+            raise ValueError("at most %d ids in one call" % self.STATEMENTS_MAX)
+        if n == 0:  # the library returns at once and leaves its result alone
+            return np.zeros(0, dtype=STATEMENT_DTYPE), 0, True
+        cap = n if out_cap_rows is None else int(out_cap_rows)
+        if cap < 0 or cap >> 32:
+            raise ValueError("out_cap_rows is 32 bits")
+        out = np.zeros(max(cap, 1), dtype=STATEMENT_DTYPE)
+        res = _lib.tbgpu_query_result()
+        src = ctypes.create_string_buffer(id_bytes, len(id_bytes))
+        _lib.check(self.lib.tbgpu_get_account_statements(self.h, int(t_open), int(t_close), src, n, out.ctypes.data, cap,
+                                                         ctypes.byref(res)))
+        return out[:res.count], int(res.matched), bool(res.complete)
+
     @staticmethod
     def query_filter(user_data_128=0, user_data_64=0, user_data_32=0, ledger=0, code=0, *, reversed=False,
                      timestamp_min=0, timestamp_max=0, limit=8190):
@@ -843,6 +880,10 @@ class StateMachine:
     def get_pending_transfers(self, account_id=0, **filter):
         """The two-phase transfers with their state (Engine.get_pending_transfers): a read, not a commit."""
         return self.engine.get_pending_transfers(account_id, **filter)
+
+    def get_account_statements(self, ids, t_open, t_close, out_cap_rows=None):
+        """Statement headers over a period (Engine.get_account_statements): a read, not a commit."""
+        return self.engine.get_account_statements(ids, t_open, t_close, out_cap_rows)
 
     def query_transfers(self, **filter):
         """The field-filter query over transfers (Engine.query_transfers): a read, not a commit."""

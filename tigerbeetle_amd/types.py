@@ -132,6 +132,18 @@ PENDING_OPEN, PENDING_EXPIRED, PENDING_POSTED, PENDING_VOIDED = 1 << 4, 1 << 5, 
 PENDING_STATES = PENDING_OPEN | PENDING_EXPIRED | PENDING_POSTED | PENDING_VOIDED
 PENDING_ROWS_MAX = 4095
 
+# tbgpu_account_statement (include/tbgpu.h tbgpu_get_account_statements): 256 bytes, no padding; the
+# balances at the period's start and end in ACCOUNT_DTYPE's column order, the period's gross flows and
+# its transfer counts.
+_BALANCE_COLUMNS = ("debits_pending", "debits_posted", "credits_pending", "credits_posted")
+STATEMENT_DTYPE = np.dtype(
+    _u128("id")
+    + [f for when in ("opening", "closing") for c in _BALANCE_COLUMNS for f in _u128(when + "_" + c)]
+    + [f for side in ("debits", "credits") for c in ("pending_in", "pending_out", "posted_in") for f in _u128(side + "_" + c)]
+    + [("debit_transfers", "<u8"), ("credit_transfers", "<u8")])
+assert STATEMENT_DTYPE.itemsize == 256
+STATEMENTS_MAX = 4095
+
 # tbgpu_query_filter (include/tbgpu.h tbgpu_query_transfers / tbgpu_query_accounts): 64 bytes, no padding.
 QUERY_FILTER_DTYPE = np.dtype(
     _u128("user_data_128") + [("user_data_64", "<u8"), ("user_data_32", "<u4"), ("ledger", "<u4"), ("code", "<u2"),

@@ -757,6 +757,40 @@ pub fn StateMachineType(
             return result.count;
         }
 
+        /// Statement headers for the accounts `ids` over the period (t_open, t_close]
+        /// (tbgpu_get_account_statements; 0 leaves an end open): a read, with no operation in this
+        /// reference's enum, so nothing in commit() dispatches to it (INTEGRATION.md, "Account
+        /// statements over a period"). One 256-byte tbgpu_account_statement per id the engine holds
+        /// and that existed at t_close, in request order, into `output`; returns the bytes written.
+        /// `complete` is false once transfers were evicted or a summed post had lost its pending
+        /// transfer: the caller then merges with the forest.
+        pub fn get_account_statements(
+            self: *StateMachine,
+            t_open: u64,
+            t_close: u64,
+            ids: []const u128,
+            output: []align(16) u8,
+            complete: *bool,
+        ) usize {
+            assert(ids.len <= tbgpu.TBGPU_STATEMENTS_MAX);
+            var result: tbgpu.tbgpu_query_result = undefined;
+            result.count = 0;
+            result.complete = 1;
+            result.matched = 0;
+            check(tbgpu.tbgpu_get_account_statements(
+                self.engine,
+                t_open,
+                t_close,
+                ids.ptr,
+                @intCast(ids.len),
+                output.ptr,
+                @intCast(output.len / @sizeOf(tbgpu.tbgpu_account_statement)),
+                &result,
+            ));
+            complete.* = result.complete != 0;
+            return @as(usize, result.count) * @sizeOf(tbgpu.tbgpu_account_statement);
+        }
+
         pub fn compact(self: *StateMachine, callback: *const fn (*StateMachine) void, op: u64) void {
             assert(self.compact_callback == null);
             assert(self.checkpoint_callback == null);
