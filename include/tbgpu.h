@@ -99,7 +99,8 @@ extern "C" {
 
 typedef struct tbgpu_config {
     uint64_t accounts_max;      /* HBM account table capacity (the groove's object count) */
-    uint64_t transfers_max;     /* HBM transfer store capacity (the whole ledger, over every device) */
+    uint64_t transfers_max;     /* HBM transfer store capacity (the whole ledger, over every device);
+                                   137 bytes per position: record, posted byte, timestamp plane */
     uint32_t pass_events_max;   /* max events in one device pass (tbgpu_commit_many); on a node: per
                                    source device and pass */
     uint32_t pass_batches_max;  /* max prepares in one device pass; on a node: per source device */
@@ -180,10 +181,14 @@ int tbgpu_sync(tbgpu_t* engine);
  * stored (the transfer log from the engine's next position; the groove's insert,
  * src/lsm/groove.zig:950-1014, lands here).  Prepares placed there — by DMA from the message
  * buffers, by a peer, by a generator — and committed with tbgpu_commit_device_async(operation 129,
- * events_dev = *window) are committed IN PLACE: a committed transfer's record is its event with its
- * timestamp written, so the pass stores 8 bytes of it instead of copying 128 (results identical to
- * a copy commit).  The window is valid until the next call that stores transfers; INVALID when the
- * log cannot hold `events` more, or on a node engine. */
+ * events_dev = *window) are committed IN PLACE: a committed create's record is its event where it
+ * lies, and the pass stores its 8-byte timestamp into a dense plane beside the log (one u64 per log
+ * position, 8 bytes of HBM per transfers_max) instead of copying 128 bytes (results identical to a
+ * copy commit).  After the commit the window's bytes are the events as placed — a committed
+ * create's timestamp field may still read 0 — so records are read through the API (lookups,
+ * queries, exports, the write-back), which all return them with their timestamps, never from the
+ * window.  The window is valid until the next call that stores transfers; INVALID when the log
+ * cannot hold `events` more, or on a node engine. */
 int tbgpu_log_window(tbgpu_t* engine, uint64_t events, void** window);
 
 /* Host-memory registration for the replica's message pool (allocated once at init, like every

@@ -469,6 +469,7 @@ static int engine_clear(tbgpu* E) {
     HIPCK(hipMemsetAsync(E->T.xidx, 0, E->xidx_cap * sizeof(u64), E->stream));
     HIPCK(hipMemsetAsync(E->T.xdup, 0, E->xidx_cap, E->stream));
     HIPCK(hipMemsetAsync(E->T.xposted, 0, E->xlog_cap, E->stream));
+    HIPCK(hipMemsetAsync(E->T.xts, 0, E->xlog_cap * sizeof(u64), E->stream));
     HIPCK(hipMemsetAsync(E->bloom, 0, (E->bloom_mask + 1) / 8, E->stream));
     E->log_next = 0;
     E->evicted_total = 0;
@@ -683,7 +684,7 @@ static int engine_init(tbgpu* E) {
 
     size_t free_b = 0, total_b = 0;
     HIPCK(hipMemGetInfo(&free_b, &total_b));
-    const u64 need = E->account_cap * (sizeof(Account) + 4) + E->xlog_cap * (sizeof(Transfer) + 1) +
+    const u64 need = E->account_cap * (sizeof(Account) + 4) + E->xlog_cap * (sizeof(Transfer) + 1 + sizeof(u64)) +
                      E->xidx_cap * (sizeof(u64) + 1) +
                      (u64)E->pe_max * (4 * 4 + 8 * 4 + 128 * PIPE_SLOTS + 8 + 4) + E->dedup_cap * 8;
     if (need > free_b) {
@@ -700,6 +701,7 @@ static int engine_init(tbgpu* E) {
     HIPCK(tbMalloc(E->own, &E->T.xdup, E->xidx_cap));
     HIPCK(tbMalloc(E->own, &E->T.xlog, E->xlog_cap * sizeof(Transfer)));
     HIPCK(tbMalloc(E->own, &E->T.xposted, E->xlog_cap));
+    HIPCK(tbMalloc(E->own, &E->T.xts, E->xlog_cap * sizeof(u64)));  // the timestamp plane (tb_device.h tb_log_ts)
     HIPCK(tbMalloc(E->own, &E->g, sizeof(Globals)));
     {
         // The evicted-id filter: 8 bits per log position (about 2 % false positives at one log's worth
@@ -3238,9 +3240,11 @@ static int engine_evict(tbgpu_t* E, uint64_t keep, uint64_t* evicted) {
         const u64 m = std::min<u64>(cut, kept - a);
         HIPCK(hipMemcpyAsync(E->T.xlog + a, E->T.xlog + cut + a, m * sizeof(Transfer), hipMemcpyDeviceToDevice, E->stream));
         HIPCK(hipMemcpyAsync(E->T.xposted + a, E->T.xposted + cut + a, m, hipMemcpyDeviceToDevice, E->stream));
+        HIPCK(hipMemcpyAsync(E->T.xts + a, E->T.xts + cut + a, m * sizeof(u64), hipMemcpyDeviceToDevice, E->stream));
     }
     HIPCK(hipMemsetAsync(E->T.xlog + kept, 0, cut * sizeof(Transfer), E->stream));
     HIPCK(hipMemsetAsync(E->T.xposted + kept, 0, cut, E->stream));
+    HIPCK(hipMemsetAsync(E->T.xts + kept, 0, cut * sizeof(u64), E->stream));
     HIPCK(hipMemsetAsync(E->T.xidx, 0, E->xidx_cap * sizeof(u64), E->stream));
     if (kept) {
         hipLaunchKernelGGL(tb_evict_reindex, dim3((u32)std::min<u64>(4096, (kept + 255) / 256)), dim3(256), 0, E->stream,

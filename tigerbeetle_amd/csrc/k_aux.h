@@ -18,7 +18,7 @@ __global__ void tb_lookup(Tables T, const u64* ids, u32 n, u8* out, u8* found) {
     } else {
         const u32 pos = tb_transfer_find(T, lo, hi);
         found[i] = pos != TB_NOT_FOUND;
-        if (pos != TB_NOT_FOUND) *(Transfer*)(out + (u64)i * 128) = T.xlog[pos];
+        if (pos != TB_NOT_FOUND) *(Transfer*)(out + (u64)i * 128) = tb_log_load(T, pos);
     }
 }
 
@@ -41,7 +41,7 @@ __global__ void tb_export_transfers(Tables T, u64 first, u64 n, u8* out, u64* co
     const u64 e = T.xidx[i];
     if (e == 0 || (e & XI_TOMB)) return;
     const u32 pos = tb_xi_pos(e);
-    const Transfer& t = T.xlog[pos];
+    const Transfer t = tb_log_load(T, pos);
     const u64 k = atomicAdd((unsigned long long*)count, 1ULL);
     *(Transfer*)(out + k * 128) = t;
     const u8 st = T.xposted[pos];
@@ -128,7 +128,7 @@ __global__ void tb_delta_accounts(Tables T, BalView snap, u64 ts0, u64 first, u6
 
 __device__ static inline bool tb_delta_live(const Tables& T, u64 pos, u64 ts0) {
     const Transfer& t = T.xlog[pos];
-    return t.timestamp > ts0 && tb_transfer_find(T, tb_lo(t.id), tb_hi(t.id)) == (u32)pos;
+    return tb_log_ts(T, pos, t.timestamp) > ts0 && tb_transfer_find(T, tb_lo(t.id), tb_hi(t.id)) == (u32)pos;
 }
 
 __global__ __launch_bounds__(DELTA_THREADS) void tb_delta_log_count(Tables T, u64 pos0, u64 n, u64 ts0, u32* block_counts) {
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(DELTA_THREADS) void tb_delta_log_scatter(Tables T, 
     if (!live) return;
     u64 k = block_base[blockIdx.x] + __popcll(m & ((1ULL << lane) - 1));
     for (u32 w = 0; w < wave; w++) k += s_wave[w];
-    const Transfer& t = T.xlog[pos0 + i];
+    const Transfer t = tb_log_load(T, pos0 + i);
     if (out) *(Transfer*)(out + k * 128) = t;
     if (ids) {
         ids[4 * k] = tb_lo(t.debit_account_id);
@@ -203,7 +203,7 @@ __global__ void tb_delta_posted(Tables T, const u64* pv, const u64* npv, u64* pa
         atomicOr((unsigned long long*)status, 1ULL);
         return;
     }
-    pairs[2 * q] = T.xlog[pos].timestamp;
+    pairs[2 * q] = tb_log_ts(T, pos, T.xlog[pos].timestamp);
     pairs[2 * q + 1] = pv[3 * q + 2];
 }
 

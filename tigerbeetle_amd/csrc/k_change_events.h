@@ -178,7 +178,7 @@ __global__ __launch_bounds__(CHANGE_THREADS) void tb_change_effects(NodeTablesAr
         // The timestamp alone first: below the page's end (every tile of an ordered log's prefix) the
         // ids are never read.
         const u64* w = (const u64*)&T.xlog[pos < n ? pos : 0];
-        const u64 ts = pos < n ? w[15] : 0;
+        const u64 ts = pos < n ? tb_log_ts(T, pos, w[15]) : 0;  // the plane: coalesced, beside chunk 7
         const bool newer = ts > t_last;
         if (__ballot(newer) == 0) continue;  // the whole wave alike
         u32 idx[2] = {CHANGE_NONE, CHANGE_NONE};  // the debit and the credit account's index

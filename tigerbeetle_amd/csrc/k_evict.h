@@ -47,7 +47,7 @@ __global__ void tb_evict_scan(Tables T, u64 cut, u64 n, u64* bloom, u64 mask, u8
     for (u64 pos = (u64)blockIdx.x * blockDim.x + threadIdx.x; pos < n; pos += (u64)gridDim.x * blockDim.x) {
         const Transfer& t = T.xlog[pos];
         const u64 lo = tb_lo(t.id), hi = tb_hi(t.id);
-        const bool alive = t.timestamp != 0 && !tb_id_reserved(lo, hi) && tb_transfer_find(T, lo, hi) == (u32)pos;
+        const bool alive = tb_log_ts(T, pos, t.timestamp) != 0 && !tb_id_reserved(lo, hi) && tb_transfer_find(T, lo, hi) == (u32)pos;
         if (pos < cut) {
             if (alive) {
                 tb_bloom_add(bloom, mask, lo, hi);

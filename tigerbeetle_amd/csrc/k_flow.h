@@ -308,7 +308,7 @@ __device__ static inline u64 fl_run_unit(const PassArgs& P, const FlowArgs& F, R
         Transfer t = *(const Transfer*)ev;
         const u32 L = (u32)(bend - boff);
         const u32 i = (u32)(P.e0 + pe - boff);
-        // In place, kernel 1 stamped an HZ_INPLACE event's record (= the event): its field was 0.
+        // In place, an HZ_INPLACE event is its record and its timestamp is in the plane: its field is 0.
         const u64 evts = (P.routed || (info & HZ_INPLACE)) ? 0 : t.timestamp;
         const bool linked = flags & TF_LINKED;
         u32 result;

@@ -238,7 +238,7 @@ __global__ __launch_bounds__(LEDGER_THREADS) void tb_ledger_effects(NodeTablesAr
         // The timestamp alone first: at or below T (every tile of an ordered log's prefix) nothing else
         // is read.
         const u64* w = (const u64*)&T.xlog[pos < n ? pos : 0];
-        const u64 ts = pos < n ? w[15] : 0;
+        const u64 ts = pos < n ? tb_log_ts(T, pos, w[15]) : 0;  // the plane: coalesced, beside chunk 7
         const bool newer = ts > t_at;
         if (__ballot(newer) == 0) continue;  // the whole wave alike
         u32 my = CHANGE_NONE;

@@ -819,7 +819,7 @@ __global__ void tb_seq_load_transfers(NodeTablesArgs N, SeqSet tset, Tables X, u
         const Tables& H = N.T[tb_home(q.lo, q.hi, N.world)];
         const u32 pos = tb_transfer_find(H, q.lo, q.hi);
         if (pos == TB_NOT_FOUND) continue;
-        const Transfer t = H.xlog[pos];
+        const Transfer t = tb_log_load(H, pos);  // the copy carries its timestamp in its field
         const u32 xp = (u32)tb_wave_claim(true, loaded);
         X.xlog[xp] = t;
         X.xposted[xp] = H.xposted[pos];
@@ -897,7 +897,7 @@ __global__ void tb_seq_writeback_transfers(Tables X, u64 base, u64 n, SeqSet tse
                                            u64 h_base, u64* h_count) {
     const u64 stride = (u64)gridDim.x * blockDim.x;
     for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const Transfer& t = X.xlog[base + i];
+        const Transfer t = tb_log_load(X, base + i);  // the copy carries its timestamp in its field
         if (t.timestamp == 0 || tb_home(tb_lo(t.id), tb_hi(t.id), world) != self) continue;
         if (tb_transfer_find(X, tb_lo(t.id), tb_hi(t.id)) != (u32)(base + i)) continue;  // withdrawn
         const u64 lp = h_base + tb_wave_claim(true, h_count);

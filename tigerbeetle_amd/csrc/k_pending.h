@@ -42,8 +42,8 @@ __global__ __launch_bounds__(QUERY_THREADS) void tb_pending_gather(Tables T, Que
     if (pos >= n) return;
     const ulonglong2* c = (const ulonglong2*)&T.xlog[pos];
     const ulonglong2 b = c[6], d = c[7];
-    const QueryPendingFields f{d.y, (u32)(b.y >> 32), (u32)(d.x >> 48)};
-    *(Transfer*)(out + (u64)i * 128) = T.xlog[pos];
+    const QueryPendingFields f{tb_log_ts(T, pos, d.y), (u32)(b.y >> 32), (u32)(d.x >> 48)};
+    *(Transfer*)(out + (u64)i * 128) = tb_log_load(T, pos);
     flt.states[i] = (u8)flt.state(f, T.xposted, pos);
 }
 
@@ -65,13 +65,15 @@ __global__ __launch_bounds__(PENDING_THREADS) void tb_pending_resolutions(Tables
         const ulonglong2* c = (const ulonglong2*)&T.xlog[pos];
         const ulonglong2 d = c[7];
         const u32 tf = (u32)(d.x >> 48);
-        if (d.y <= ts_floor || !(tf & (TF_POST | TF_VOID)) || (tf & TF_PENDING)) continue;
+        // A post / void's record is always written whole (its field holds its timestamp): a zero
+        // field is a create's or a dead position's, which the flags drop.
+        if (!(tf & (TF_POST | TF_VOID)) || (tf & TF_PENDING) || tb_log_ts(T, pos, d.y) <= ts_floor) continue;
         const ulonglong2 p = c[4];
         const u32 index = tb_change_probe(s_set, mask, ids, p.x, p.y);
         if (index == CHANGE_NONE) continue;
         // Live: the id index holds this record's id at this position (tb_query_hit's test).
         const ulonglong2 id = c[0];
         if (tb_id_reserved(id.x, id.y) || tb_transfer_find(T, id.x, id.y) != (u32)pos) continue;
-        *(Transfer*)(slots + (u64)index * 128) = T.xlog[pos];
+        *(Transfer*)(slots + (u64)index * 128) = tb_log_load(T, pos);
     }
 }

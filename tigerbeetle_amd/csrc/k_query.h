@@ -135,7 +135,7 @@ __device__ static inline typename F::Fields tb_query_fields(const Tables& T, u64
         if (pos < n) {
             const ulonglong2* c = (const ulonglong2*)&T.xlog[pos];
             const ulonglong2 b = c[6], d = c[7];
-            v.timeout = (u32)(b.y >> 32), v.flags = (u32)(d.x >> 48), v.ts = d.y;
+            v.timeout = (u32)(b.y >> 32), v.flags = (u32)(d.x >> 48), v.ts = tb_log_ts(T, pos, d.y);
         }
         return v;
     } else if constexpr (std::is_same<F, QueryFieldFilter>::value) {
@@ -146,7 +146,7 @@ __device__ static inline typename F::Fields tb_query_fields(const Tables& T, u64
             const ulonglong2* c = (const ulonglong2*)&T.xlog[pos];
             const ulonglong2 a = c[5], b = c[6], d = c[7];
             v.u128_lo = a.x, v.u128_hi = a.y, v.u64v = b.x, v.u32v = (u32)b.y;
-            v.ledger = (u32)d.x, v.code = (u32)(d.x >> 32) & 0xFFFF, v.ts = d.y;
+            v.ledger = (u32)d.x, v.code = (u32)(d.x >> 32) & 0xFFFF, v.ts = tb_log_ts(T, pos, d.y);
         }
         return v;
     } else {
@@ -156,7 +156,7 @@ __device__ static inline typename F::Fields tb_query_fields(const Tables& T, u64
         if (pos < n) {
             const ulonglong2* c = (const ulonglong2*)&T.xlog[pos];
             const ulonglong2 d = c[1], cr = c[2];
-            f.ts = ((const u64*)c)[15];
+            f.ts = tb_log_ts(T, pos, ((const u64*)c)[15]);
             f.dlo = d.x, f.dhi = d.y, f.clo = cr.x, f.chi = cr.y;
         }
         return f;
@@ -174,6 +174,8 @@ __device__ static inline typename F::Fields tb_query_fields(const Tables& T, u64
     __syncthreads();
     const ulonglong2 d = s[lane * 3], cr = s[lane * 3 + 1], t = s[lane * 3 + 2];
     f.dlo = d.x, f.dhi = d.y, f.clo = cr.x, f.chi = cr.y, f.ts = t.y;
+    // A zero field of a record inside the log: the plane, one coalesced 8-B load per lane.
+    if (f.ts == 0 && wave0 + lane < n) f.ts = T.xts[wave0 + lane];
     return f;
     }
 }
@@ -321,7 +323,7 @@ __global__ __launch_bounds__(QUERY_THREADS) void tb_query_scatter(Tables T, F fl
     if (!hit || rank < lo || rank >= hi) return;
     const u64 dst = reversed ? total - 1 - rank : rank;
     if (dst < k) {
-        *(Transfer*)(out + dst * 128) = T.xlog[pos];
+        *(Transfer*)(out + dst * 128) = tb_log_load(T, pos);
         if constexpr (std::is_same<F, QueryPendingFilter>::value) flt.states[dst] = (u8)flt.state(f, T.xposted, pos);
     }
 }
@@ -349,5 +351,5 @@ __global__ __launch_bounds__(QUERY_THREADS) void tb_query_gather(Tables T, const
     const u32 i = blockIdx.x * QUERY_THREADS + threadIdx.x;
     if (i >= m) return;
     const u64 pos = positions[i];
-    if (pos < n) *(Transfer*)(out + (u64)i * 128) = T.xlog[pos];
+    if (pos < n) *(Transfer*)(out + (u64)i * 128) = tb_log_load(T, pos);
 }

@@ -309,7 +309,7 @@ __global__ __launch_bounds__(QUERY_THREADS) void tb_qm_scatter(Tables T, const Q
             const u64 rank = start + __popcll(b & ((1ULL << lane) - 1));
             if (rank < s_lo[bit] || rank >= s_hi[bit]) continue;
             const u64 dst = ((s_tab.reversed >> bit) & 1) ? s_total[bit] - 1 - rank : rank;
-            if (dst < s_tab.k[bit]) *(Transfer*)(out + (s_start[bit] + dst) * 128) = T.xlog[pos];
+            if (dst < s_tab.k[bit]) *(Transfer*)(out + (s_start[bit] + dst) * 128) = tb_log_load(T, pos);
         }
         run += tot;
     }

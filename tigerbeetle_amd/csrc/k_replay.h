@@ -298,7 +298,10 @@ __device__ static inline u32 rp_post_or_void(Replay& R, const Transfer& t, u32 l
 
     const u32 pslot = rp_transfer_find<FLOW>(T, tb_lo(t.pending_id), tb_hi(t.pending_id));
     if (pslot == TB_NOT_FOUND) return CT_PENDING_TRANSFER_NOT_FOUND;
-    const Transfer p = rp_load<FLOW>(&T.xlog[pslot]);
+    Transfer p = rp_load<FLOW>(&T.xlog[pslot]);
+    // A zero field: an in-place record, its timestamp in the plane, written by kernel 1 of this pass
+    // or of an earlier one (no unit of the ordered path writes the plane).
+    p.timestamp = tb_log_ts(T, pslot, p.timestamp);
     if (!(p.flags & TF_PENDING)) return CT_PENDING_TRANSFER_NOT_PENDING;
     // hint: the pending transfer's account slots, from kernel 1 (it found the same record: an
     // earlier pass's, whose id no event of this pass can re-create).
@@ -529,7 +532,7 @@ __device__ static inline u64 rp_batch(const PassArgs& P, Replay& R, u32 b) {
         const u32 i = list[k];
         const u8* ev = P.events + (boff + i) * 128;
         const u16 flags = P.eflags[pbase + i];
-        const u64 evts = (P.routed || (P.info[pbase + i] & HZ_INPLACE)) ? 0 : *(const u64*)(ev + 120);  // stamped in place
+        const u64 evts = (P.routed || (P.info[pbase + i] & HZ_INPLACE)) ? 0 : *(const u64*)(ev + 120);  // in place: its field is the 0 it was checked to be
         const bool linked = flags & 1;
         u32 result;
         if (linked && !in_chain) {

@@ -192,7 +192,8 @@ __device__ static inline void tb_emit_legs(const PassArgs& P, u32 pbase, u32 leg
 
 // In-place pass: an independent ok post / void's record is composed here over its event (kernel 1
 // did not write it, so the ordered path could still read the event as given).  A create's record is
-// its event, stamped by kernel 1 (HZ_INPLACE).
+// its event as it lies, its timestamp in the plane (HZ_INPLACE, tb_log_ts); the pending record's
+// timestamp is not part of a post / void's record, so it is read here without the plane.
 __device__ static inline void tb_inplace_record(const PassArgs& P, u32 pe, u32 info, u64 ts) {
     if (!(info & HZ_POSTVOID)) return;
     Transfer* rec = &P.T.xlog[P.log_base + pe];

@@ -352,7 +352,7 @@ __global__ void tb_fetch_transfers(Tables T, const u64* ids, u32 n, u8* out, u8*
         state[i] = 0;
         return;
     }
-    *(Transfer*)(out + (u64)i * 128) = T.xlog[pos];
+    *(Transfer*)(out + (u64)i * 128) = tb_log_load(T, pos);
     state[i] = 1 + T.xposted[pos];
 }
 

@@ -84,7 +84,7 @@ __global__ __launch_bounds__(CHANGE_THREADS) void tb_statement_effects(NodeTable
         // The timestamp alone first: at or below t_open (every tile of an ordered log's prefix) the
         // ids are never read.
         const u64* w = (const u64*)&T.xlog[pos < n ? pos : 0];
-        const u64 ts = pos < n ? w[15] : 0;
+        const u64 ts = pos < n ? tb_log_ts(T, pos, w[15]) : 0;  // the plane: coalesced, beside chunk 7
         const bool wanted = ts > t_open;
         if (__ballot(wanted) == 0) continue;  // the whole wave alike
         const u32 zone = t_close != 0 && ts > t_close ? 0 : 1;

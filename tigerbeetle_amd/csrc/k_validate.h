@@ -18,8 +18,9 @@ struct TransferScratch {
     u128 amount = 0;        // amount applied by an independent ok event (post: posted amount)
     u128 contrib = 0;       // contribution to S (overflow certificate)
     u64 kid = 0, kpid = 0;  // dedup keys of id / pending_id
-    u64 rec_ts = 0;         // != 0: the event's record is the event with this timestamp (written
-                            // from the LDS stage by the whole workgroup, coalesced)
+    u64 rec_ts = 0;         // != 0: the event's record is the event with this timestamp (HZ_REC: written
+                            // from the LDS stage by the whole workgroup, coalesced; HZ_INPLACE: the
+                            // event where it lies, the timestamp into the plane)
 };
 
 // create_transfer_exists (state_machine.zig:886-905).
@@ -142,7 +143,7 @@ __device__ static inline u32 tb_validate_post_void(const PassArgs& P, const Tran
         return R_OK;
     }
     if (pslot == TB_NOT_FOUND) return CT_PENDING_TRANSFER_NOT_FOUND;
-    const Transfer p = T.xlog[pslot];
+    const Transfer p = tb_log_load(T, pslot);
     if (!(p.flags & TF_PENDING)) return CT_PENDING_TRANSFER_NOT_PENDING;
 
     const u32 drs = tb_account_find(T, tb_lo(p.debit_account_id), tb_hi(p.debit_account_id));
@@ -284,10 +285,10 @@ __device__ static inline u32 tb_validate_transfer(const PassArgs& P, const Trans
     const u64 timeout_ns = (u64)t.timeout * 1000000000ULL;
     if (ts + timeout_ns < ts) return CT_OVERFLOWS_TIMEOUT;  // entry withdrawn by kernel 2
     if ((s.hz & HZ_SPEC) && P.inplace) {
-        // The record is the event in place: 8 bytes of it written here (its line was just read).  The
-        // ordered path reads an HZ_INPLACE event's timestamp field as the 0 it was checked to be.
+        // The record is the event in place, untouched: its timestamp field stays the 0 it was checked
+        // to be, and the kernel's epilogue stores the timestamp in the plane (tb_log_ts).
         s.hz |= HZ_INPLACE;
-        P.T.xlog[P.log_base + pe].timestamp = ts;
+        s.rec_ts = ts;
     } else if ((s.hz & HZ_SPEC) && !TB_ABL(P, ABL_RECORD)) {
         s.rec_ts = ts;
         s.hz |= HZ_REC;
@@ -353,6 +354,12 @@ __global__ __launch_bounds__(VALIDATE_THREADS) void tb_transfers_validate(PassAr
         P.amt[pe] = tb_lo(s.amount);
         if (s.hz & HZ_AMT_HI) P.amt_hi[pe] = tb_hi(s.amount);
         if (code != R_OK) s.contrib = 0;
+        // In place: the plane takes the timestamp of an HZ_INPLACE event and 0 for every other event
+        // of the pass (rec_ts is non-zero for exactly the former), 512 contiguous bytes per wave.
+        if (P.inplace) {
+            if (!TB_ABL(P, ABL_STAMP)) P.T.xts[P.log_base + pe] = s.rec_ts;
+            s.rec_ts = 0;
+        }
         // The record (create_transfer :870) is the event as staged, with its timestamp.
         if (s.rec_ts) *(u64*)(stage + tb_stage_off(threadIdx.x, 7) + 8) = s.rec_ts;  // timestamp @120
     }

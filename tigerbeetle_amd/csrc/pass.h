@@ -34,8 +34,8 @@ enum : u32 {
     HZ_LATE = 1u << 20,      // tb_resolve: an independent ok create_transfers event that is not a
                              // balance leg — tb_apply_events applies exactly these
     HZ_INPLACE = 1u << 21,   // in-place pass (PassArgs.inplace): the event at log_base + event is its
-                             // record, and kernel 1 wrote its timestamp there (read back as 0 by the
-                             // ordered path, which re-evaluates the event)
+                             // record, and kernel 1 wrote its timestamp into the plane (T.xts,
+                             // tb_log_ts); its field stays 0
 };
 
 #define SUM_SHARDS 64
@@ -93,11 +93,11 @@ struct PassArgs {
     const u64* ev_ts;
     // In-place pass (tbgpu_log_window): the events already sit at their transfer-log positions
     // (events + (e0 + pe) * 128 == &T.xlog[log_base + pe]).  Kernel 1 writes the timestamp of each
-    // create that may commit (HZ_INPLACE: its record is the event) and no post / void record;
-    // tb_resolve composes the record of each independent ok post / void over its event; the ordered
-    // path stores its records as always.  No kernel reads an event's bytes after its record is
-    // written, except its id and pending id, which a record keeps, and an HZ_INPLACE event's
-    // timestamp, which the ordered path takes as the 0 kernel 1 checked.
+    // create that may commit (HZ_INPLACE: its record is the event) into the timestamp plane
+    // (T.xts[log_base + pe], 0 for the pass's other events) and no post / void record; tb_resolve
+    // composes the record of each independent ok post / void over its event; the ordered path stores
+    // its records as always.  No kernel reads an event's bytes after its record is written, except
+    // its id and pending id, which a record keeps.
     u32 inplace;
     // Balance legs (k_apply.h): with the 64-bit certificate, the balance deltas of independent ok
     // create_transfer events are written as legs, bucketed by account slot per prepare, and summed
@@ -194,7 +194,8 @@ __device__ static inline bool tb_ts_carried(const PassArgs& P) { return P.routed
 #endif
 enum : u32 { ABL_DEDUP = 1, ABL_SPEC = 2, ABL_ACCTS = 4, ABL_XFIND = 8, ABL_STAGE = 16, ABL_RECORD = 32, ABL_CAS = 64, EXP_NT = 128,
              ABL_LEGS = 256, ABL_LEG_STORES = 512, ABL_LEG_WORK = 1024,  // ABL_LEG_*: timing only (wrong balances)
-             ABL_FLOW = 2048 };  // sequential replay instead of the parallel flow path (exact either way)
+             ABL_FLOW = 2048,    // sequential replay instead of the parallel flow path (exact either way)
+             ABL_STAMP = 4096 };  // timing only: kernel 1 stores no in-place timestamp (the plane keeps what it held)
 
 // Batch of a call-relative event index: binary search over batch_off[lo..hi) (off[lo] <= e < off[hi]).
 __device__ static inline u32 tb_batch_search(const u64* off, u32 lo, u32 hi, u64 e) {

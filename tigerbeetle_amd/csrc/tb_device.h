@@ -284,6 +284,7 @@ struct Tables {
     u64 xidx_mask;
     Transfer* xlog;           // [xlog_cap]
     u8* xposted;              // [xlog_cap] POSTED_* of the pending transfer at that log position
+    u64* xts;                 // [xlog_cap] the timestamp plane (tb_log_ts)
     u64 xlog_cap;
     Globals* g;
 };
@@ -541,6 +542,20 @@ __device__ static inline u32 tb_transfer_find(const Tables& T, u64 lo, u64 hi) {
         pos = tb_xi_next(pos, T.xidx_mask);
     }
     return TB_NOT_FOUND;
+}
+
+// The timestamp of the record at a log position: its own field when that field is non-zero, and
+// otherwise xts[pos] (timestamps are >= 1, so 0 is free to mean "look in the plane").  The plane has
+// one writer: an in-place pass's kernel 1 (k_validate.h) stores there, coalesced, the timestamp of each
+// create whose event is its record — and 0 for the pass's other events — instead of 8 B into each
+// 128-B event line.  Every path that writes a whole record writes the field and leaves the plane
+// alone.  No reader takes a log record's timestamp, or hands a record to a caller, but through
+// these two.
+__device__ static inline u64 tb_log_ts(const Tables& T, u64 pos, u64 field) { return field ? field : T.xts[pos]; }
+__device__ static inline Transfer tb_log_load(const Tables& T, u64 pos) {
+    Transfer t = T.xlog[pos];
+    t.timestamp = tb_log_ts(T, pos, t.timestamp);
+    return t;
 }
 
 enum : u32 { CLAIM_NEW = 0, CLAIM_EXISTS = 1, CLAIM_COLLIDED = 2, CLAIM_FULL = 3 };
