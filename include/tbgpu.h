@@ -26,6 +26,7 @@
  *   (no reference: a trial balance per ledger)             tbgpu_get_ledger_balances (likewise)
  *   (no reference: pending transfers with their state)     tbgpu_get_pending_transfers (likewise)
  *   (no reference: account statements over a period)       tbgpu_get_account_statements (likewise)
+ *   (no reference: time-weighted balances over a period)   tbgpu_get_account_balance_integrals (likewise)
  *   `setup` action of the table tests (:1398-1407)         tbgpu_test_set_balances (test only)
  *   StateMachine.commit_timestamp field (:251)             tbgpu_commit_timestamp
  *
@@ -759,6 +760,67 @@ typedef struct tbgpu_account_statement {   /* 256 bytes, little-endian, no paddi
 int tbgpu_get_account_statements(tbgpu_t* engine, uint64_t t_open, uint64_t t_close,
                                  const void* ids /* n x {lo, hi} */, uint32_t n,
                                  void* out, uint32_t out_cap_rows, tbgpu_query_result* result);
+
+/* get_account_balance_integrals: for each account the caller names, over a period the caller names,
+ * how much was held for how long — the time integral of each of the four balances over the period,
+ * balance x nanoseconds, the "average daily balance" once divided by the period's length: what every
+ * interest, fee and overdraft calculation starts from.  No reference has an operation for it, and
+ * paging tbgpu_get_account_balances per account to integrate on the host is a log scan per account
+ * per page; this call derives it in one scan of the log in HBM, whatever the number of ids, and stores
+ * nothing at commit.  An entry point of its own, as above; this comment is its specification.
+ *   The period is (t_open, t_end], as tbgpu_get_account_statements' is.  t_open == 0 is read
+ *     literally.  t_close == 0 means t_end = tbgpu_commit_timestamp (a node: the node's own), read once
+ *     at the call — an integral needs a finite end; otherwise t_end = t_close.  L = t_end - t_open.
+ *     The row carries the period as used (t_open, t_end).
+ *   Which rows: tbgpu_lookup_accounts_at's rules with T = t_end — one 256-byte row per requested id
+ *     that its owner's account table holds, in request order.  Absent ids and the reserved ids (0,
+ *     2^128-1) are skipped; a repeated id is answered once per occurrence; an account whose own
+ *     timestamp is above t_end is skipped.  `matched` is the number of ids that yield a row; count =
+ *     min(matched, out_cap_rows), the first ones in request order; bytes past count rows are not
+ *     written.
+ *   opening, closing: tbgpu_lookup_accounts_at's formula at t_open and at t_end, byte for byte
+ *     tbgpu_get_account_statements' fields for the same (t_open, t_end).
+ *   integral[c], for each column c of {debits_pending, debits_posted, credits_pending,
+ *     credits_posted}, three words, low word first, modulo 2^192:
+ *         integral[c] = the sum over t = t_open .. t_end - 1 of balance_at(a, t).c
+ *     where balance_at is tbgpu_lookup_accounts_at's formula: its anchor at the current balance, its
+ *     effect table, the P rule, the orphan rule and the liveness rule.  The balance is below 2^128 and
+ *     L below 2^64, so the value fits and the modular result is exact.  It is computed without any
+ *     order of the log, as
+ *         integral[c] = opening.c * L + the sum of effect(r).c * (t_end - r.timestamp)
+ *     over the live resident records r that name the account with t_open < r.timestamp <= t_end (a
+ *     record at t_end weighs 0); a released hold's effect on a *_pending column is negative and enters
+ *     as its two's complement modulo 2^192.  The two forms are equal wherever no balance_at in the
+ *     period falls below zero; one that does — only behind a tbgpu_test_set_balances or
+ *     tbgpu_load_accounts step that set a balance below what the later records move — counts as that
+ *     negative number, not as its wrap modulo 2^128, while `opening` itself is the wrapped value the
+ *     other calls give.  L == 0 gives zero integrals and opening == closing.  Timestamps before the
+ *     account's creation follow the definition: zero on an engine that never had its balances set or
+ *     loaded.  The integrals are additive: over (t0, t1] and (t1, t2] they add to (t0, t2]'s.
+ *   complete: tbgpu_lookup_accounts_at's rule.
+ *   t_open or t_close equal to 2^64-1, or t_end below t_open (this includes t_close == 0 with
+ *     commit_timestamp < t_open), returns TBGPU_STATUS_OK with count = matched = 0.  n == 0 returns
+ *     TBGPU_STATUS_OK and writes nothing.  n > TBGPU_INTEGRALS_MAX, or a NULL ids, out or result with
+ *     n > 0, is TBGPU_STATUS_INVALID and writes nothing.  After any failing status the result names
+ *     no row.
+ *   The call contract of tbgpu_get_account_statements: synchronous, drains a pending
+ *     tbgpu_commit_device_async first, a read that changes nothing, works on an engine a device panic
+ *     stopped, allocates nothing after tbgpu_init, legal beside an asynchronous write-back.
+ *   A node engine has the same contract: every home shard scans its own log on its own device and
+ *     stream, side by side, reading a post's pending transfer on the home shard of its pending_id;
+ *     each account's record, and whether it existed at t_end, come from its owner shard only; the
+ *     host adds the shards' sums modulo 2^192. */
+#define TBGPU_INTEGRALS_MAX 4095u            /* 256 B rows in one message body */
+typedef struct tbgpu_account_balance_integral {   /* 256 bytes, little-endian, no padding */
+    uint64_t id_lo, id_hi;
+    uint64_t opening[8];      /* debits_pending, debits_posted, credits_pending, credits_posted: lo, hi each */
+    uint64_t closing[8];      /* likewise */
+    uint64_t integral[12];    /* the same four columns, three words each, low word first: balance x ns, mod 2^192 */
+    uint64_t t_open, t_end;   /* the period as used: t_end is t_close, or commit_timestamp where t_close was 0 */
+} tbgpu_account_balance_integral;
+int tbgpu_get_account_balance_integrals(tbgpu_t* engine, uint64_t t_open, uint64_t t_close,
+                                        const void* ids /* n x {lo, hi} */, uint32_t n,
+                                        void* out, uint32_t out_cap_rows, tbgpu_query_result* result);
 
 /* The replica writes StateMachine.commit_timestamp itself: the header timestamp after every commit
  * (src/vsr/replica.zig:3664-3665) and the checkpoint's value on open / state sync.  The wrapper

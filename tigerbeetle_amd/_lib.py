@@ -112,6 +112,16 @@ class tbgpu_account_statement(ctypes.Structure):
 STATEMENTS_MAX = 4095  # TBGPU_STATEMENTS_MAX
 
 
+class tbgpu_account_balance_integral(ctypes.Structure):
+    _fields_ = [("id_lo", ctypes.c_uint64), ("id_hi", ctypes.c_uint64),
+                ("opening", ctypes.c_uint64 * 8), ("closing", ctypes.c_uint64 * 8),
+                ("integral", ctypes.c_uint64 * 12),
+                ("t_open", ctypes.c_uint64), ("t_end", ctypes.c_uint64)]
+
+
+INTEGRALS_MAX = 4095  # TBGPU_INTEGRALS_MAX
+
+
 class tbgpu_stats(ctypes.Structure):
     _fields_ = [
         ("passes", ctypes.c_uint64),
@@ -239,6 +249,7 @@ SIGNATURES = [
     ("tbgpu_get_ledger_balances", ctypes.c_int, [_P, _U64, _P, _U32, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_get_pending_transfers", ctypes.c_int, [_P, _P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_get_account_statements", ctypes.c_int, [_P, _U64, _U64, _P, _U32, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
+    ("tbgpu_get_account_balance_integrals", ctypes.c_int, [_P, _U64, _U64, _P, _U32, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_query_transfers", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_query_accounts", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_bench_query_keys_max", ctypes.c_int, [_P, _U32]),

@@ -39,6 +39,7 @@
 #include "k_change_events.h"
 #include "k_asof.h"
 #include "k_statement.h"
+#include "k_integral.h"
 #include "k_ledgers.h"
 #include "k_pending.h"
 #include "checksum.h"

@@ -1,7 +1,7 @@
 // query.h — the host side of the queries (include/tbgpu.h): get_account_transfers and its batched form
 // get_account_transfers_many, get_account_balances, query_transfers, query_accounts,
-// get_change_events, lookup_accounts_at, get_ledger_balances, get_pending_transfers and
-// get_account_statements; their buffers, made at tbgpu_init, and their entry points.  Included by engine.hip after the engine's own helpers and before node.h.
+// get_change_events, lookup_accounts_at, get_ledger_balances, get_pending_transfers,
+// get_account_statements and get_account_balance_integrals; their buffers, made at tbgpu_init, and their entry points.  Included by engine.hip after the engine's own helpers and before node.h.
 //
 // Every query is written once, over a list of engines (QueryCall): the one engine, or a node's shards.
 // A transfer lives on its home shard only and an account is answered by its owner only, so every
@@ -176,6 +176,15 @@ struct StatementBufs {
 };
 #define STATEMENT_BIN_BYTES(n) (((u64)(n) * STATEMENT_BIN_WORDS + 1) * 8)
 
+// tbgpu_get_account_balance_integrals (k_integral.h): the same request, set, records, flags, rows and
+// result words as a statements call, at the same sizes, and both calls are synchronous — it works in
+// StatementBufs.  Only its bins are wider (INTEGRAL_BIN_WORDS), so they are its own.
+struct IntegralBufs {
+    u64* d_bins = nullptr;  // [INTEGRAL_IDS_MAX][INTEGRAL_BIN_WORDS] the bins by request position, then the flag word
+    u64* h_bins = nullptr;  // pinned mirror, read by a node's host only: it adds the shards' bins
+};
+#define INTEGRAL_BIN_BYTES(n) (((u64)(n) * INTEGRAL_BIN_WORDS + 1) * 8)
+
 // One engine's query buffers (tbgpu::qs), in the order query_init makes them.
 struct QueryState {
     QueryBufs q;
@@ -187,6 +196,7 @@ struct QueryState {
     LedgerBufs qg;
     PendingBufs qp;
     StatementBufs qt;
+    IntegralBufs qi;
 };
 
 // Called by engine_init on the engine's device, after every other buffer.  The buffers go into the
@@ -319,6 +329,11 @@ static int query_init(tbgpu* E) {
         HIPCK(tbHostMalloc(E->own, &S.h_bins, bin_bytes, hipHostMallocDefault));
         HIPCK(tbHostMalloc(E->own, &S.h_accounts, ni * 128, hipHostMallocDefault));
         HIPCK(tbHostMalloc(E->own, &S.h_found, ni * 4, hipHostMallocDefault));
+    }
+    {  // tbgpu_get_account_balance_integrals: its bins; the rest is the statements call's
+        IntegralBufs& I = E->qs->qi;
+        HIPCK(tbMalloc(E->own, &I.d_bins, INTEGRAL_BIN_BYTES(INTEGRAL_IDS_MAX)));
+        HIPCK(tbHostMalloc(E->own, &I.h_bins, INTEGRAL_BIN_BYTES(INTEGRAL_IDS_MAX), hipHostMallocDefault));
     }
     return TBGPU_STATUS_OK;
 }
@@ -1473,6 +1488,148 @@ extern "C" int tbgpu_get_account_statements(tbgpu_t* E, uint64_t t_open, uint64_
         HIPCK(hipStreamSynchronize(S0->stream));
     }
     if (S.h_res[STATEMENT_RES_ORPHAN]) result->complete = 0;
+    result->count = m;
+    result->matched = matched;
+    return TBGPU_STATUS_OK;
+}
+
+// ---- get_account_balance_integrals (k_integral.h, include/tbgpu.h) --------------------------------
+// get_account_statements' shape with T = t_end, a scan of its own and wider bins.  One engine: ids up,
+// set and bins zeroed, tb_asof_gather -> tb_integral_effects -> tb_integral_emit on the engine stream,
+// the result words back; one wait; then the answer's count * 256 bytes.  The request, the set, the
+// records, the flags, the rows and the result words are the statements call's buffers (StatementBufs);
+// the bins are IntegralBufs'.  A node: every shard gathers and scans its own log on its own device and
+// stream, side by side; the host adds the shards' bins modulo 2^128 and 2^192 and writes the rows
+// (tb_integral_row).
+static int integrals_enqueue(tbgpu* E, const NodeTablesArgs& NT, u32 self, u32 n, u64 t_open, u64 t_end, bool emit, u32 cap) {
+    StatementBufs& S = E->qs->qt;
+    IntegralBufs& I = E->qs->qi;
+    HIPCK(hipSetDevice(E->device));
+    const u32 slots = tb_change_set_slots(n), mask = slots - 1;
+    const u64 bin_bytes = INTEGRAL_BIN_BYTES(n);
+    const unsigned nb_ids = (n + QUERY_THREADS - 1) / QUERY_THREADS;
+    HIPCK(hipMemcpyAsync(S.d_ids, S.h_ids, (u64)n * 16, hipMemcpyHostToDevice, E->stream));
+    HIPCK(hipMemsetAsync(S.d_set, 0, (u64)slots * 4, E->stream));
+    HIPCK(hipMemsetAsync(I.d_bins, 0, bin_bytes, E->stream));
+    const bool store = emit || self == 0;  // a node reads the first shard's records only
+    hipLaunchKernelGGL(tb_asof_gather, dim3(nb_ids), dim3(QUERY_THREADS), 0, E->stream, NT, (const u64*)S.d_ids, n, t_end,
+                       store ? S.d_accounts : nullptr, store ? S.d_found : nullptr, S.d_set, mask);
+    HIPCK(hipGetLastError());
+    const u64 records = E->log_next, per = (u64)CHANGE_THREADS * CHANGE_TILES, nb = (records + per - 1) / per;
+    if (nb) {
+        const size_t lds = (size_t)slots * 4 + (size_t)INTEGRAL_LDS_BINS * (INTEGRAL_BIN_WORDS * 8 + 4);
+        hipLaunchKernelGGL(tb_integral_effects, dim3((unsigned)nb), dim3(CHANGE_THREADS), lds, E->stream, NT, self, records, t_open,
+                           t_end, (const u32*)S.d_set, mask, (const u64*)S.d_ids, n, I.d_bins);
+        HIPCK(hipGetLastError());
+    }
+    if (emit) {
+        hipLaunchKernelGGL(tb_integral_emit, dim3(nb_ids), dim3(QUERY_THREADS), 0, E->stream, (const u64*)S.d_ids, n,
+                           (const u8*)S.d_accounts, (const u32*)S.d_found, (const u32*)S.d_set, mask, (const u64*)I.d_bins, t_open,
+                           t_end, cap, S.d_out, S.d_res);
+        HIPCK(hipGetLastError());
+        HIPCK(hipMemcpyAsync(S.h_res, S.d_res, INTEGRAL_RES_WORDS * 8, hipMemcpyDeviceToHost, E->stream));
+        return TBGPU_STATUS_OK;
+    }
+    HIPCK(hipMemcpyAsync(I.h_bins, I.d_bins, bin_bytes, hipMemcpyDeviceToHost, E->stream));
+    if (self == 0) {
+        HIPCK(hipMemcpyAsync(S.h_accounts, S.d_accounts, (u64)n * 128, hipMemcpyDeviceToHost, E->stream));
+        HIPCK(hipMemcpyAsync(S.h_found, S.d_found, (u64)n * 4, hipMemcpyDeviceToHost, E->stream));
+    }
+    return TBGPU_STATUS_OK;
+}
+
+// A node's answer from its shards' pinned mirrors, as statements_node_rows builds it: the found
+// positions in request order, each from its record and the sum of every shard's bin of its id (the bin
+// of the smallest position that names the id).  The bins' words add as the device added them: the
+// eight 128-bit sums and the four 192-bit sums, each with its carries.
+static void integrals_node_rows(const QueryCall& c, u32 n, u64 t_open, u64 t_end, u32 cap, u8* out, tbgpu_query_result* result) {
+    const StatementBufs& S = c.Es[0]->qs->qt;
+    std::vector<u32> index(n), order(n);
+    std::iota(order.begin(), order.end(), 0u);
+    auto id_of = [&](u32 i) { return std::make_pair(S.h_ids[2 * (u64)i + 1], S.h_ids[2 * (u64)i]); };
+    std::sort(order.begin(), order.end(), [&](u32 a, u32 b) { return id_of(a) != id_of(b) ? id_of(a) < id_of(b) : a < b; });
+    for (u32 j = 0; j < n; j++) index[order[j]] = j && id_of(order[j - 1]) == id_of(order[j]) ? index[order[j - 1]] : order[j];
+    u32 m = 0, written = 0;
+    for (u32 i = 0; i < n; i++) {
+        if (!S.h_found[i]) continue;
+        if (m++ >= cap) continue;
+        u64 bin[INTEGRAL_BIN_WORDS] = {};
+        for (u32 d = 0; d < c.world; d++) {
+            const u64* b = c.Es[d]->qs->qi.h_bins + (u64)index[i] * INTEGRAL_BIN_WORDS;
+            for (u32 w = 0; w < INTEGRAL_WEIGHTED; w += 2) {
+                const u128 v = tb_u128(bin[w], bin[w + 1]) + tb_u128(b[w], b[w + 1]);
+                bin[w] = tb_lo(v), bin[w + 1] = tb_hi(v);
+            }
+            for (u32 w = INTEGRAL_WEIGHTED; w < INTEGRAL_BIN_WORDS; w += 3) {
+                const U192 v = tb_add192({bin[w], bin[w + 1], bin[w + 2]}, {b[w], b[w + 1], b[w + 2]});
+                bin[w] = v.w0, bin[w + 1] = v.w1, bin[w + 2] = v.w2;
+            }
+        }
+        u64 row[INTEGRAL_ROW_BYTES / 8];
+        tb_integral_row((const u64*)(S.h_accounts + (u64)i * 128), bin, t_open, t_end, row);
+        memcpy(out + (u64)written++ * INTEGRAL_ROW_BYTES, row, sizeof row);
+    }
+    for (u32 d = 0; d < c.world; d++) {
+        if (c.Es[d]->qs->qi.h_bins[(u64)n * INTEGRAL_BIN_WORDS]) result->complete = 0;
+    }
+    result->count = written;
+    result->matched = m;
+}
+
+extern "C" int tbgpu_get_account_balance_integrals(tbgpu_t* E, uint64_t t_open, uint64_t t_close, const void* ids, uint32_t n, void* out,
+                                                   uint32_t out_cap_rows, tbgpu_query_result* result) {
+    static_assert(sizeof(tbgpu_account_balance_integral) == INTEGRAL_ROW_BYTES && INTEGRAL_IDS_MAX == TBGPU_INTEGRALS_MAX &&
+                      INTEGRAL_WEIGHTED + 4 * 3 == INTEGRAL_BIN_WORDS && INTEGRAL_IDS_MAX == STATEMENT_IDS_MAX &&
+                      INTEGRAL_ROW_BYTES == STATEMENT_ROW_BYTES && INTEGRAL_RES_WORDS == STATEMENT_RES_WORDS,
+                  "k_integral.h's constants are the header's, and the statements call's buffers fit");
+    static_assert((size_t)CHANGE_LDS_BINS_SLOTS_MAX * 4 + (size_t)INTEGRAL_LDS_BINS * (INTEGRAL_BIN_WORDS * 8 + 4) <= 65536,
+                  "set, bins and tags stay within 64 KB a workgroup");
+    API_ENTER(E, false);
+    if (n > TBGPU_INTEGRALS_MAX) return fail(TBGPU_STATUS_INVALID, "get_account_balance_integrals: %u ids (at most %u)", n, TBGPU_INTEGRALS_MAX);
+    if (n == 0) return TBGPU_STATUS_OK;
+    if (!ids || !out || !result) return fail(TBGPU_STATUS_INVALID, "get_account_balance_integrals: NULL ids, out or result");
+    QueryCall c;
+    result->count = 0;
+    result->matched = 0;
+    result->complete = query_engines(E, true, &c);
+    if (t_open == ~0ULL || t_close == ~0ULL) return TBGPU_STATUS_OK;
+    // Every engine is drained before any is asked: a gather reads the owners' tables and a scan its
+    // posts' pending transfers on their homes.
+    for (u32 d = 0; d < c.world; d++) {
+        HIPCK(hipSetDevice(c.Es[d]->device));
+        if (c.Es[d]->pending) {
+            const int st = engine_sync(c.Es[d]);
+            if (st) return query_end(result, st);
+        }
+    }
+    // An integral needs a finite end: "now" is commit_timestamp, read once.  No account and no record
+    // has timestamp 0, so an end at 0 (nothing was ever committed) has no rows.
+    const u64 t_end = t_close ? t_close : tbgpu_commit_timestamp(E);
+    if (t_end < t_open || t_end == 0) return TBGPU_STATUS_OK;
+    const bool one = c.world == 1;
+    NodeTablesArgs NT{};
+    NT.world = c.world;
+    for (u32 d = 0; d < c.world; d++) NT.T[d] = c.Es[d]->T;
+    memcpy(c.Es[0]->qs->qt.h_ids, ids, (u64)n * 16);
+    int st = query_side_by_side(c.Es, c.world, [&](u32 d) -> int {
+        if (d) memcpy(c.Es[d]->qs->qt.h_ids, c.Es[0]->qs->qt.h_ids, (u64)n * 16);
+        return integrals_enqueue(c.Es[d], NT, d, n, t_open, t_end, one, out_cap_rows);
+    });
+    if (st) return query_end(result, st);
+    if (!one) {
+        integrals_node_rows(c, n, t_open, t_end, out_cap_rows, (u8*)out, result);
+        return TBGPU_STATUS_OK;
+    }
+    tbgpu* S0 = c.Es[0];
+    const StatementBufs& S = S0->qs->qt;
+    const u64 matched = S.h_res[INTEGRAL_RES_MATCHED];
+    const u32 m = (u32)std::min<u64>(matched, out_cap_rows);
+    if (matched > n) return query_end(result, fail(TBGPU_STATUS_PANIC, "get_account_balance_integrals: %llu rows for %u ids", (unsigned long long)matched, n));
+    if (m) {
+        HIPCK(hipMemcpyAsync(out, S.d_out, (u64)m * INTEGRAL_ROW_BYTES, hipMemcpyDeviceToHost, S0->stream));
+        HIPCK(hipStreamSynchronize(S0->stream));
+    }
+    if (S.h_res[INTEGRAL_RES_ORPHAN]) result->complete = 0;
     result->count = m;
     result->matched = matched;
     return TBGPU_STATUS_OK;

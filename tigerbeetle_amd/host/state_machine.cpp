@@ -335,6 +335,13 @@ tbgpu_query_result StateMachine::get_account_statements(uint64_t t_open, uint64_
     return r;
 }
 
+tbgpu_query_result StateMachine::get_account_balance_integrals(uint64_t t_open, uint64_t t_close, const void* ids, uint32_t n, void* out,
+                                                               uint32_t out_cap_rows) {
+    tbgpu_query_result r{};
+    check(tbgpu_get_account_balance_integrals(engine_, t_open, t_close, ids, n, out, out_cap_rows, &r), "get_account_balance_integrals");
+    return r;
+}
+
 tbgpu_query_result StateMachine::query_transfers(const tbgpu_query_filter& filter, void* out, uint32_t out_cap_records) {
     tbgpu_query_result r{};
     check(tbgpu_query_transfers(engine_, &filter, out, out_cap_records, &r), "query_transfers");

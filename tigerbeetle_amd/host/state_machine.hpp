@@ -291,6 +291,16 @@ public:
     tbgpu_query_result get_account_statements(uint64_t t_open, uint64_t t_close, const void* ids, uint32_t n, void* out,
                                               uint32_t out_cap_rows);
 
+    // Time-weighted balances over the period (t_open, t_end] (tbgpu_get_account_balance_integrals; a
+    // read, and no reference operation behind it): one 256-byte tbgpu_account_balance_integral per id
+    // the table holds and that existed at t_end, in request order — the balances at the period's start
+    // and end and each balance summed over every nanosecond of the period, modulo 2^192, from one scan
+    // of the log.  ids: n x {lo, hi}, at most TBGPU_INTEGRALS_MAX.  t_open 0 is read literally; t_close
+    // 0: t_end is commit_timestamp.  result.complete == 0: transfers were evicted or a summed post had
+    // lost its pending transfer.
+    tbgpu_query_result get_account_balance_integrals(uint64_t t_open, uint64_t t_close, const void* ids, uint32_t n, void* out,
+                                                     uint32_t out_cap_rows);
+
     // The field-filter queries (tbgpu_query_transfers / tbgpu_query_accounts; reads, not commits): the
     // resident transfers, or the accounts, whose user_data_128 / user_data_64 / user_data_32 / ledger /
     // code equal the filter's non-zero fields, by timestamp (newest first under TBGPU_QUERY_REVERSED),

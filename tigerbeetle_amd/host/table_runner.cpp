@@ -315,8 +315,10 @@ std::string run_table(tb::StateMachine& sm, const std::string& text) {
 // answered by get_pending_transfers: the result, the rows (tbgpu_pending_row) and then a state byte a row.
 // --query-statements (tests/test_gpu_statements_cpp.py): the prepares ending in {0, 0, 16 + n * 16, t_open,
 // t_close and n ids}, answered by get_account_statements (the records are tbgpu_account_statement rows).
+// --query-integrals (tests/test_gpu_integrals_cpp.py): the same request, answered by
+// get_account_balance_integrals (the records are tbgpu_account_balance_integral rows).
 enum QueryKind { ACCOUNT_TRANSFERS, ACCOUNT_BALANCES, QUERY_TRANSFERS, QUERY_ACCOUNTS, CHANGE_EVENTS, ACCOUNT_TRANSFERS_MANY, ACCOUNTS_AT,
-                 LEDGER_BALANCES, PENDING_TRANSFERS, ACCOUNT_STATEMENTS };
+                 LEDGER_BALANCES, PENDING_TRANSFERS, ACCOUNT_STATEMENTS, ACCOUNT_INTEGRALS };
 
 int run_query(tb::StateMachine& sm, QueryKind kind, const char* in_path, const char* out_path) {
     std::ifstream in(in_path, std::ios::binary);
@@ -411,6 +413,22 @@ int run_query(tb::StateMachine& sm, QueryKind kind, const char* in_path, const c
         printf("query: %u of %llu rows, complete %u\n", r.count, (unsigned long long)r.matched, r.complete);
         return o ? 0 : 2;
     }
+    if (kind == ACCOUNT_INTEGRALS) {
+        const size_t n = body.size() >= 16 ? body.size() / 16 - 1 : 0;
+        if (body.size() % 16 != 0 || body.size() < 16 || n > TBGPU_INTEGRALS_MAX) {
+            fprintf(stderr, "%s: t_open, t_close and at most %u ids of 16 bytes\n", in_path, TBGPU_INTEGRALS_MAX);
+            return 2;
+        }
+        uint64_t period[2] = {0, 0};
+        memcpy(period, body.data(), 16);
+        std::vector<uint8_t> out((size_t)TBGPU_INTEGRALS_MAX * sizeof(tbgpu_account_balance_integral));
+        const tbgpu_query_result r =
+            sm.get_account_balance_integrals(period[0], period[1], body.data() + 16, (uint32_t)n, out.data(), TBGPU_INTEGRALS_MAX);
+        std::ofstream o(out_path, std::ios::binary);
+        o.write((const char*)&r, sizeof(r)).write((const char*)out.data(), (size_t)r.count * sizeof(tbgpu_account_balance_integral));
+        printf("query: %u of %llu rows, complete %u\n", r.count, (unsigned long long)r.matched, r.complete);
+        return o ? 0 : 2;
+    }
     if (kind == PENDING_TRANSFERS) {
         tbgpu_pending_filter pf;
         if (body.size() != sizeof(pf)) {
@@ -457,8 +475,9 @@ int main(int argc, char** argv) {
     const bool ledgers = argc > 1 && std::string(argv[1]) == "--query-ledgers";
     const bool pending = argc > 1 && std::string(argv[1]) == "--query-pending";
     const bool statements = argc > 1 && std::string(argv[1]) == "--query-statements";
-    const bool query = fields || balances || changes || many || at || ledgers || pending || statements || (argc > 1 && std::string(argv[1]) == "--query");
-    QueryKind kind = balances ? ACCOUNT_BALANCES : changes ? CHANGE_EVENTS : many ? ACCOUNT_TRANSFERS_MANY : at ? ACCOUNTS_AT : ledgers ? LEDGER_BALANCES : pending ? PENDING_TRANSFERS : statements ? ACCOUNT_STATEMENTS : ACCOUNT_TRANSFERS;
+    const bool integrals = argc > 1 && std::string(argv[1]) == "--query-integrals";
+    const bool query = fields || balances || changes || many || at || ledgers || pending || statements || integrals || (argc > 1 && std::string(argv[1]) == "--query");
+    QueryKind kind = balances ? ACCOUNT_BALANCES : changes ? CHANGE_EVENTS : many ? ACCOUNT_TRANSFERS_MANY : at ? ACCOUNTS_AT : ledgers ? LEDGER_BALANCES : pending ? PENDING_TRANSFERS : statements ? ACCOUNT_STATEMENTS : integrals ? ACCOUNT_INTEGRALS : ACCOUNT_TRANSFERS;
     const char* self = argv[0];
     if (fields && argc > 2) {
         const std::string which = argv[2];
@@ -476,8 +495,9 @@ int main(int argc, char** argv) {
                 "       %s --query-ledgers <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-pending <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-statements <prepares.bin> <answer.bin> [device]\n"
+                "       %s --query-integrals <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-fields <transfers|accounts> <prepares.bin> <answer.bin> [device]\n",
-                self, self, self, self, self, self, self, self, self, self);
+                self, self, self, self, self, self, self, self, self, self, self);
         return 2;
     }
     if (query) {

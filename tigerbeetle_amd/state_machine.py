@@ -23,7 +23,18 @@ import numpy as np
 
 from . import _lib
 from .types import (ACCOUNT_BALANCE_DTYPE, ACCOUNT_DTYPE, ACCOUNT_FILTER_DTYPE, BATCH_MAX, CHANGE_EVENT_DTYPE, CHANGE_EVENTS_FILTER_DTYPE,
-                    CHANGE_EVENTS_MAX, LEDGER_BALANCE_DTYPE, LEDGERS_MAX, PENDING_FILTER_DTYPE, PENDING_ROW_DTYPE, PENDING_ROWS_MAX, PENDING_STATES, STATEMENT_DTYPE, FILTER_CREDITS, FILTER_DEBITS, FILTER_REVERSED, pack_change_events_filter, QUERY_FILTER_DTYPE, QUERY_REVERSED, TRANSFER_DTYPE, U64_MAX, Operation)
+                    CHANGE_EVENTS_MAX, LEDGER_BALANCE_DTYPE, LEDGERS_MAX, PENDING_FILTER_DTYPE, PENDING_ROW_DTYPE, PENDING_ROWS_MAX, PENDING_STATES, STATEMENT_DTYPE, INTEGRAL_DTYPE, FILTER_CREDITS, FILTER_DEBITS, FILTER_REVERSED, pack_change_events_filter, QUERY_FILTER_DTYPE, QUERY_REVERSED, TRANSFER_DTYPE, U64_MAX, Operation)
+
+
+def average_balances(row):
+    """The four time-weighted average balances of one get_account_balance_integrals row — (debits_pending,
+    debits_posted, credits_pending, credits_posted), each `integral // L` with L = t_end - t_open, as
+    Python ints; None for an empty period (L == 0)."""
+    length = int(row["t_end"]) - int(row["t_open"])
+    if length == 0:
+        return None
+    return tuple(sum(int(row["integral_%s_w%d" % (c, k)]) << (64 * k) for k in range(3)) // length
+                 for c in ("debits_pending", "debits_posted", "credits_pending", "credits_posted"))
 
 
 @dataclass
@@ -493,6 +504,44 @@ class Engine:
                                                          ctypes.byref(res)))
         return out[:res.count], int(res.matched), bool(res.complete)
 
+    INTEGRALS_MAX = 4095  # TBGPU_INTEGRALS_MAX
+
+    def get_account_balance_integrals(self, ids, t_open, t_close, out_cap_rows=None):
+        """The time-weighted balances of the accounts `ids` over the period (t_open, t_end]
+        (tbgpu_get_account_balance_integrals): the balances at its start and at its end and, per
+        column, the sum of the balance over every nanosecond of the period, modulo 2^192 (three words,
+        low word first) — one row per id the table holds and that existed at t_end, in request order,
+        a repeated id once per occurrence.  t_open 0 is read literally; t_close 0: t_end is
+        commit_timestamp.  Returns (rows ndarray of INTEGRAL_DTYPE, matched, complete); `complete` is
+        False once the engine has evicted transfers or a post in a sum had lost its pending transfer.
+        An invalid period (an end at 2^64-1, t_end below t_open) matches nothing.
+        average_balances(row) divides by the period's length."""
+        ids = [int(i) for i in ids]
+        if len(ids) > self.INTEGRALS_MAX:
+            raise ValueError("at most %d ids in one call" % self.INTEGRALS_MAX)
+        body = b"".join(i.to_bytes(16, "little") for i in ids)
+        return self.get_account_balance_integrals_raw(body, t_open, t_close, out_cap_rows)
+
+    def get_account_balance_integrals_raw(self, id_bytes, t_open, t_close, out_cap_rows=None):
+        """get_account_balance_integrals from the ids' bytes, 16 each ({lo, hi}, little-endian)."""
+        id_bytes = bytes(id_bytes)
+        if len(id_bytes) % 16 != 0:
+            raise ValueError("an id is 16 bytes")
+        n = len(id_bytes) // 16
+        if n > self.INTEGRALS_MAX:
+            raise ValueError("at most %d ids in one call" % self.INTEGRALS_MAX)
+        if n == 0:  # the library returns at once and leaves its result alone
+            return np.zeros(0, dtype=INTEGRAL_DTYPE), 0, True
+        cap = n if out_cap_rows is None else int(out_cap_rows)
+        if cap < 0 or cap >> 32:
+            raise ValueError("out_cap_rows is 32 bits")
+        out = np.zeros(max(cap, 1), dtype=INTEGRAL_DTYPE)
+        res = _lib.tbgpu_query_result()
+        src = ctypes.create_string_buffer(id_bytes, len(id_bytes))
+        _lib.check(self.lib.tbgpu_get_account_balance_integrals(self.h, int(t_open), int(t_close), src, n, out.ctypes.data, cap,
+                                                                ctypes.byref(res)))
+        return out[:res.count], int(res.matched), bool(res.complete)
+
     @staticmethod
     def query_filter(user_data_128=0, user_data_64=0, user_data_32=0, ledger=0, code=0, *, reversed=False,
                      timestamp_min=0, timestamp_max=0, limit=8190):
@@ -884,6 +933,10 @@ class StateMachine:
     def get_account_statements(self, ids, t_open, t_close, out_cap_rows=None):
         """Statement headers over a period (Engine.get_account_statements): a read, not a commit."""
         return self.engine.get_account_statements(ids, t_open, t_close, out_cap_rows)
+
+    def get_account_balance_integrals(self, ids, t_open, t_close, out_cap_rows=None):
+        """Time-weighted balances over a period (Engine.get_account_balance_integrals): a read, not a commit."""
+        return self.engine.get_account_balance_integrals(ids, t_open, t_close, out_cap_rows)
 
     def query_transfers(self, **filter):
         """The field-filter query over transfers (Engine.query_transfers): a read, not a commit."""

@@ -144,6 +144,17 @@ STATEMENT_DTYPE = np.dtype(
 assert STATEMENT_DTYPE.itemsize == 256
 STATEMENTS_MAX = 4095
 
+# tbgpu_account_balance_integral (include/tbgpu.h tbgpu_get_account_balance_integrals): 256 bytes, no
+# padding; the balances at the period's start and end as STATEMENT_DTYPE has them, each column's time
+# integral over the period in three words (low word first, modulo 2^192) and the period as used.
+INTEGRAL_DTYPE = np.dtype(
+    _u128("id")
+    + [f for when in ("opening", "closing") for c in _BALANCE_COLUMNS for f in _u128(when + "_" + c)]
+    + [("integral_" + c + w, "<u8") for c in _BALANCE_COLUMNS for w in ("_w0", "_w1", "_w2")]
+    + [("t_open", "<u8"), ("t_end", "<u8")])
+assert INTEGRAL_DTYPE.itemsize == 256
+INTEGRALS_MAX = 4095
+
 # tbgpu_query_filter (include/tbgpu.h tbgpu_query_transfers / tbgpu_query_accounts): 64 bytes, no padding.
 QUERY_FILTER_DTYPE = np.dtype(
     _u128("user_data_128") + [("user_data_64", "<u8"), ("user_data_32", "<u4"), ("ledger", "<u4"), ("code", "<u2"),

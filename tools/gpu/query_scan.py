@@ -1,7 +1,7 @@
 """The account-filter scan (tbgpu_get_account_transfers, csrc/k_query.h) over a 16M-transfer log (2 GB)
 against a device-to-device copy of the same log range, in one process.
 
-usage: python tools/gpu/query_scan.py [transfers] [runs] [--only account|fields|balances|change_events|many|asof|ledgers|pending|statements]
+usage: python tools/gpu/query_scan.py [transfers] [runs] [--only account|fields|balances|change_events|many|asof|ledgers|pending|statements|integrals]
 
 The log is built by the device generator, committed in place (the way tools/gpu/device_pass.py builds
 a pass): once with uniform C2 ids, where the queried account is a cold one (a few dozen matches), and
@@ -63,6 +63,13 @@ first) with the period covering the whole log, its middle half, and t_open above
 reads timestamps only).  The yardstick runs in the same process: two tbgpu_lookup_accounts_at calls with
 the same ids at T = t_open and T = t_close, timed together; the aim is below their sum.  An older library
 loaded through TBGPU_AB_LIB lacks the call: the yardstick alone is timed then.
+
+`--only integrals` (tbgpu_get_account_balance_integrals) times the C call alone, into buffers
+made once, on both logs, with --only statements' ids and periods: the whole log, its middle half, and t_open
+at the last record (the scan reads timestamps only).  The yardstick runs in the same process: one
+tbgpu_get_account_statements call with the same ids and period.  An older library loaded through
+TBGPU_AB_LIB lacks the call: its get_account_statements alone is timed then, the yardstick to hold this
+build's call against.
 """
 import json
 import os
@@ -495,6 +502,72 @@ def measure_statements():
     return out
 
 
+def measure_integrals():
+    """get_account_balance_integrals beside get_account_statements with the same ids, on both logs, in one process."""
+    import ctypes
+
+    from tigerbeetle_amd import _lib
+    os.environ["TBGPU_QUERY_COOP"] = "0"
+    e = Engine(Options(accounts_max=n_acct, transfers_max=n_xfer, pass_events_max=pb * batch, pass_batches_max=pb))
+    a_lens = batches(n_acct, batch)
+    a_ts, t = timestamps(a_lens, 1_000_000_000)
+    acct = e.alloc(n_acct * 128)
+    e.generate_accounts(acct, 0, n_acct, seed=42)
+    res = e.alloc(max(n_acct, n_xfer) * 8)
+    rb = e.alloc((n_xfer // batch + 2) * 4)
+    e.commit_device_async(128, a_ts, a_lens, acct, res, rb)
+    e.sync()
+    n_ids = 4095
+    have = hasattr(e.lib, "tbgpu_get_account_balance_integrals")  # an older library (TBGPU_AB_LIB): the yardstick alone
+    h_out = np.zeros(n_ids * 256, dtype=np.uint8)
+    h_res = _lib.tbgpu_query_result()
+
+    def raw(fn, ids, t_open, t_close):
+        body = b"".join(i.to_bytes(16, "little") for i in ids)
+        src = ctypes.create_string_buffer(body, len(body))
+        return lambda: _lib.check(fn(e.h, t_open, t_close, src, len(ids), h_out.ctypes.data, len(ids), ctypes.byref(h_res)))
+
+    out = {}
+    for name, kind in (("uniform", "c2"), ("zipf", "c3")):
+        if name != "uniform":
+            e.reset_transfers()
+        log = e.log_window(n_xfer)
+        e.generate_transfers(log, 0, n_xfer, n_acct, seed=42, kind=KINDS[kind])
+        e.sync()
+        x_lens = batches(n_xfer, batch)
+        x_ts, t = timestamps(x_lens, t + 10)
+        e.commit_device_async(129, x_ts, x_lens, log, res, rb)
+        e.sync()
+        oldest, _, _ = e.query_transfers(limit=1)
+        newest, _, _ = e.query_transfers(reversed=True, limit=1)
+        t_first, t_last = int(oldest["timestamp"][0]), int(newest["timestamp"][0])
+        quarter = (t_last - t_first) // 4
+        sample = e.to_host(log + (n_xfer // 2) * 128, min(n_xfer // 2, 1 << 16) * 128).view(TRANSFER_DTYPE)
+        accounts, counts = np.unique(sample[["debit_account_id_lo", "debit_account_id_hi"]], return_counts=True)
+        hottest = np.argsort(-counts, kind="stable")[:n_ids]  # the Zipf log's hottest accounts; any of the uniform log's
+        ids = [int(lo) | (int(hi) << 64) for lo, hi in accounts[hottest].tolist()]
+        assert len(ids) == n_ids
+        legs = (("whole_log", t_first - 1, t_last), ("middle_half", t_first + quarter, t_last - quarter),
+                ("t_open_above_every_record", t_last, t_last + 1))
+        if have:
+            rows, matched, complete = e.get_account_balance_integrals(ids, t_first + quarter, t_last - quarter)
+            held = e.get_account_statements(ids, t_first + quarter, t_last - quarter)[0]
+            assert complete and matched == n_ids and int(rows["integral_debits_posted_w0"].astype(bool).sum()) > n_ids // 2
+            for c in ("debits_pending", "debits_posted", "credits_pending", "credits_posted"):
+                for when in ("opening_", "closing_"):
+                    for w in ("_lo", "_hi"):
+                        assert np.array_equal(rows[when + c + w], held[when + c + w])
+        for leg, t_open, t_close in legs:
+            st_med, st_lo, st_hi = timed(e, raw(e.lib.tbgpu_get_account_statements, ids, t_open, t_close))
+            entry = dict(ids=n_ids, statements_ms=round(st_med, 4), statements_min_ms=round(st_lo, 4), statements_max_ms=round(st_hi, 4))
+            if have:
+                med, lo_ms, hi_ms = timed(e, raw(e.lib.tbgpu_get_account_balance_integrals, ids, t_open, t_close))
+                entry = row(med, lo_ms, hi_ms, over_statements=round(med / st_med, 2), **entry)
+            out["%s_integrals_%s" % (name, leg)] = entry
+    e.close()
+    return out
+
+
 def measure_ledgers():
     """get_ledger_balances beside query_accounts, query_transfers and the copies, in one process."""
     import ctypes
@@ -679,6 +752,8 @@ elif only == "pending":
     result["pending"] = measure_pending()
 elif only == "statements":
     result["statements"] = measure_statements()
+elif only == "integrals":
+    result["integrals"] = measure_integrals()
 elif only == "many":
     result["many"] = measure_many()
 elif only == "balances":
@@ -690,6 +765,6 @@ elif only != "fields":
     for shape in ("lane_per_record", "cooperative"):
         r = result[shape]
         r["bar_query_le_copy"] = all(v["ms"] <= r["copy_d2d"]["ms"] for k, v in r.items() if k != "copy_d2d")
-if only not in ("account", "balances", "change_events", "many", "asof", "ledgers", "pending", "statements"):
+if only not in ("account", "balances", "change_events", "many", "asof", "ledgers", "pending", "statements", "integrals"):
     result["field_filters"] = measure_fields()
 print(json.dumps(result))

@@ -791,6 +791,41 @@ pub fn StateMachineType(
             return @as(usize, result.count) * @sizeOf(tbgpu.tbgpu_account_statement);
         }
 
+        /// Time-weighted balances for the accounts `ids` over the period (t_open, t_end]
+        /// (tbgpu_get_account_balance_integrals; t_close 0: t_end is commit_timestamp): a read, with no
+        /// operation in this reference's enum, so nothing in commit() dispatches to it
+        /// (INTEGRATION.md, "Time-weighted balances over a period"). One 256-byte
+        /// tbgpu_account_balance_integral per id the engine holds and that existed at t_end, in
+        /// request order, into `output`; returns the bytes written. `complete` is false once
+        /// transfers were evicted or a summed post had lost its pending transfer: the caller then
+        /// merges with the forest.
+        pub fn get_account_balance_integrals(
+            self: *StateMachine,
+            t_open: u64,
+            t_close: u64,
+            ids: []const u128,
+            output: []align(16) u8,
+            complete: *bool,
+        ) usize {
+            assert(ids.len <= tbgpu.TBGPU_INTEGRALS_MAX);
+            var result: tbgpu.tbgpu_query_result = undefined;
+            result.count = 0;
+            result.complete = 1;
+            result.matched = 0;
+            check(tbgpu.tbgpu_get_account_balance_integrals(
+                self.engine,
+                t_open,
+                t_close,
+                ids.ptr,
+                @intCast(ids.len),
+                output.ptr,
+                @intCast(output.len / @sizeOf(tbgpu.tbgpu_account_balance_integral)),
+                &result,
+            ));
+            complete.* = result.complete != 0;
+            return @as(usize, result.count) * @sizeOf(tbgpu.tbgpu_account_balance_integral);
+        }
+
         pub fn compact(self: *StateMachine, callback: *const fn (*StateMachine) void, op: u64) void {
             assert(self.compact_callback == null);
             assert(self.checkpoint_callback == null);
