@@ -27,6 +27,7 @@
  *   (no reference: pending transfers with their state)     tbgpu_get_pending_transfers (likewise)
  *   (no reference: account statements over a period)       tbgpu_get_account_statements (likewise)
  *   (no reference: time-weighted balances over a period)   tbgpu_get_account_balance_integrals (likewise)
+ *   (no reference: statements per bucket of a period)      tbgpu_get_account_statement_series (likewise)
  *   `setup` action of the table tests (:1398-1407)         tbgpu_test_set_balances (test only)
  *   StateMachine.commit_timestamp field (:251)             tbgpu_commit_timestamp
  *
@@ -821,6 +822,59 @@ typedef struct tbgpu_account_balance_integral {   /* 256 bytes, little-endian, n
 int tbgpu_get_account_balance_integrals(tbgpu_t* engine, uint64_t t_open, uint64_t t_close,
                                         const void* ids /* n x {lo, hi} */, uint32_t n,
                                         void* out, uint32_t out_cap_rows, tbgpu_query_result* result);
+
+/* get_account_statement_series: tbgpu_get_account_statements cut into consecutive periods — for each
+ * account the caller names, one statement row per bucket: daily closing balances for a month, monthly
+ * turnover for a year, the day-by-day ledger an interest run walks.  One scan of the log in HBM
+ * answers every bucket of every account, where the single call would scan once per bucket.  Each row
+ * is the row the single call would have written.  An entry point of its own, as above; this comment
+ * is its specification.
+ *   Buckets: bounds holds n_buckets + 1 timestamps, and bucket k is the period
+ *     (bounds[k], bounds[k+1]], so buckets tile exactly as consecutive statements do.  bounds[0] == 0
+ *     is read literally (from before every record); bounds[n_buckets] == 0 leaves the last bucket
+ *     open-ended, as t_close == 0 does; bounds[1 .. n_buckets-1] must be non-zero.  Bounds are
+ *     non-decreasing; equal neighbours make an empty bucket, which is legal, as t_open == t_close is
+ *     for the single call.  A record with timestamp ts belongs to the smallest k with
+ *     ts <= bounds[k+1]; a record at or below bounds[0] belongs to none; a record above a non-zero
+ *     last bound belongs to the tail, the effects "above t_close".
+ *   Which accounts: tbgpu_lookup_accounts_at's rules with T = the last bound, or no limit when the
+ *     last bound is 0 — an account counts when its owner's table holds it and its own timestamp is
+ *     not above T.  Answers are in request order; absent ids and the reserved ids are skipped; a
+ *     repeated id is answered once per occurrence.
+ *   Rows: tbgpu_account_statement, unchanged.  Each such account yields exactly n_buckets rows,
+ *     contiguous, bucket ascending: found account r's bucket k is row r * n_buckets + k.  `matched` is
+ *     found accounts x n_buckets; count = min(matched, out_cap_rows): the cap cuts in that row order
+ *     and may cut inside an account.  Bytes past count rows are not written.
+ *   What a row holds: row (a, k) is byte for byte the row
+ *     tbgpu_get_account_statements(bounds[k], bounds[k+1], {a}) writes, wherever that call yields a
+ *     row.  Where the single call would skip `a` because its creation timestamp is above bounds[k+1]
+ *     (it is still at or below the last bound), the row is present and holds the same formula's
+ *     values: zeros on an engine that never had balances set or loaded — it follows the definition,
+ *     not the ledger's past.  By construction the closing of bucket k is the opening of bucket k+1,
+ *     the last bucket's closing is tbgpu_lookup_accounts_at at the last bound, and the sums and
+ *     counts over all buckets equal the single call's over (bounds[0], bounds[n_buckets]].
+ *   complete: tbgpu_lookup_accounts_at's rule over everything above bounds[0] — one value for the
+ *     whole answer.  It may be 0 where a single narrow call would say 1: an orphan post in another
+ *     bucket, or in the tail, drops it for every row.
+ *   Any bound equal to 2^64-1, a zero among bounds[1 .. n_buckets-1], or a bound below its
+ *     predecessor (except an open last bound of 0) returns TBGPU_STATUS_OK with count = matched = 0
+ *     and writes nothing.  n == 0 returns TBGPU_STATUS_OK and writes nothing.  n_buckets == 0,
+ *     n * n_buckets > TBGPU_SERIES_ROWS_MAX, NULL bounds, or a NULL ids, out or result with n > 0, is
+ *     TBGPU_STATUS_INVALID and writes nothing.  After any failing status the result names no row.
+ *   With n_buckets == 1 the answer is byte-identical to
+ *     tbgpu_get_account_statements(bounds[0], bounds[1], ids, ...), `matched` and `complete` included.
+ *   The call contract of tbgpu_get_account_statements: synchronous, drains a pending
+ *     tbgpu_commit_device_async first, a read that changes nothing, works on an engine a device panic
+ *     stopped, allocates nothing after tbgpu_init, legal beside an asynchronous write-back.
+ *   A node engine has the same contract: every home shard scans its own log on its own device and
+ *     stream, side by side, reading a post's pending transfer on the home shard of its pending_id;
+ *     each account's record, and whether it existed at the last bound, come from its owner shard
+ *     only; the host adds the shards' sums and builds the rows by the device's row function. */
+#define TBGPU_SERIES_ROWS_MAX 4095u   /* 256 B rows in one message body */
+int tbgpu_get_account_statement_series(tbgpu_t* engine,
+        const uint64_t* bounds /* n_buckets + 1 */, uint32_t n_buckets,
+        const void* ids /* n x {lo, hi} */, uint32_t n,
+        void* out, uint32_t out_cap_rows, tbgpu_query_result* result);
 
 /* The replica writes StateMachine.commit_timestamp itself: the header timestamp after every commit
  * (src/vsr/replica.zig:3664-3665) and the checkpoint's value on open / state sync.  The wrapper

@@ -120,6 +120,7 @@ class tbgpu_account_balance_integral(ctypes.Structure):
 
 
 INTEGRALS_MAX = 4095  # TBGPU_INTEGRALS_MAX
+SERIES_ROWS_MAX = 4095  # TBGPU_SERIES_ROWS_MAX
 
 
 class tbgpu_stats(ctypes.Structure):
@@ -250,6 +251,7 @@ SIGNATURES = [
     ("tbgpu_get_pending_transfers", ctypes.c_int, [_P, _P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_get_account_statements", ctypes.c_int, [_P, _U64, _U64, _P, _U32, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_get_account_balance_integrals", ctypes.c_int, [_P, _U64, _U64, _P, _U32, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
+    ("tbgpu_get_account_statement_series", ctypes.c_int, [_P, _P, _U32, _P, _U32, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_query_transfers", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_query_accounts", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_bench_query_keys_max", ctypes.c_int, [_P, _U32]),

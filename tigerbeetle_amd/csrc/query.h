@@ -1,7 +1,7 @@
 // query.h — the host side of the queries (include/tbgpu.h): get_account_transfers and its batched form
 // get_account_transfers_many, get_account_balances, query_transfers, query_accounts,
 // get_change_events, lookup_accounts_at, get_ledger_balances, get_pending_transfers,
-// get_account_statements and get_account_balance_integrals; their buffers, made at tbgpu_init, and their entry points.  Included by engine.hip after the engine's own helpers and before node.h.
+// get_account_statements, get_account_balance_integrals and get_account_statement_series; their buffers, made at tbgpu_init, and their entry points.  Included by engine.hip after the engine's own helpers and before node.h.
 //
 // Every query is written once, over a list of engines (QueryCall): the one engine, or a node's shards.
 // A transfer lives on its home shard only and an account is answered by its owner only, so every
@@ -185,6 +185,17 @@ struct IntegralBufs {
 };
 #define INTEGRAL_BIN_BYTES(n) (((u64)(n) * INTEGRAL_BIN_WORDS + 1) * 8)
 
+// tbgpu_get_account_statement_series (k_series.h): a statements call's request, set, records, flags,
+// rows and result words (StatementBufs: n * n_buckets rows are at most STATEMENT_IDS_MAX), its own
+// bounds and its own bins, one per key.
+struct SeriesBufs {
+    u64* d_bounds = nullptr;  // [SERIES_ROWS_MAX + 1] the request's bounds
+    u64* h_bounds = nullptr;  // pinned: the caller's bounds on their way up
+    u64* d_bins = nullptr;    // [SERIES_KEYS_MAX][SERIES_BIN_WORDS] the bins by key, then the flag word
+    u64* h_bins = nullptr;    // pinned mirror, read by a node's host only: it adds the shards' bins
+};
+#define SERIES_BIN_BYTES(keys) (((u64)(keys) * SERIES_BIN_WORDS + 1) * 8)
+
 // One engine's query buffers (tbgpu::qs), in the order query_init makes them.
 struct QueryState {
     QueryBufs q;
@@ -197,6 +208,7 @@ struct QueryState {
     PendingBufs qp;
     StatementBufs qt;
     IntegralBufs qi;
+    SeriesBufs qr;
 };
 
 // Called by engine_init on the engine's device, after every other buffer.  The buffers go into the
@@ -334,6 +346,13 @@ static int query_init(tbgpu* E) {
         IntegralBufs& I = E->qs->qi;
         HIPCK(tbMalloc(E->own, &I.d_bins, INTEGRAL_BIN_BYTES(INTEGRAL_IDS_MAX)));
         HIPCK(tbHostMalloc(E->own, &I.h_bins, INTEGRAL_BIN_BYTES(INTEGRAL_IDS_MAX), hipHostMallocDefault));
+    }
+    {  // tbgpu_get_account_statement_series: its bounds and its bins; the rest is the statements call's
+        SeriesBufs& R = E->qs->qr;
+        HIPCK(tbMalloc(E->own, &R.d_bounds, (u64)(SERIES_ROWS_MAX + 1) * 8));
+        HIPCK(tbHostMalloc(E->own, &R.h_bounds, (u64)(SERIES_ROWS_MAX + 1) * 8, hipHostMallocDefault));
+        HIPCK(tbMalloc(E->own, &R.d_bins, SERIES_BIN_BYTES(SERIES_KEYS_MAX)));
+        HIPCK(tbHostMalloc(E->own, &R.h_bins, SERIES_BIN_BYTES(SERIES_KEYS_MAX), hipHostMallocDefault));
     }
     return TBGPU_STATUS_OK;
 }
@@ -1630,6 +1649,188 @@ extern "C" int tbgpu_get_account_balance_integrals(tbgpu_t* E, uint64_t t_open, 
         HIPCK(hipStreamSynchronize(S0->stream));
     }
     if (S.h_res[INTEGRAL_RES_ORPHAN]) result->complete = 0;
+    result->count = m;
+    result->matched = matched;
+    return TBGPU_STATUS_OK;
+}
+
+// ---- get_account_statement_series (k_series.h, include/tbgpu.h) -----------------------------------
+// get_account_statements' shape with T = the last bound, B + 1 buckets for its two zones and bins by
+// key.  One engine: ids and bounds up, set and bins zeroed, tb_asof_gather -> tb_series_effects ->
+// tb_series_emit on the engine stream, the result words back; one wait; then the answer's count * 256
+// bytes.  The request, the set, the records, the flags, the rows and the result words are the
+// statements call's buffers (StatementBufs); the bounds and the bins are SeriesBufs'.  A node: every
+// shard gathers and scans its own log on its own device and stream, side by side; the host adds the
+// shards' bins and writes the rows, an account's buckets from the last to the first (tb_series_row).
+static int series_enqueue(tbgpu* E, const NodeTablesArgs& NT, u32 self, u32 n, u32 n_buckets, bool emit, u32 cap) {
+    StatementBufs& S = E->qs->qt;
+    SeriesBufs& R = E->qs->qr;
+    HIPCK(hipSetDevice(E->device));
+    const u32 slots = tb_change_set_slots(n), mask = slots - 1;
+    const u64 keys = (u64)n * (n_buckets + 1), bin_bytes = SERIES_BIN_BYTES(keys);
+    const unsigned nb_ids = (n + QUERY_THREADS - 1) / QUERY_THREADS;
+    const u64 t_last = R.h_bounds[n_buckets];
+    HIPCK(hipMemcpyAsync(S.d_ids, S.h_ids, (u64)n * 16, hipMemcpyHostToDevice, E->stream));
+    HIPCK(hipMemcpyAsync(R.d_bounds, R.h_bounds, ((u64)n_buckets + 1) * 8, hipMemcpyHostToDevice, E->stream));
+    HIPCK(hipMemsetAsync(S.d_set, 0, (u64)slots * 4, E->stream));
+    HIPCK(hipMemsetAsync(R.d_bins, 0, bin_bytes, E->stream));
+    const bool store = emit || self == 0;  // a node reads the first shard's records only
+    hipLaunchKernelGGL(tb_asof_gather, dim3(nb_ids), dim3(QUERY_THREADS), 0, E->stream, NT, (const u64*)S.d_ids, n, t_last,
+                       store ? S.d_accounts : nullptr, store ? S.d_found : nullptr, S.d_set, mask);
+    HIPCK(hipGetLastError());
+    const u64 records = E->log_next, per = (u64)CHANGE_THREADS * CHANGE_TILES, nb = (records + per - 1) / per;
+    if (nb) {
+        const size_t lds = tb_series_lds_bytes(slots, n_buckets);
+        if (lds > 65536) return fail(TBGPU_STATUS_PANIC, "get_account_statement_series: %zu bytes of LDS", lds);
+        hipLaunchKernelGGL(tb_series_effects, dim3((unsigned)nb), dim3(CHANGE_THREADS), lds, E->stream, NT, self, records,
+                           (const u64*)R.d_bounds, n_buckets, (const u32*)S.d_set, mask, (const u64*)S.d_ids, n, R.d_bins);
+        HIPCK(hipGetLastError());
+    }
+    if (emit) {
+        const unsigned nb_rows = (n * n_buckets + QUERY_THREADS - 1) / QUERY_THREADS;
+        hipLaunchKernelGGL(tb_series_emit, dim3(nb_rows), dim3(QUERY_THREADS), 0, E->stream, (const u64*)S.d_ids, n, n_buckets,
+                           (const u8*)S.d_accounts, (const u32*)S.d_found, (const u32*)S.d_set, mask, (const u64*)R.d_bins, cap,
+                           S.d_out, S.d_res);
+        HIPCK(hipGetLastError());
+        HIPCK(hipMemcpyAsync(S.h_res, S.d_res, SERIES_RES_WORDS * 8, hipMemcpyDeviceToHost, E->stream));
+        return TBGPU_STATUS_OK;
+    }
+    HIPCK(hipMemcpyAsync(R.h_bins, R.d_bins, bin_bytes, hipMemcpyDeviceToHost, E->stream));
+    if (self == 0) {
+        HIPCK(hipMemcpyAsync(S.h_accounts, S.d_accounts, (u64)n * 128, hipMemcpyDeviceToHost, E->stream));
+        HIPCK(hipMemcpyAsync(S.h_found, S.d_found, (u64)n * 4, hipMemcpyDeviceToHost, E->stream));
+    }
+    return TBGPU_STATUS_OK;
+}
+
+// A node's answer from its shards' pinned mirrors, as statements_node_rows builds it: the found
+// positions in request order, each with its n_buckets rows from its record and the sums of every
+// shard's bins of its id's keys.  The closing balances run from the tail down: a bucket's opening is
+// the closing of the one before it.
+static void series_node_rows(const QueryCall& c, u32 n, u32 n_buckets, u32 cap, u8* out, tbgpu_query_result* result) {
+    const StatementBufs& S = c.Es[0]->qs->qt;
+    const u32 stride = n_buckets + 1;
+    std::vector<u32> index(n), order(n);
+    std::iota(order.begin(), order.end(), 0u);
+    auto id_of = [&](u32 i) { return std::make_pair(S.h_ids[2 * (u64)i + 1], S.h_ids[2 * (u64)i]); };
+    std::sort(order.begin(), order.end(), [&](u32 a, u32 b) { return id_of(a) != id_of(b) ? id_of(a) < id_of(b) : a < b; });
+    for (u32 j = 0; j < n; j++) index[order[j]] = j && id_of(order[j - 1]) == id_of(order[j]) ? index[order[j - 1]] : order[j];
+    std::vector<u64> bins((u64)stride * SERIES_BIN_WORDS);
+    u64 m = 0;
+    u32 written = 0;
+    for (u32 i = 0; i < n; i++) {
+        if (!S.h_found[i]) continue;
+        const u64 first = m;  // the account's first row
+        m += n_buckets;
+        if (first >= cap) continue;
+        std::fill(bins.begin(), bins.end(), 0);
+        for (u32 d = 0; d < c.world; d++) {
+            const u64* b = c.Es[d]->qs->qr.h_bins + (u64)index[i] * stride * SERIES_BIN_WORDS;
+            for (u32 k = 0; k < stride; k++) {
+                u64* sum = bins.data() + (u64)k * SERIES_BIN_WORDS;
+                const u64* src = b + (u64)k * SERIES_BIN_WORDS;
+                for (u32 w = 0; w < SERIES_BIN_WORDS;) {
+                    if (w % SERIES_SIDE_WORDS == 6) {  // a count
+                        sum[w] += src[w];
+                        w += 1;
+                    } else {
+                        const u128 v = tb_u128(sum[w], sum[w + 1]) + tb_u128(src[w], src[w + 1]);
+                        sum[w] = tb_lo(v), sum[w + 1] = tb_hi(v);
+                        w += 2;
+                    }
+                }
+            }
+        }
+        const u64* account = (const u64*)(S.h_accounts + (u64)i * 128);
+        u128 closing[4], net[4];
+        tb_series_net(bins.data() + (u64)n_buckets * SERIES_BIN_WORDS, net);  // the tail
+        for (u32 col = 0; col < 4; col++) closing[col] = tb_u128(account[2 + 2 * col], account[3 + 2 * col]) - net[col];
+        for (u32 k = n_buckets; k-- > 0;) {
+            u64 row[STATEMENT_ROW_BYTES / 8];
+            tb_series_row(account, bins.data() + (u64)k * SERIES_BIN_WORDS, closing, row);
+            if (first + k < cap) {
+                memcpy(out + (first + k) * STATEMENT_ROW_BYTES, row, sizeof row);
+                written++;
+            }
+            for (u32 col = 0; col < 4; col++) closing[col] = tb_u128(row[2 + 2 * col], row[3 + 2 * col]);  // its opening
+        }
+    }
+    for (u32 d = 0; d < c.world; d++) {
+        if (c.Es[d]->qs->qr.h_bins[(u64)n * stride * SERIES_BIN_WORDS]) result->complete = 0;
+    }
+    result->count = written;
+    result->matched = m;
+}
+
+extern "C" int tbgpu_get_account_statement_series(tbgpu_t* E, const uint64_t* bounds, uint32_t n_buckets, const void* ids, uint32_t n,
+                                                  void* out, uint32_t out_cap_rows, tbgpu_query_result* result) {
+    static_assert(SERIES_ROWS_MAX == TBGPU_SERIES_ROWS_MAX && SERIES_ROWS_MAX == STATEMENT_IDS_MAX &&
+                      2 * SERIES_SIDE_WORDS == SERIES_BIN_WORDS && SERIES_RES_WORDS == STATEMENT_RES_WORDS,
+                  "k_series.h's constants are the header's, and the statements call's buffers fit");
+    // n * n_buckets <= 4,095: above 2,048 ids there is one bucket, and 256 slots hold at most 128 ids.
+    static_assert((size_t)CHANGE_LDS_BINS_SLOTS_MAX * 4 + 2 * 8 <= SERIES_LDS_FIXED_MAX &&
+                      (size_t)CHANGE_LDS_BINS_SLOTS_MAX / 2 * 4 + 3 * 8 <= SERIES_LDS_FIXED_MAX &&
+                      (size_t)SERIES_LDS_FIXED_MAX + (size_t)SERIES_LDS_BINS * (SERIES_BIN_WORDS * 8 + 4) <= 65536,
+                  "bounds, set, bins and tags stay within 64 KB a workgroup");
+    API_ENTER(E, false);
+    if (n_buckets == 0) return fail(TBGPU_STATUS_INVALID, "get_account_statement_series: no buckets");
+    if ((u64)n * n_buckets > TBGPU_SERIES_ROWS_MAX) {
+        return fail(TBGPU_STATUS_INVALID, "get_account_statement_series: %u ids x %u buckets (at most %u rows)", n, n_buckets,
+                    TBGPU_SERIES_ROWS_MAX);
+    }
+    if (!bounds) return fail(TBGPU_STATUS_INVALID, "get_account_statement_series: NULL bounds");
+    if (n == 0) return TBGPU_STATUS_OK;
+    if (!ids || !out || !result) return fail(TBGPU_STATUS_INVALID, "get_account_statement_series: NULL ids, out or result");
+    QueryCall c;
+    result->count = 0;
+    result->matched = 0;
+    result->complete = query_engines(E, true, &c);
+    for (u32 k = 0; k <= n_buckets; k++) {
+        if (bounds[k] == ~0ULL) return TBGPU_STATUS_OK;
+        if (k == 0) continue;
+        const bool open_end = k == n_buckets && bounds[k] == 0;
+        if (!open_end && (bounds[k] == 0 || bounds[k] < bounds[k - 1])) return TBGPU_STATUS_OK;
+    }
+    const bool one = c.world == 1;
+    NodeTablesArgs NT{};
+    NT.world = c.world;
+    for (u32 d = 0; d < c.world; d++) NT.T[d] = c.Es[d]->T;
+    // Every engine is drained before any is asked: a gather reads the owners' tables and a scan its
+    // posts' pending transfers on their homes.
+    for (u32 d = 0; d < c.world; d++) {
+        HIPCK(hipSetDevice(c.Es[d]->device));
+        if (c.Es[d]->pending) {
+            const int st = engine_sync(c.Es[d]);
+            if (st) return query_end(result, st);
+        }
+    }
+    memcpy(c.Es[0]->qs->qt.h_ids, ids, (u64)n * 16);
+    memcpy(c.Es[0]->qs->qr.h_bounds, bounds, ((u64)n_buckets + 1) * 8);
+    int st = query_side_by_side(c.Es, c.world, [&](u32 d) -> int {
+        if (d) {
+            memcpy(c.Es[d]->qs->qt.h_ids, c.Es[0]->qs->qt.h_ids, (u64)n * 16);
+            memcpy(c.Es[d]->qs->qr.h_bounds, c.Es[0]->qs->qr.h_bounds, ((u64)n_buckets + 1) * 8);
+        }
+        return series_enqueue(c.Es[d], NT, d, n, n_buckets, one, out_cap_rows);
+    });
+    if (st) return query_end(result, st);
+    if (!one) {
+        series_node_rows(c, n, n_buckets, out_cap_rows, (u8*)out, result);
+        return TBGPU_STATUS_OK;
+    }
+    tbgpu* S0 = c.Es[0];
+    const StatementBufs& S = S0->qs->qt;
+    const u64 matched = S.h_res[SERIES_RES_MATCHED];
+    const u32 m = (u32)std::min<u64>(matched, out_cap_rows);
+    if (matched > (u64)n * n_buckets) {
+        return query_end(result, fail(TBGPU_STATUS_PANIC, "get_account_statement_series: %llu rows for %u ids x %u buckets",
+                                      (unsigned long long)matched, n, n_buckets));
+    }
+    if (m) {
+        HIPCK(hipMemcpyAsync(out, S.d_out, (u64)m * STATEMENT_ROW_BYTES, hipMemcpyDeviceToHost, S0->stream));
+        HIPCK(hipStreamSynchronize(S0->stream));
+    }
+    if (S.h_res[SERIES_RES_ORPHAN]) result->complete = 0;
     result->count = m;
     result->matched = matched;
     return TBGPU_STATUS_OK;

@@ -342,6 +342,13 @@ tbgpu_query_result StateMachine::get_account_balance_integrals(uint64_t t_open, 
     return r;
 }
 
+tbgpu_query_result StateMachine::get_account_statement_series(const uint64_t* bounds, uint32_t n_buckets, const void* ids, uint32_t n,
+                                                              void* out, uint32_t out_cap_rows) {
+    tbgpu_query_result r{};
+    check(tbgpu_get_account_statement_series(engine_, bounds, n_buckets, ids, n, out, out_cap_rows, &r), "get_account_statement_series");
+    return r;
+}
+
 tbgpu_query_result StateMachine::query_transfers(const tbgpu_query_filter& filter, void* out, uint32_t out_cap_records) {
     tbgpu_query_result r{};
     check(tbgpu_query_transfers(engine_, &filter, out, out_cap_records, &r), "query_transfers");

@@ -301,6 +301,17 @@ public:
     tbgpu_query_result get_account_balance_integrals(uint64_t t_open, uint64_t t_close, const void* ids, uint32_t n, void* out,
                                                      uint32_t out_cap_rows);
 
+    // get_account_statements cut into consecutive periods (tbgpu_get_account_statement_series; a read,
+    // and no reference operation behind it): bucket k is (bounds[k], bounds[k + 1]], and every account
+    // the table holds and that existed at the last bound yields n_buckets tbgpu_account_statement
+    // rows, contiguous and bucket ascending, accounts in request order — each the row the single call
+    // writes, all from one scan of the log.  bounds: n_buckets + 1, non-decreasing; a first bound of 0:
+    // from before every record; a last bound of 0: up to now.  n * n_buckets is at most
+    // TBGPU_SERIES_ROWS_MAX.  result.matched is found accounts x n_buckets; result.complete is one value
+    // for the whole answer.
+    tbgpu_query_result get_account_statement_series(const uint64_t* bounds, uint32_t n_buckets, const void* ids, uint32_t n, void* out,
+                                                    uint32_t out_cap_rows);
+
     // The field-filter queries (tbgpu_query_transfers / tbgpu_query_accounts; reads, not commits): the
     // resident transfers, or the accounts, whose user_data_128 / user_data_64 / user_data_32 / ledger /
     // code equal the filter's non-zero fields, by timestamp (newest first under TBGPU_QUERY_REVERSED),

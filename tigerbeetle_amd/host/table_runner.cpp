@@ -317,8 +317,11 @@ std::string run_table(tb::StateMachine& sm, const std::string& text) {
 // t_close and n ids}, answered by get_account_statements (the records are tbgpu_account_statement rows).
 // --query-integrals (tests/test_gpu_integrals_cpp.py): the same request, answered by
 // get_account_balance_integrals (the records are tbgpu_account_balance_integral rows).
+// --query-series (tests/test_gpu_series_cpp.py): the prepares ending in {0, 0, the body's length, u32 n_buckets,
+// u32 n_ids, n_buckets + 1 bounds and n_ids ids}, answered by get_account_statement_series (the records are
+// tbgpu_account_statement rows).
 enum QueryKind { ACCOUNT_TRANSFERS, ACCOUNT_BALANCES, QUERY_TRANSFERS, QUERY_ACCOUNTS, CHANGE_EVENTS, ACCOUNT_TRANSFERS_MANY, ACCOUNTS_AT,
-                 LEDGER_BALANCES, PENDING_TRANSFERS, ACCOUNT_STATEMENTS, ACCOUNT_INTEGRALS };
+                 LEDGER_BALANCES, PENDING_TRANSFERS, ACCOUNT_STATEMENTS, ACCOUNT_INTEGRALS, ACCOUNT_SERIES };
 
 int run_query(tb::StateMachine& sm, QueryKind kind, const char* in_path, const char* out_path) {
     std::ifstream in(in_path, std::ios::binary);
@@ -429,6 +432,26 @@ int run_query(tb::StateMachine& sm, QueryKind kind, const char* in_path, const c
         printf("query: %u of %llu rows, complete %u\n", r.count, (unsigned long long)r.matched, r.complete);
         return o ? 0 : 2;
     }
+    if (kind == ACCOUNT_SERIES) {
+        uint32_t head[2] = {0, 0};  // n_buckets, n_ids
+        if (body.size() >= 8) memcpy(head, body.data(), 8);
+        const size_t bounds_bytes = ((size_t)head[0] + 1) * 8;
+        if (body.size() < 8 || head[0] == 0 || (uint64_t)head[0] * head[1] > TBGPU_SERIES_ROWS_MAX ||
+            body.size() != 8 + bounds_bytes + (size_t)head[1] * 16) {
+            fprintf(stderr, "%s: n_buckets, n_ids, n_buckets + 1 bounds and the ids of 16 bytes, at most %u rows\n", in_path,
+                    TBGPU_SERIES_ROWS_MAX);
+            return 2;
+        }
+        std::vector<uint64_t> bounds((size_t)head[0] + 1);
+        memcpy(bounds.data(), body.data() + 8, bounds_bytes);
+        std::vector<uint8_t> out((size_t)TBGPU_SERIES_ROWS_MAX * sizeof(tbgpu_account_statement));
+        const tbgpu_query_result r = sm.get_account_statement_series(bounds.data(), head[0], body.data() + 8 + bounds_bytes, head[1],
+                                                                     out.data(), TBGPU_SERIES_ROWS_MAX);
+        std::ofstream o(out_path, std::ios::binary);
+        o.write((const char*)&r, sizeof(r)).write((const char*)out.data(), (size_t)r.count * sizeof(tbgpu_account_statement));
+        printf("query: %u of %llu rows, complete %u\n", r.count, (unsigned long long)r.matched, r.complete);
+        return o ? 0 : 2;
+    }
     if (kind == PENDING_TRANSFERS) {
         tbgpu_pending_filter pf;
         if (body.size() != sizeof(pf)) {
@@ -476,8 +499,9 @@ int main(int argc, char** argv) {
     const bool pending = argc > 1 && std::string(argv[1]) == "--query-pending";
     const bool statements = argc > 1 && std::string(argv[1]) == "--query-statements";
     const bool integrals = argc > 1 && std::string(argv[1]) == "--query-integrals";
-    const bool query = fields || balances || changes || many || at || ledgers || pending || statements || integrals || (argc > 1 && std::string(argv[1]) == "--query");
-    QueryKind kind = balances ? ACCOUNT_BALANCES : changes ? CHANGE_EVENTS : many ? ACCOUNT_TRANSFERS_MANY : at ? ACCOUNTS_AT : ledgers ? LEDGER_BALANCES : pending ? PENDING_TRANSFERS : statements ? ACCOUNT_STATEMENTS : integrals ? ACCOUNT_INTEGRALS : ACCOUNT_TRANSFERS;
+    const bool series = argc > 1 && std::string(argv[1]) == "--query-series";
+    const bool query = fields || balances || changes || many || at || ledgers || pending || statements || integrals || series || (argc > 1 && std::string(argv[1]) == "--query");
+    QueryKind kind = series ? ACCOUNT_SERIES : balances ? ACCOUNT_BALANCES : changes ? CHANGE_EVENTS : many ? ACCOUNT_TRANSFERS_MANY : at ? ACCOUNTS_AT : ledgers ? LEDGER_BALANCES : pending ? PENDING_TRANSFERS : statements ? ACCOUNT_STATEMENTS : integrals ? ACCOUNT_INTEGRALS : ACCOUNT_TRANSFERS;
     const char* self = argv[0];
     if (fields && argc > 2) {
         const std::string which = argv[2];
@@ -496,8 +520,9 @@ int main(int argc, char** argv) {
                 "       %s --query-pending <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-statements <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-integrals <prepares.bin> <answer.bin> [device]\n"
+                "       %s --query-series <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-fields <transfers|accounts> <prepares.bin> <answer.bin> [device]\n",
-                self, self, self, self, self, self, self, self, self, self, self);
+                self, self, self, self, self, self, self, self, self, self, self, self);
         return 2;
     }
     if (query) {

@@ -542,6 +542,53 @@ class Engine:
                                                                 ctypes.byref(res)))
         return out[:res.count], int(res.matched), bool(res.complete)
 
+    SERIES_ROWS_MAX = 4095  # TBGPU_SERIES_ROWS_MAX
+
+    def get_account_statement_series(self, ids, bounds, cap=None):
+        """get_account_statements cut into consecutive periods (tbgpu_get_account_statement_series):
+        for each account of `ids` one STATEMENT_DTYPE row per bucket (bounds[k], bounds[k + 1]], an
+        account's rows contiguous and bucket ascending, accounts in request order; each row is the row
+        get_account_statements(ids, bounds[k], bounds[k + 1]) writes, from one scan of the log.
+        bounds[0] 0: from before every record; a last bound of 0: up to now; an account created at or
+        below the last bound has a row in every bucket.  len(ids) * (len(bounds) - 1) is at most
+        SERIES_ROWS_MAX.  Returns (rows, matched, complete); `matched` is found accounts x buckets,
+        `complete` is one value for the whole answer.  Invalid bounds (one at 2^64-1, an inner zero,
+        a bound below its predecessor) match nothing."""
+        ids = [int(i) for i in ids]
+        bounds = [int(b) for b in bounds]
+        if len(bounds) < 2:
+            raise ValueError("bounds name at least one bucket")
+        if len(ids) * (len(bounds) - 1) > self.SERIES_ROWS_MAX:
+            raise ValueError("at most %d rows in one call" % self.SERIES_ROWS_MAX)
+        body = b"".join(i.to_bytes(16, "little") for i in ids)
+        return self.get_account_statement_series_raw(body, bounds, cap)
+
+    def get_account_statement_series_raw(self, id_bytes, bounds, cap=None):
+        """get_account_statement_series from the ids' bytes, 16 each ({lo, hi}, little-endian)."""
+        id_bytes = bytes(id_bytes)
+        bounds = [int(b) for b in bounds]
+        if len(id_bytes) % 16 != 0:
+            raise ValueError("an id is 16 bytes")
+        if len(bounds) < 2:
+            raise ValueError("bounds name at least one bucket")
+        if any(b < 0 or b >> 64 for b in bounds):
+            raise ValueError("a bound is 64 bits")
+        n, n_buckets = len(id_bytes) // 16, len(bounds) - 1
+        if n * n_buckets > self.SERIES_ROWS_MAX:
+            raise ValueError("at most %d rows in one call" % self.SERIES_ROWS_MAX)
+        if n == 0:  # the library returns at once and leaves its result alone
+            return np.zeros(0, dtype=STATEMENT_DTYPE), 0, True
+        cap = n * n_buckets if cap is None else int(cap)
+        if cap < 0 or cap >> 32:
+            raise ValueError("cap is 32 bits")
+        out = np.zeros(max(cap, 1), dtype=STATEMENT_DTYPE)
+        res = _lib.tbgpu_query_result()
+        src = ctypes.create_string_buffer(id_bytes, len(id_bytes))
+        edges = (ctypes.c_uint64 * len(bounds))(*bounds)
+        _lib.check(self.lib.tbgpu_get_account_statement_series(self.h, edges, n_buckets, src, n, out.ctypes.data, cap,
+                                                               ctypes.byref(res)))
+        return out[:res.count], int(res.matched), bool(res.complete)
+
     @staticmethod
     def query_filter(user_data_128=0, user_data_64=0, user_data_32=0, ledger=0, code=0, *, reversed=False,
                      timestamp_min=0, timestamp_max=0, limit=8190):
@@ -937,6 +984,10 @@ class StateMachine:
     def get_account_balance_integrals(self, ids, t_open, t_close, out_cap_rows=None):
         """Time-weighted balances over a period (Engine.get_account_balance_integrals): a read, not a commit."""
         return self.engine.get_account_balance_integrals(ids, t_open, t_close, out_cap_rows)
+
+    def get_account_statement_series(self, ids, bounds, cap=None):
+        """Statement headers per bucket (Engine.get_account_statement_series): a read, not a commit."""
+        return self.engine.get_account_statement_series(ids, bounds, cap)
 
     def query_transfers(self, **filter):
         """The field-filter query over transfers (Engine.query_transfers): a read, not a commit."""

@@ -155,6 +155,9 @@ INTEGRAL_DTYPE = np.dtype(
 assert INTEGRAL_DTYPE.itemsize == 256
 INTEGRALS_MAX = 4095
 
+# tbgpu_get_account_statement_series: STATEMENT_DTYPE rows, ids x buckets of them at most.
+SERIES_ROWS_MAX = 4095
+
 # tbgpu_query_filter (include/tbgpu.h tbgpu_query_transfers / tbgpu_query_accounts): 64 bytes, no padding.
 QUERY_FILTER_DTYPE = np.dtype(
     _u128("user_data_128") + [("user_data_64", "<u8"), ("user_data_32", "<u4"), ("ledger", "<u4"), ("code", "<u2"),

@@ -1,7 +1,7 @@
 """The account-filter scan (tbgpu_get_account_transfers, csrc/k_query.h) over a 16M-transfer log (2 GB)
 against a device-to-device copy of the same log range, in one process.
 
-usage: python tools/gpu/query_scan.py [transfers] [runs] [--only account|fields|balances|change_events|many|asof|ledgers|pending|statements|integrals]
+usage: python tools/gpu/query_scan.py [transfers] [runs] [--only account|fields|balances|change_events|many|asof|ledgers|pending|statements|integrals|series]
 
 The log is built by the device generator, committed in place (the way tools/gpu/device_pass.py builds
 a pass): once with uniform C2 ids, where the queried account is a cold one (a few dozen matches), and
@@ -70,6 +70,13 @@ at the last record (the scan reads timestamps only).  The yardstick runs in the 
 tbgpu_get_account_statements call with the same ids and period.  An older library loaded through
 TBGPU_AB_LIB lacks the call: its get_account_statements alone is timed then, the yardstick to hold this
 build's call against.
+
+`--only series` (tbgpu_get_account_statement_series) times the C call alone, into buffers made
+once, on both logs, at (ids, buckets) = (4095, 1), (136, 30), (11, 365) and (1, 4095) with equal buckets over
+the whole log and --only statements' ids.  The yardsticks run in the same process: the same question asked as
+one tbgpu_get_account_statements call per bucket (three runs for 365 buckets and more), and one such call over
+the whole period.  An older library loaded through TBGPU_AB_LIB lacks the call: the yardsticks alone are
+timed then.
 """
 import json
 import os
@@ -568,6 +575,98 @@ def measure_integrals():
     return out
 
 
+def measure_series():
+    """get_account_statement_series beside the same question asked as n_buckets get_account_statements calls
+    and beside one such call over the whole period, on both logs, in one process."""
+    import ctypes
+
+    from tigerbeetle_amd import _lib
+    os.environ["TBGPU_QUERY_COOP"] = "0"
+    e = Engine(Options(accounts_max=n_acct, transfers_max=n_xfer, pass_events_max=pb * batch, pass_batches_max=pb))
+    a_lens = batches(n_acct, batch)
+    a_ts, t = timestamps(a_lens, 1_000_000_000)
+    acct = e.alloc(n_acct * 128)
+    e.generate_accounts(acct, 0, n_acct, seed=42)
+    res = e.alloc(max(n_acct, n_xfer) * 8)
+    rb = e.alloc((n_xfer // batch + 2) * 4)
+    e.commit_device_async(128, a_ts, a_lens, acct, res, rb)
+    e.sync()
+    rows_max = 4095
+    have = hasattr(e.lib, "tbgpu_get_account_statement_series")  # an older library (TBGPU_AB_LIB): the single calls alone
+    h_out = np.zeros(rows_max * 256, dtype=np.uint8)
+    h_res = _lib.tbgpu_query_result()
+
+    def raw_series(ids, bounds):
+        body = b"".join(i.to_bytes(16, "little") for i in ids)
+        src = ctypes.create_string_buffer(body, len(body))
+        edges = (ctypes.c_uint64 * len(bounds))(*bounds)
+        return lambda: _lib.check(e.lib.tbgpu_get_account_statement_series(e.h, edges, len(bounds) - 1, src, len(ids), h_out.ctypes.data,
+                                                                           rows_max, ctypes.byref(h_res)))
+
+    def raw_singles(ids, bounds):
+        body = b"".join(i.to_bytes(16, "little") for i in ids)
+        src = ctypes.create_string_buffer(body, len(body))
+
+        def each():
+            for t_open, t_close in zip(bounds, bounds[1:]):
+                _lib.check(e.lib.tbgpu_get_account_statements(e.h, t_open, t_close, src, len(ids), h_out.ctypes.data, len(ids),
+                                                              ctypes.byref(h_res)))
+        return each
+
+    def timed_few(fn, warmups, n):  # the long single-call loops: fewer runs
+        out = []
+        for i in range(warmups + n):
+            e.marker(0)
+            fn()
+            e.marker(1)
+            e.sync()
+            if i >= warmups:
+                out.append(e.marker_elapsed_ms(0, 1))
+        return statistics.median(out), min(out), max(out)
+
+    out = {}
+    for name, kind in (("uniform", "c2"), ("zipf", "c3")):
+        if name != "uniform":
+            e.reset_transfers()
+        log = e.log_window(n_xfer)
+        e.generate_transfers(log, 0, n_xfer, n_acct, seed=42, kind=KINDS[kind])
+        e.sync()
+        x_lens = batches(n_xfer, batch)
+        x_ts, t = timestamps(x_lens, t + 10)
+        e.commit_device_async(129, x_ts, x_lens, log, res, rb)
+        e.sync()
+        oldest, _, _ = e.query_transfers(limit=1)
+        newest, _, _ = e.query_transfers(reversed=True, limit=1)
+        t_first, t_last = int(oldest["timestamp"][0]), int(newest["timestamp"][0])
+        sample = e.to_host(log + (n_xfer // 2) * 128, min(n_xfer // 2, 1 << 16) * 128).view(TRANSFER_DTYPE)
+        accounts, counts = np.unique(sample[["debit_account_id_lo", "debit_account_id_hi"]], return_counts=True)
+        hottest = np.argsort(-counts, kind="stable")[:rows_max]  # the Zipf log's hottest accounts; any of the uniform log's
+        all_ids = [int(lo) | (int(hi) << 64) for lo, hi in accounts[hottest].tolist()]
+        assert len(all_ids) == rows_max
+        for n_ids, n_buckets in ((4095, 1), (136, 30), (11, 365), (1, 4095)):
+            ids = all_ids[:n_ids]
+            bounds = [t_first - 1 + (t_last - t_first + 1) * k // n_buckets for k in range(n_buckets + 1)]
+            assert bounds[-1] == t_last and all(a < b for a, b in zip(bounds, bounds[1:]))
+            if have:
+                rows, matched, complete = e.get_account_statement_series(ids, bounds)
+                assert complete and matched == n_ids * n_buckets == len(rows) and int(rows["debit_transfers"].sum()) > 0
+                for k in sorted({0, n_buckets // 2, n_buckets - 1}):
+                    assert rows[k::n_buckets].tobytes() == e.get_account_statements(ids, bounds[k], bounds[k + 1])[0].tobytes()
+            few = n_buckets >= 365
+            s_med, s_lo, s_hi = timed_few(raw_singles(ids, bounds), 1, 3) if few else timed(e, raw_singles(ids, bounds))
+            w_med, w_lo, w_hi = timed(e, raw_singles(ids, [bounds[0], bounds[-1]]))
+            entry = dict(ids=n_ids, buckets=n_buckets, single_calls_ms=round(s_med, 4), single_calls_min_ms=round(s_lo, 4),
+                         single_calls_max_ms=round(s_hi, 4), single_calls_runs=3 if few else runs, whole_period_call_ms=round(w_med, 4),
+                         whole_period_call_min_ms=round(w_lo, 4), whole_period_call_max_ms=round(w_hi, 4))
+            if have:
+                med, lo_ms, hi_ms = timed(e, raw_series(ids, bounds))
+                entry = row(med, lo_ms, hi_ms, over_single_calls=round(med / s_med, 4), over_whole_period_call=round(med / w_med, 2),
+                            **entry)
+            out["%s_series_%d_x_%d" % (name, n_ids, n_buckets)] = entry
+    e.close()
+    return out
+
+
 def measure_ledgers():
     """get_ledger_balances beside query_accounts, query_transfers and the copies, in one process."""
     import ctypes
@@ -754,6 +853,8 @@ elif only == "statements":
     result["statements"] = measure_statements()
 elif only == "integrals":
     result["integrals"] = measure_integrals()
+elif only == "series":
+    result["series"] = measure_series()
 elif only == "many":
     result["many"] = measure_many()
 elif only == "balances":
@@ -765,6 +866,6 @@ elif only != "fields":
     for shape in ("lane_per_record", "cooperative"):
         r = result[shape]
         r["bar_query_le_copy"] = all(v["ms"] <= r["copy_d2d"]["ms"] for k, v in r.items() if k != "copy_d2d")
-if only not in ("account", "balances", "change_events", "many", "asof", "ledgers", "pending", "statements", "integrals"):
+if only not in ("account", "balances", "change_events", "many", "asof", "ledgers", "pending", "statements", "integrals", "series"):
     result["field_filters"] = measure_fields()
 print(json.dumps(result))

@@ -826,6 +826,41 @@ pub fn StateMachineType(
             return @as(usize, result.count) * @sizeOf(tbgpu.tbgpu_account_balance_integral);
         }
 
+        /// Statement headers for the accounts `ids` per bucket (bounds[k], bounds[k + 1]]
+        /// (tbgpu_get_account_statement_series; a first bound of 0: from before every record, a last
+        /// bound of 0: up to now): a read, with no operation in this reference's enum, so nothing in
+        /// commit() dispatches to it (INTEGRATION.md, "Account statements per bucket"). Every id the
+        /// engine holds and that existed at the last bound yields bounds.len - 1 rows of 256 bytes,
+        /// contiguous and bucket ascending, ids in request order, into `output`; returns the bytes
+        /// written. `complete` is one value for the whole answer: false once transfers were evicted
+        /// or a post above bounds[0] had lost its pending transfer.
+        pub fn get_account_statement_series(
+            self: *StateMachine,
+            bounds: []const u64,
+            ids: []const u128,
+            output: []align(16) u8,
+            complete: *bool,
+        ) usize {
+            assert(bounds.len >= 2);
+            assert(ids.len * (bounds.len - 1) <= tbgpu.TBGPU_SERIES_ROWS_MAX);
+            var result: tbgpu.tbgpu_query_result = undefined;
+            result.count = 0;
+            result.complete = 1;
+            result.matched = 0;
+            check(tbgpu.tbgpu_get_account_statement_series(
+                self.engine,
+                bounds.ptr,
+                @intCast(bounds.len - 1),
+                ids.ptr,
+                @intCast(ids.len),
+                output.ptr,
+                @intCast(output.len / @sizeOf(tbgpu.tbgpu_account_statement)),
+                &result,
+            ));
+            complete.* = result.complete != 0;
+            return @as(usize, result.count) * @sizeOf(tbgpu.tbgpu_account_statement);
+        }
+
         pub fn compact(self: *StateMachine, callback: *const fn (*StateMachine) void, op: u64) void {
             assert(self.compact_callback == null);
             assert(self.checkpoint_callback == null);
