@@ -5,27 +5,20 @@
 // was stored at commit, the log is in HBM and the account table holds the current balances, so
 //   balance_at(a, T) = current(a) - the effects of every live resident record that names a and has a
 //                      timestamp strictly above T,
-// per column modulo 2^128 — k_change_events.h's sum with the caller's ids as the page's accounts and
-// T as the page's last timestamp.  The scan *is* tb_change_effects, with the two parameters a request
-// needs that a page does not (below); what is new is around it, so that nothing but the ids and the
-// answer crosses PCIe:
+// per column modulo 2^128.  A member of k_account_scan.h's family whose scan *is* k_change_events.h's
+// tb_change_effects, with the caller's ids as the page's accounts and T as the page's last timestamp:
 //   tb_asof_gather   a lane per request position: the id's record from its owner's table, or a
 //                    not-found mark (absent, reserved, or created after T); a found id enters the set;
-//   tb_change_effects  (k_change_events.h) bins[index] += the effects of the records newer than T;
 //   tb_asof_emit     a lane per request position: a found one writes its record, the four balances
 //                    less its id's bin, at its rank among the found positions.
-// The set is k_change_events.h's — 32-bit entries {16-bit tag, index + 1}, probed by tb_change_probe
-// — but built on the device: an id's index is the smallest request position that names it, and `ids`
-// is the request itself, so the set needs no id array of its own and a repeated id resolves to one
-// bin whichever lane came first.  An insert is one atomicCAS on an empty slot or one atomicMin on a
-// slot that already holds the same id (same id, same tag: the smaller entry is the smaller position).
-// The scan's two parameters.  A page's order says which accounts are hot and a request's does not, so
-// the LDS bins are CACHED: each is claimed by the first index that adds to it in the workgroup,
-// whatever its position in the request.  And 8,191 ids need 16,384 slots, all 64 KB as 32-bit entries:
-// above 4,096 ids the workgroup's copy of the set is narrowed to 16 bits an entry (the set in HBM
-// stays as it is), which leaves the bins their room (DESIGN.md 7h has both measured).
-// Plain launches: no grid barrier, no spin, no wait on another workgroup; every loop is bounded by
-// the set's slots, a workgroup's share of the found flags or the 64 lanes of a wave.
+// Its own, and every later member's with it: the set is built on the device.  An id's index is the
+// smallest request position that names it, and `ids` is the request itself, so the set needs no id
+// array of its own and a repeated id resolves to one bin whichever lane came first.  An insert is one
+// atomicCAS on an empty slot or one atomicMin on a slot that already holds the same id (same id, same
+// tag: the smaller entry is the smaller position).  A request's order says nothing about hotness, so
+// the scan's LDS bins are CACHED, claimed by first use; and 8,191 ids need 16,384 slots, all 64 KB as
+// 32-bit entries, so above 4,096 ids the workgroup's copy of the set is narrowed to 16 bits an entry
+// (the set in HBM stays as it is), which leaves the bins their room (DESIGN.md 7h has both measured).
 #pragma once
 
 #include "k_change_events.h"
@@ -35,10 +28,6 @@
 // 28 KB of bins and their tags beside at most 32 KB of set — 8,192 entries of 32 bits up to 4,096 ids,
 // 16,384 narrowed to 16 bits above — stay within 64 KB.
 #define ASOF_LDS_BINS 448u
-// What tb_asof_emit leaves in `res`: {0: found positions, 1: a post's pending transfer was not resident}.
-#define ASOF_RES_MATCHED 0
-#define ASOF_RES_ORPHAN 1
-#define ASOF_RES_WORDS 2
 
 // Request position i's id into the set, under the smallest position that names it.
 __device__ static inline void tb_asof_insert(u32* set, u32 mask, const u64* ids, u32 i, u64 lo, u64 hi) {
@@ -80,35 +69,18 @@ __global__ __launch_bounds__(QUERY_THREADS) void tb_asof_gather(NodeTablesArgs N
     if (have && set) tb_asof_insert(set, mask, ids, i, lo, hi);
 }
 
-// Workgroup b answers request positions [b, b + 1) * QUERY_THREADS.  Its base — the found positions
-// before its first — is a sum over found[0, b * QUERY_THREADS), at most 32 flags a thread, so no
-// workgroup waits for another.  set, bins: the scan's (bins + n * BALANCE_SLOT_WORDS its flag slot),
-// or null when none ran: the records go out as they are.  out: room for `cap` records.
+// Workgroup b answers request positions [b, b + 1) * QUERY_THREADS (tb_scan_emit_rank).  set, bins: the
+// scan's (bins + n * BALANCE_SLOT_WORDS its flag slot), or null when none ran: the records go out as
+// they are.  out: room for `cap` records.
 __global__ __launch_bounds__(QUERY_THREADS) void tb_asof_emit(const u64* ids, u32 n, const u8* accounts, const u32* found,
                                                               const u32* set, u32 mask, const u64* bins, u32 cap, u8* out,
                                                               u64* res) {
-    __shared__ u32 s_part[QUERY_WAVES];
-    __shared__ u32 s_wave[QUERY_WAVES];
-    const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const u32 first = blockIdx.x * QUERY_THREADS, i = first + threadIdx.x;
-    u32 before = 0;
-    for (u32 j = threadIdx.x; j < first; j += QUERY_THREADS) before += found[j];
-#pragma unroll
-    for (u32 off = 32; off > 0; off >>= 1) before += __shfl_xor(before, off);
-    const bool have = i < n && found[i] != 0;
-    const u64 mine = __ballot(have);
-    if (lane == 0) s_part[wave] = before, s_wave[wave] = (u32)__popcll(mine);
-    __syncthreads();
-    u32 rank = (u32)__popcll(mine & ((1ULL << lane) - 1));
-    u32 total = 0;
-    for (u32 w = 0; w < QUERY_WAVES; w++) {
-        rank += s_part[w];
-        if (w < wave) rank += s_wave[w];
-        total += s_part[w] + s_wave[w];
-    }
-    if (first + QUERY_THREADS >= n && threadIdx.x == 0) {  // the last workgroup: every found position
-        res[ASOF_RES_MATCHED] = total;
-        res[ASOF_RES_ORPHAN] = bins ? bins[(u64)n * BALANCE_SLOT_WORDS + CHANGE_FLAG_ORPHAN] : 0;
+    u32 rank, total;
+    const bool have = tb_scan_emit_rank(found, n, rank, total);
+    const u32 i = blockIdx.x * QUERY_THREADS + threadIdx.x;
+    if ((blockIdx.x + 1) * QUERY_THREADS >= n && threadIdx.x == 0) {  // the last workgroup: every found position
+        res[SCAN_RES_MATCHED] = total;
+        res[SCAN_RES_ORPHAN] = bins ? bins[(u64)n * BALANCE_SLOT_WORDS + CHANGE_FLAG_ORPHAN] : 0;
     }
     if (!have || rank >= cap) return;
     const ulonglong2* src = (const ulonglong2*)(accounts + (u64)i * 128);

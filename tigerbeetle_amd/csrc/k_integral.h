@@ -26,13 +26,8 @@
 //   tb_asof_gather        (k_asof.h, as it is, T = t_end) the owners' records, the found flags, the set;
 //   tb_integral_effects   bins[index] += the record's zone sums, for every record above t_open;
 //   tb_integral_emit      a lane per request position: a found one writes its 256-byte row at its rank.
-// The scan is modelled on tb_statement_effects: the timestamp plane alone first, the id set probed
-// only above t_open, the liveness probe on a set hit only, the wave's lanes combined along
-// (index, zone) chains before one adds, LDS bins claimed by first use (tb_change_bin_claim), flushed
-// to HBM at the workgroup's end and bypassed for HBM when no slot is free.
-// Plain launches: no grid barrier, no spin, no wait on another workgroup; every loop is bounded by
-// the workgroup's tiles, the set's slots, a workgroup's share of the found flags or the 64 lanes of a
-// wave.
+// A member of k_account_scan.h's family.  Its own: the 28-word bin, and a chain pass that sums a column
+// at a time, so that one 128-bit and one 192-bit sum are live at once.
 #pragma once
 
 #include "k_asof.h"
@@ -55,10 +50,6 @@
 #ifndef INTEGRAL_LDS_BINS
 #define INTEGRAL_LDS_BINS 88u
 #endif
-// What tb_integral_emit leaves in `res`, as tb_asof_emit does.
-#define INTEGRAL_RES_MATCHED 0
-#define INTEGRAL_RES_ORPHAN 1
-#define INTEGRAL_RES_WORDS 2
 
 // A value modulo 2^192, low word first.
 struct U192 {
@@ -114,77 +105,36 @@ __global__ __launch_bounds__(CHANGE_THREADS) void tb_integral_effects(NodeTables
     u32* s_set = (u32*)s_lds;                // mask + 1 entries
     u64* s_bins = (u64*)(s_set + mask + 1);  // the claimed bins
     u32* s_tags = (u32*)(s_bins + INTEGRAL_LDS_BINS * INTEGRAL_BIN_WORDS);  // the index each holds
-    const Tables& T = N.T[self];
     const u32 lane = threadIdx.x & 63;
     u64* flags = bins + (u64)n_ids * INTEGRAL_BIN_WORDS;
-    for (u32 i = threadIdx.x; i <= mask; i += CHANGE_THREADS) s_set[i] = set[i];
-    for (u32 i = threadIdx.x; i < INTEGRAL_LDS_BINS * INTEGRAL_BIN_WORDS; i += CHANGE_THREADS) s_bins[i] = 0;
-    for (u32 i = threadIdx.x; i < INTEGRAL_LDS_BINS; i += CHANGE_THREADS) s_tags[i] = CHANGE_NONE;
+    tb_scan_lds_init(s_set, set, mask, s_bins, INTEGRAL_LDS_BINS * INTEGRAL_BIN_WORDS, s_tags, INTEGRAL_LDS_BINS);
     __syncthreads();
     for (u32 t = 0; t < CHANGE_TILES; t++) {
         const u64 tile0 = ((u64)blockIdx.x * CHANGE_TILES + t) * CHANGE_THREADS, pos = tile0 + threadIdx.x;
         if (tile0 >= n) break;  // the whole workgroup alike
-        // The timestamp alone first: at or below t_open (every tile of an ordered log's prefix) the
-        // ids are never read.
-        const u64* w = (const u64*)&T.xlog[pos < n ? pos : 0];
-        const u64 ts = pos < n ? tb_log_ts(T, pos, w[15]) : 0;  // the plane: coalesced, beside chunk 7
-        const bool wanted = ts > t_open;
-        if (__ballot(wanted) == 0) continue;  // the whole wave alike
+        ScanRecord r;
+        u128 a0 = 0, a1 = 0;    // the record's effect on its sides' *_pending and *_posted
+        bool released = false;  // a0 is negative: a post or a void releases a hold
+        const u64 any = tb_scan_record(N, self, pos, n, t_open, s_set, mask, ids, flags, r, [&](u32 tf, u128 amount, u128 p) {
+            const BalanceEffect e = tb_balance_effect(tf, amount, p);
+            a0 = e.pend, a1 = e.post;
+            released = tb_effect_is_post(tf) || (!(tf & TF_PENDING) && (tf & TF_VOID));  // tb_balance_effect's cases by sign
+        });
+        if (any == 0) continue;  // the whole wave alike
+        const u64 ts = r.ts;
         const u32 zone = ts > t_end ? 0 : 1;
-        u32 idx[2] = {CHANGE_NONE, CHANGE_NONE};  // the debit and the credit account's index
-        u128 a0 = 0, a1 = 0;                      // the record's effect on its sides' *_pending and *_posted
-        bool released = false;                    // a0 is negative: a post or a void releases a hold
-        if (wanted) {
-            const ulonglong2 d = ((const ulonglong2*)w)[1], c = ((const ulonglong2*)w)[2];
-            idx[0] = tb_change_probe(s_set, mask, ids, d.x, d.y);
-            idx[1] = tb_change_probe(s_set, mask, ids, c.x, c.y);
-        }
-        if ((idx[0] & idx[1]) != CHANGE_NONE) {
-            // Live: the id index holds this record's id at this position (tb_query_hit's test).
-            const u64 lo = w[0], hi = w[1];
-            if (tb_id_reserved(lo, hi) || tb_transfer_find(T, lo, hi) != (u32)pos) {
-                idx[0] = idx[1] = CHANGE_NONE;
-            } else {
-                const u128 amount = tb_u128(w[6], w[7]);
-                const u32 tf = (u32)(w[14] >> 48);
-                u128 p = amount;
-                if (tb_effect_is_post(tf) && !tb_pending_amount(N, w[8], w[9], &p)) {
-                    atomicOr((unsigned long long*)flags, 1ULL);
-                }
-                const BalanceEffect e = tb_balance_effect(tf, amount, p);
-                a0 = e.pend, a1 = e.post;
-                released = tb_effect_is_post(tf) || (!(tf & TF_PENDING) && (tf & TF_VOID));  // tb_balance_effect's cases by sign
-            }
-        }
-        // The adds, a side at a time.  The lanes of the wave that hold the same (index, zone) combine
-        // before one of them adds, by tb_statement_effects' chains: the loop visits each distinct key
-        // once and links its lanes, and a pointer-jumping pass of six steps sums every chain into its
-        // first lane.  Then every first lane adds at once: into the workgroup's LDS bin where the
-        // index has claimed one, else into the bin in HBM.
+        // The adds, a side at a time: the lanes that hold the same (index, zone) are linked into
+        // chains, then every first lane adds at once, into the workgroup's LDS bin where the index
+        // has claimed one, else into the bin in HBM.
 #pragma unroll
         for (u32 side = 0; side < 2; side++) {
-            const u32 index = idx[side];
+            const u32 index = r.idx[side];
             const bool named = index != CHANGE_NONE;
             bool adds = named;  // after the chains: this lane adds its chain's sum
             const u32 my = adds ? index * 2 + zone : CHANGE_NONE;  // (an index is below 4,095)
-            u32 nxt = lane;  // the next lane of this lane's group; itself: none
-            bool chains = false;
-            u64 todo = __ballot(adds);
             const bool weighted = __ballot(adds && zone == 1) != 0;  // the whole wave alike
-            while (todo) {  // at most 64 rounds: every round clears its leader's bit
-                const int leader = __ffsll((unsigned long long)todo) - 1;
-                const u32 b = __shfl(my, leader);
-                const bool mine = my == b;  // (CHANGE_NONE lanes never equal a leader's key)
-                const u64 group = __ballot(mine);
-                todo &= ~group;
-                if ((group & (group - 1)) == 0) continue;
-                chains = true;
-                if (mine) {
-                    const u64 above = lane == 63 ? 0 : group & ~((2ULL << lane) - 1);
-                    if (above) nxt = (u32)__ffsll((unsigned long long)above) - 1;
-                    if ((int)lane != leader) adds = false;
-                }
-            }
+            u32 nxt;  // the next lane of this lane's group; itself: none
+            const bool chains = tb_scan_link(lane, my, adds, nxt);
             // A column at a time, *_pending then *_posted, so that one 128-bit and one 192-bit sum are
             // live at once: v = the side's effect, x (zone 1) = the effect times (t_end - ts), and after
             // step s of the chain pass both cover 2^(s+1) lanes of the chain from this lane on.
@@ -260,34 +210,17 @@ __host__ __device__ static inline void tb_integral_row(const u64* account /* 128
     row[30] = t_open, row[31] = t_end;
 }
 
-// Workgroup b answers request positions [b, b + 1) * QUERY_THREADS, ranked as tb_statement_emit ranks
-// them: its base is a sum over found[0, b * QUERY_THREADS), so no workgroup waits for another.
+// Workgroup b answers request positions [b, b + 1) * QUERY_THREADS (tb_scan_emit_rank).
 // out: room for `cap` rows of INTEGRAL_ROW_BYTES.
 __global__ __launch_bounds__(QUERY_THREADS) void tb_integral_emit(const u64* ids, u32 n, const u8* accounts, const u32* found,
                                                                   const u32* set, u32 mask, const u64* bins, u64 t_open, u64 t_end,
                                                                   u32 cap, u8* out, u64* res) {
-    __shared__ u32 s_part[QUERY_WAVES];
-    __shared__ u32 s_wave[QUERY_WAVES];
-    const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const u32 first = blockIdx.x * QUERY_THREADS, i = first + threadIdx.x;
-    u32 before = 0;
-    for (u32 j = threadIdx.x; j < first; j += QUERY_THREADS) before += found[j];
-#pragma unroll
-    for (u32 off = 32; off > 0; off >>= 1) before += __shfl_xor(before, off);
-    const bool have = i < n && found[i] != 0;
-    const u64 mine = __ballot(have);
-    if (lane == 0) s_part[wave] = before, s_wave[wave] = (u32)__popcll(mine);
-    __syncthreads();
-    u32 rank = (u32)__popcll(mine & ((1ULL << lane) - 1));
-    u32 total = 0;
-    for (u32 w = 0; w < QUERY_WAVES; w++) {
-        rank += s_part[w];
-        if (w < wave) rank += s_wave[w];
-        total += s_part[w] + s_wave[w];
-    }
-    if (first + QUERY_THREADS >= n && threadIdx.x == 0) {  // the last workgroup: every found position
-        res[INTEGRAL_RES_MATCHED] = total;
-        res[INTEGRAL_RES_ORPHAN] = bins[(u64)n * INTEGRAL_BIN_WORDS];
+    u32 rank, total;
+    const bool have = tb_scan_emit_rank(found, n, rank, total);
+    const u32 i = blockIdx.x * QUERY_THREADS + threadIdx.x;
+    if ((blockIdx.x + 1) * QUERY_THREADS >= n && threadIdx.x == 0) {  // the last workgroup: every found position
+        res[SCAN_RES_MATCHED] = total;
+        res[SCAN_RES_ORPHAN] = bins[(u64)n * INTEGRAL_BIN_WORDS];
     }
     if (!have || rank >= cap) return;
     const u64* account = (const u64*)(accounts + (u64)i * 128);

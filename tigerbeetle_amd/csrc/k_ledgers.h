@@ -20,8 +20,8 @@
 // a ledger's bin is its slot, so the set holds nothing else.  A requested 0 asks for every ledger together: one
 // more bin, behind the set's, that takes every live owned account and every live newer record.
 // Both scans combine before any atomic.  The common table has one ledger, so all 64 lanes of a wave
-// hit one bin: the lanes that share a bin are chained and summed by pointer jumping (as
-// tb_change_effects does), the every-ledger share by a butterfly (tb_wave_sum128) carried in registers
+// hit one bin: the lanes that share a bin are chained and summed by pointer jumping
+// (k_account_scan.h's tb_scan_combine), the every-ledger share by a butterfly (tb_wave_sum128) carried in registers
 // across the workgroup's tiles; the chains' first lanes add into LDS bins claimed at first use
 // (tb_change_bin_claim), and the workgroup hands each LDS bin it touched to HBM once, at its end
 // (tb_atomic_add128).  Sizes: 512 threads; 16 tiles (8,192 records) a workgroup of the log scan, as
@@ -79,47 +79,6 @@ __host__ static inline u32 tb_ledger_insert(u32* set, u32 mask, u32 ledger) {
     while (set[s] != 0 && set[s] != ledger) s = (s + 1) & mask;
     set[s] = ledger;
     return s;
-}
-
-// The lanes of the wave that hold the same bin `my` (CHANGE_NONE: none) combine: afterwards `adds` is
-// true in one lane of each group, whose v[0, NV) and count hold the group's sums.  tb_change_effects'
-// way: a loop over the distinct bins links each group's lanes into a chain, then one pointer-jumping
-// pass of six steps sums every chain at once into its first lane.
-template <u32 NV>
-__device__ static inline void tb_ledger_combine(u32 lane, u32 my, bool& adds, u128 (&v)[NV], u32& count) {
-    u32 nxt = lane;  // the next lane of this lane's group; itself: none
-    bool chains = false;
-    u64 todo = __ballot(adds);
-    while (todo) {  // at most 64 rounds: every round clears its leader's bit
-        const int leader = __ffsll((unsigned long long)todo) - 1;
-        const u32 b = __shfl(my, leader);
-        const bool mine = adds && my == b;
-        const u64 group = __ballot(mine);
-        todo &= ~group;
-        if ((group & (group - 1)) == 0) continue;
-        chains = true;
-        if (mine) {
-            const u64 above = lane == 63 ? 0 : group & ~((2ULL << lane) - 1);
-            if (above) nxt = (u32)__ffsll((unsigned long long)above) - 1;
-            if ((int)lane != leader) adds = false;
-        }
-    }
-    if (!chains) return;  // the whole wave alike
-#pragma unroll
-    for (u32 s = 0; s < 6; s++) {
-        const bool has = nxt != lane;
-        u128 o[NV];
-#pragma unroll
-        for (u32 c = 0; c < NV; c++) o[c] = tb_shfl128(v[c], nxt);
-        const u32 oc = __shfl(count, nxt);
-        const u32 nn = __shfl(nxt, nxt);
-        if (has) {
-#pragma unroll
-            for (u32 c = 0; c < NV; c++) v[c] += o[c];
-            count += oc;
-            nxt = nn == nxt ? lane : nn;
-        }
-    }
 }
 
 // A chain's first lane adds its sums: into the workgroup's LDS bin of `my` where it has or gets one,
@@ -190,7 +149,7 @@ __global__ __launch_bounds__(LEDGER_THREADS) void tb_ledger_accounts(Tables T, u
             held_count += (u32)__popcll(__ballot(count != 0));
         }
         if (__ballot(adds) == 0) continue;
-        tb_ledger_combine<4>(lane, my, adds, v, count);
+        tb_scan_combine<4>(lane, my, adds, v, count);
         if (adds) {
             u64* dst = bins + (u64)my * LEDGER_BIN_WORDS;
             tb_ledger_add<4, LEDGER_TABLE_WORDS>(s_tags, s_bins, my, v, count, dst, dst + LEDGER_BIN_COUNT);
@@ -269,7 +228,7 @@ __global__ __launch_bounds__(LEDGER_THREADS) void tb_ledger_effects(NodeTablesAr
         if (all) held[0] += tb_wave_sum128(v[0]), held[1] += tb_wave_sum128(v[1]);
         if (__ballot(adds) == 0) continue;
         u32 none = 0;
-        tb_ledger_combine<2>(lane, my, adds, v, none);
+        tb_scan_combine<2>(lane, my, adds, v, none);
         if (adds) {
             u64* dst = bins + (u64)my * LEDGER_BIN_WORDS + LEDGER_BIN_EFFECTS;
             tb_ledger_add<2, LEDGER_LOG_WORDS>(s_tags, s_bins, my, v, 0, dst, dst);

@@ -16,14 +16,10 @@
 //   tb_series_effects  bins[index * (B + 1) + bucket] += the record's sums, for every record above bounds[0];
 //   tb_series_emit     a lane per (found account, bucket): the suffix sum over the account's later
 //                      buckets is a segmented scan over the lanes, so no lane walks B buckets.
-// The scan is modelled on tb_statement_effects: the timestamp alone first, the set probed on both
-// ids, the liveness probe on a set hit only, and only then the bucket, a binary search of at most 12
-// steps over the bounds in LDS.  The in-wave combine and the claimed LDS bins go by the key
-// index * (B + 1) + bucket: one wave can hold one account below bounds[0], in many buckets and in the
-// tail at once.
-// Plain launches: no grid barrier, no spin, no wait on another workgroup; every loop is bounded by
-// the workgroup's tiles, the set's slots, the 12 steps of the search, the request's found flags, an
-// account's buckets shared among a workgroup's threads or the 64 lanes of a wave.
+// A member of k_account_scan.h's family.  Its own: after the record step, and only for a live hit, the
+// bucket, a binary search of at most 12 steps over the bounds in LDS; the in-wave combine and the
+// claimed LDS bins go by the key index * (B + 1) + bucket: one wave can hold one account below
+// bounds[0], in many buckets and in the tail at once.
 #pragma once
 
 #include "k_statement.h"
@@ -31,8 +27,7 @@
 #define SERIES_ROWS_MAX 4095u  // TBGPU_SERIES_ROWS_MAX: n * n_buckets, 256-B rows in one message body
 // A bin, in 64-bit words: per side (debit, then credit) {pending_in, pending_out, posted_in} of two
 // words each and the side's transfer count — k_statement.h's zone 1.
-#define SERIES_SIDE_WORDS 7
-#define SERIES_BIN_WORDS 14
+#define SERIES_BIN_WORDS (2 * STATEMENT_SIDE_WORDS)
 // Keys: index * (B + 1) + bucket, index < n and n * B <= 4,095, so below n * (B + 1) <= 8,190.
 #define SERIES_KEYS_MAX (2 * SERIES_ROWS_MAX)
 #define SERIES_SEARCH_STEPS 12  // 2^12 > 4,095 bounds
@@ -48,10 +43,6 @@
 #endif
 // tb_series_emit reads the request's found flags in chunks of its workgroup's size: 16 x 256 >= 4,095.
 #define SERIES_EMIT_CHUNKS ((SERIES_ROWS_MAX + QUERY_THREADS) / QUERY_THREADS)
-// What tb_series_emit leaves in `res`: {0: rows = found positions * B, 1: the orphan flag}.
-#define SERIES_RES_MATCHED 0
-#define SERIES_RES_ORPHAN 1
-#define SERIES_RES_WORDS 2
 
 __host__ static inline size_t tb_series_lds_bytes(u32 slots, u32 n_buckets) {
     return (size_t)slots * 4 + ((size_t)n_buckets + 1) * 8 + (size_t)SERIES_LDS_BINS * (SERIES_BIN_WORDS * 8 + 4);
@@ -71,7 +62,6 @@ __global__ __launch_bounds__(CHANGE_THREADS) void tb_series_effects(NodeTablesAr
     u32* s_set = (u32*)(s_bounds + n_buckets + 1);     // mask + 1 entries
     u64* s_bins = (u64*)(s_set + mask + 1);            // the claimed bins (mask + 1 is even: 8-B aligned)
     u32* s_tags = (u32*)(s_bins + SERIES_LDS_BINS * SERIES_BIN_WORDS);  // the key each holds
-    const Tables& T = N.T[self];
     const u32 lane = threadIdx.x & 63;
     const u32 stride = n_buckets + 1;  // keys of one index
     u64* flags = bins + (u64)n_ids * stride * SERIES_BIN_WORDS;
@@ -79,102 +69,48 @@ __global__ __launch_bounds__(CHANGE_THREADS) void tb_series_effects(NodeTablesAr
         const u64 b = bounds[i];
         s_bounds[i] = i == n_buckets && b == 0 ? ~0ULL : b;
     }
-    for (u32 i = threadIdx.x; i <= mask; i += CHANGE_THREADS) s_set[i] = set[i];
-    for (u32 i = threadIdx.x; i < SERIES_LDS_BINS * SERIES_BIN_WORDS; i += CHANGE_THREADS) s_bins[i] = 0;
-    for (u32 i = threadIdx.x; i < SERIES_LDS_BINS; i += CHANGE_THREADS) s_tags[i] = CHANGE_NONE;
+    tb_scan_lds_init(s_set, set, mask, s_bins, SERIES_LDS_BINS * SERIES_BIN_WORDS, s_tags, SERIES_LDS_BINS);
     __syncthreads();
     const u64 t_open = s_bounds[0];
     for (u32 t = 0; t < CHANGE_TILES; t++) {
         const u64 tile0 = ((u64)blockIdx.x * CHANGE_TILES + t) * CHANGE_THREADS, pos = tile0 + threadIdx.x;
         if (tile0 >= n) break;  // the whole workgroup alike
-        // The timestamp alone first: at or below bounds[0] (every tile of an ordered log's prefix)
-        // the ids are never read.
-        const u64* w = (const u64*)&T.xlog[pos < n ? pos : 0];
-        const u64 ts = pos < n ? tb_log_ts(T, pos, w[15]) : 0;  // the plane: coalesced, beside chunk 7
-        const bool wanted = ts > t_open;
-        if (__ballot(wanted) == 0) continue;  // the whole wave alike
-        u32 idx[2] = {CHANGE_NONE, CHANGE_NONE};  // the debit and the credit account's index
-        u128 a0 = 0, a1 = 0, a2 = 0;              // {pending_in, pending_out, posted_in}
+        ScanRecord r;
+        u128 a[3] = {0, 0, 0};  // {pending_in, pending_out, posted_in}
         u32 bucket = 0;
-        if (wanted) {
-            const ulonglong2 d = ((const ulonglong2*)w)[1], c = ((const ulonglong2*)w)[2];
-            idx[0] = tb_change_probe(s_set, mask, ids, d.x, d.y);
-            idx[1] = tb_change_probe(s_set, mask, ids, c.x, c.y);
-        }
-        if ((idx[0] & idx[1]) != CHANGE_NONE) {
-            // Live: the id index holds this record's id at this position (tb_query_hit's test).
-            const u64 lo = w[0], hi = w[1];
-            if (tb_id_reserved(lo, hi) || tb_transfer_find(T, lo, hi) != (u32)pos) {
-                idx[0] = idx[1] = CHANGE_NONE;
-            } else {
-                const u128 amount = tb_u128(w[6], w[7]);
-                const u32 tf = (u32)(w[14] >> 48);
-                u128 p = amount;
-                if (tb_effect_is_post(tf) && !tb_pending_amount(N, w[8], w[9], &p)) {
-                    atomicOr((unsigned long long*)flags, 1ULL);
-                }
-                const StatementFlows f = tb_statement_flows(tf, amount, p);
-                a0 = f.pending_in, a1 = f.pending_out, a2 = f.posted_in;
-                // The bucket: the number of bounds[1 .. n_buckets] below ts — the smallest k with
-                // ts <= bounds[k + 1], or n_buckets, the tail, above them all.
-                u32 lo_k = 0, hi_k = n_buckets;
+        const u64 any = tb_scan_record(N, self, pos, n, t_open, s_set, mask, ids, flags, r, [&](u32 tf, u128 amount, u128 p) {
+            const StatementFlows f = tb_statement_flows(tf, amount, p);
+            a[0] = f.pending_in, a[1] = f.pending_out, a[2] = f.posted_in;
+            // The bucket: the number of bounds[1 .. n_buckets] below ts — the smallest k with
+            // ts <= bounds[k + 1], or n_buckets, the tail, above them all.
+            u32 lo_k = 0, hi_k = n_buckets;
 #pragma unroll 1
-                for (u32 s = 0; s < SERIES_SEARCH_STEPS && lo_k < hi_k; s++) {
-                    const u32 mid = (lo_k + hi_k) >> 1;
-                    if (s_bounds[1 + mid] < ts) lo_k = mid + 1;
-                    else hi_k = mid;
-                }
-                bucket = lo_k;
+            for (u32 s = 0; s < SERIES_SEARCH_STEPS && lo_k < hi_k; s++) {
+                const u32 mid = (lo_k + hi_k) >> 1;
+                if (s_bounds[1 + mid] < r.ts) lo_k = mid + 1;
+                else hi_k = mid;
             }
-        }
-        // The adds, a side at a time.  The lanes of the wave that hold the same key combine before
-        // one of them adds, by tb_statement_effects' chains; then every first lane adds at once: into
-        // the workgroup's LDS bin where the key has claimed one, else into the bin in HBM.
+            bucket = lo_k;
+        });
+        if (any == 0) continue;  // the whole wave alike
+        // The adds, a side at a time: the lanes that hold the same key combine, then every first lane
+        // adds at once, into the workgroup's LDS bin where the key has claimed one, else into the bin
+        // in HBM.
 #pragma unroll
         for (u32 side = 0; side < 2; side++) {
-            const u32 index = idx[side];
+            const u32 index = r.idx[side];
             bool adds = index != CHANGE_NONE;
             const u32 my = adds ? index * stride + bucket : CHANGE_NONE;  // (below SERIES_KEYS_MAX)
-            u128 v0 = adds ? a0 : (u128)0, v1 = adds ? a1 : (u128)0, v2 = adds ? a2 : (u128)0;
+            u128 v[3] = {adds ? a[0] : (u128)0, adds ? a[1] : (u128)0, adds ? a[2] : (u128)0};
             u32 count = adds ? 1 : 0;  // the lanes summed: the bucket's transfers
-            u32 nxt = lane;            // the next lane of this lane's group; itself: none
-            bool chains = false;
-            u64 todo = __ballot(adds);
-            while (todo) {  // at most 64 rounds: every round clears its leader's bit
-                const int leader = __ffsll((unsigned long long)todo) - 1;
-                const u32 b = __shfl(my, leader);
-                const bool mine = my == b;  // (CHANGE_NONE lanes never equal a leader's key)
-                const u64 group = __ballot(mine);
-                todo &= ~group;
-                if ((group & (group - 1)) == 0) continue;
-                chains = true;
-                if (mine) {
-                    const u64 above = lane == 63 ? 0 : group & ~((2ULL << lane) - 1);
-                    if (above) nxt = (u32)__ffsll((unsigned long long)above) - 1;
-                    if ((int)lane != leader) adds = false;
-                }
-            }
-            if (chains) {
-                // v = the sum of the chain from this lane on: after step s it covers 2^(s+1) lanes.
-#pragma unroll
-                for (u32 s = 0; s < 6; s++) {
-                    const bool has = nxt != lane;
-                    const u128 o0 = tb_shfl128(v0, nxt), o1 = tb_shfl128(v1, nxt), o2 = tb_shfl128(v2, nxt);
-                    const u32 oc = __shfl(count, nxt);
-                    const u32 nn = __shfl(nxt, nxt);
-                    if (has) {
-                        v0 += o0, v1 += o1, v2 += o2, count += oc;
-                        nxt = nn == nxt ? lane : nn;
-                    }
-                }
-            }
+            tb_scan_combine<3>(lane, my, adds, v, count);
             if (!adds) continue;
             const u32 at = tb_change_bin_claim(s_tags, SERIES_LDS_BINS, my);
             u64* bin = at != CHANGE_NONE ? s_bins + at * SERIES_BIN_WORDS : bins + (u64)my * SERIES_BIN_WORDS;
-            u64* dst = bin + SERIES_SIDE_WORDS * side;
-            tb_atomic_add128(dst, v0);
-            tb_atomic_add128(dst + 2, v1);
-            tb_atomic_add128(dst + 4, v2);
+            u64* dst = bin + STATEMENT_SIDE_WORDS * side;
+            tb_atomic_add128(dst, v[0]);
+            tb_atomic_add128(dst + 2, v[1]);
+            tb_atomic_add128(dst + 4, v[2]);
             atomicAdd((unsigned long long*)(dst + 6), (unsigned long long)count);
         }
     }
@@ -187,10 +123,10 @@ __global__ __launch_bounds__(CHANGE_THREADS) void tb_series_effects(NodeTablesAr
         const u64* src = s_bins + b * SERIES_BIN_WORDS;
         u64* dst = bins + (u64)key * SERIES_BIN_WORDS;
         if (part < 6) {  // the six sums: three a side
-            const u32 o = SERIES_SIDE_WORDS * (part / 3) + 2 * (part % 3);
+            const u32 o = STATEMENT_SIDE_WORDS * (part / 3) + 2 * (part % 3);
             tb_atomic_add128(dst + o, tb_u128(src[o], src[o + 1]));
         } else {  // the two counts
-            const u32 o = SERIES_SIDE_WORDS * (part - 6) + 6;
+            const u32 o = STATEMENT_SIDE_WORDS * (part - 6) + 6;
             if (src[o]) atomicAdd((unsigned long long*)(dst + o), (unsigned long long)src[o]);
         }
     }
@@ -201,39 +137,16 @@ __global__ __launch_bounds__(CHANGE_THREADS) void tb_series_effects(NodeTablesAr
 __host__ __device__ static inline void tb_series_net(const u64* bin, u128 net[4]) {
 #pragma unroll
     for (u32 side = 0; side < 2; side++) {
-        const u64* z = bin + SERIES_SIDE_WORDS * side;
+        const u64* z = bin + STATEMENT_SIDE_WORDS * side;
         net[2 * side] = tb_u128(z[0], z[1]) - tb_u128(z[2], z[3]);
         net[2 * side + 1] = tb_u128(z[4], z[5]);
-    }
-}
-
-// One (account, bucket) row from the account's record, the bucket's bin (the sum of every engine's)
-// and the bucket's closing balances: tb_statement_row's 32 words and its arithmetic.  Device and host
-// alike: a node's host writes its rows with it.
-__host__ __device__ static inline void tb_series_row(const u64* account /* 128-B record */, const u64* bin, const u128 closing[4],
-                                                     u64* row) {
-    row[0] = account[0], row[1] = account[1];
-#pragma unroll
-    for (u32 side = 0; side < 2; side++) {
-        const u64* z = bin + SERIES_SIDE_WORDS * side;
-        const u128 pending_in = tb_u128(z[0], z[1]), pending_out = tb_u128(z[2], z[3]), posted_in = tb_u128(z[4], z[5]);
-        const u32 c = 2 * side;  // the side's *_pending column; c + 1: its *_posted
-        const u128 close_pending = closing[c], close_posted = closing[c + 1];
-        const u128 open_pending = close_pending - pending_in + pending_out, open_posted = close_posted - posted_in;
-        row[2 + 2 * c] = tb_lo(open_pending), row[3 + 2 * c] = tb_hi(open_pending);
-        row[4 + 2 * c] = tb_lo(open_posted), row[5 + 2 * c] = tb_hi(open_posted);
-        row[10 + 2 * c] = tb_lo(close_pending), row[11 + 2 * c] = tb_hi(close_pending);
-        row[12 + 2 * c] = tb_lo(close_posted), row[13 + 2 * c] = tb_hi(close_posted);
-#pragma unroll
-        for (u32 q = 0; q < 6; q++) row[18 + 6 * side + q] = z[q];
-        row[30 + side] = z[6];
     }
 }
 
 // Workgroup b writes rows [b, b + 1) * QUERY_THREADS; row g is bucket g % n_buckets of the found
 // account of rank g / n_buckets.  Every workgroup ranks the whole request for itself (at most 4,095
 // flags, 16 a thread, by ballots and one wave's scan of the 64 counts), so none waits for another.  A row's closing is the account's current balances
-// less the nets of its later buckets and the tail: lane (r, k) loads net(k + 1), a segmented suffix
+// (tb_flows_row's `closing`) less the nets of its later buckets and the tail: lane (r, k) loads net(k + 1), a segmented suffix
 // scan over the wave's lanes sums them within each account, the waves' heads carry across waves, and
 // what lies past the workgroup's last row — buckets of its last account only — is summed by all of
 // its threads together.  out: room for `cap` rows of STATEMENT_ROW_BYTES.
@@ -284,8 +197,8 @@ __global__ __launch_bounds__(QUERY_THREADS) void tb_series_emit(const u64* ids, 
         if (f && rank >= r0 && rank - r0 <= QUERY_THREADS) s_pos[rank - r0] = c * QUERY_THREADS + threadIdx.x;
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        res[SERIES_RES_MATCHED] = rows;
-        res[SERIES_RES_ORPHAN] = bins[(u64)n * stride * SERIES_BIN_WORDS];
+        res[SCAN_RES_MATCHED] = rows;
+        res[SCAN_RES_ORPHAN] = bins[(u64)n * stride * SERIES_BIN_WORDS];
     }
     __syncthreads();
     const u32 g = row0 + threadIdx.x;
@@ -368,7 +281,7 @@ __global__ __launch_bounds__(QUERY_THREADS) void tb_series_emit(const u64* ids, 
 #pragma unroll
     for (u32 c = 0; c < 4; c++) closing[c] = tb_u128(account[2 + 2 * c], account[3 + 2 * c]) - x[c];
     u64 row[32];
-    tb_series_row(account, bins + ((u64)index * stride + k) * SERIES_BIN_WORDS, closing, row);
+    tb_flows_row(account, bins + ((u64)index * stride + k) * SERIES_BIN_WORDS, closing, row);
     ulonglong2* dst = (ulonglong2*)(out + (u64)g * STATEMENT_ROW_BYTES);
 #pragma unroll
     for (u32 q = 0; q < 16; q++) dst[q] = make_ulonglong2(row[2 * q], row[2 * q + 1]);

@@ -11,6 +11,8 @@
 // sequencer's engine of a node is never asked.
 #pragma once
 
+#include "account_scan_host.h"
+
 // tbgpu_get_account_transfers and tbgpu_query_transfers (k_query.h; one scan, two predicates): every
 // buffer made at tbgpu_init, none shared with the write-back or the lookups (a write-back may be in
 // flight beside a query).
@@ -113,23 +115,29 @@ struct QueryManyBufs {
     u64 n = 0;                       // one batch in flight between query_many_enqueue and _collect
 };
 
-// tbgpu_lookup_accounts_at (k_asof.h): the request's ids, the set built from them, the bins, the
-// accounts' records and found flags, the answer and the result words; made by query_init and shared
-// with nothing.  Every word a query reads is a word it wrote, so tbgpu_reset clears none of them.
-struct LookupAtBufs {
-    u64* d_ids = nullptr;      // [ASOF_IDS_MAX][2] the request
+// One set of the account-set scan's buffers (k_account_scan.h; the driver is further down): the
+// request's ids, the set built from them, the bins, the accounts' records and found flags, the answer
+// and the result words; made by query_init and shared with nothing outside the family.  Every word a
+// query reads is a word it wrote, so tbgpu_reset clears none of them.  tbgpu_lookup_accounts_at has
+// its own (ql: 8,191 ids, 128-B records, 8-word bins); tbgpu_get_account_statements' (qt: 4,095 ids,
+// 256-B rows, 22-word bins) also serve the integrals and the series call, which are synchronous like
+// it and bring only their own bins.
+struct AccountScanBufs {
+    u64* d_ids = nullptr;      // [ids][2] the request
     u64* h_ids = nullptr;      // pinned: the caller's ids on their way up (a node copies them into every shard's)
-    u32* d_set = nullptr;      // [CHANGE_SET_SLOTS_MAX] the set's entries
-    u64* d_bins = nullptr;     // [ASOF_IDS_MAX + 1][BALANCE_SLOT_WORDS] the bins by request position, then the flag slot
-    u8* d_accounts = nullptr;  // [ASOF_IDS_MAX] the records as the owners hold them
-    u32* d_found = nullptr;    // [ASOF_IDS_MAX] 1: the position yields a record
-    u8* d_out = nullptr;       // [ASOF_IDS_MAX] the answer's records (one engine)
-    u64* d_res = nullptr;      // [ASOF_RES_WORDS]
+    u32* d_set = nullptr;      // [tb_change_set_slots(ids)] the set's entries
+    u64* d_bins = nullptr;     // the bins by request position, then the flag word
+    u8* d_accounts = nullptr;  // [ids] the records as the owners hold them
+    u32* d_found = nullptr;    // [ids] 1: the position yields a row
+    u8* d_out = nullptr;       // [ids] the answer's rows (one engine)
+    u64* d_res = nullptr;      // [SCAN_RES_WORDS]
     u64* h_res = nullptr;      // pinned mirror
     u64* h_bins = nullptr;     // pinned mirrors, read by a node's host only: it adds the shards' bins
     u8* h_accounts = nullptr;
     u32* h_found = nullptr;
 };
+#define ASOF_BIN_BYTES(n) (((u64)(n) + 1) * BALANCE_SLOT_WORDS * 8)  // the flag word has a slot of its own
+#define STATEMENT_BIN_BYTES(n) (((u64)(n) * STATEMENT_BIN_WORDS + 1) * 8)
 
 // tbgpu_get_ledger_balances (k_ledgers.h): the ledger set and the bins, on the device and pinned; made
 // by query_init and shared with nothing.  The host builds the set and writes the rows.
@@ -156,29 +164,9 @@ struct PendingBufs {
     u32* h_row_of = nullptr;  // pinned [PENDING_ROWS_MAX] the row an index stands for
 };
 
-// tbgpu_get_account_statements (k_statement.h): lookup_accounts_at's buffers at this call's sizes — the
-// request's ids, the set, the bins of STATEMENT_BIN_WORDS, the accounts' records and found flags, the
-// answer's rows and the result words; made by query_init and shared with nothing.  Every word a query
-// reads is a word it wrote, so tbgpu_reset clears none of them.
-struct StatementBufs {
-    u64* d_ids = nullptr;      // [STATEMENT_IDS_MAX][2] the request
-    u64* h_ids = nullptr;      // pinned: the caller's ids on their way up (a node copies them into every shard's)
-    u32* d_set = nullptr;      // [tb_change_set_slots(STATEMENT_IDS_MAX)] the set's entries
-    u64* d_bins = nullptr;     // [STATEMENT_IDS_MAX][STATEMENT_BIN_WORDS] the bins by request position, then the flag word
-    u8* d_accounts = nullptr;  // [STATEMENT_IDS_MAX] the records as the owners hold them
-    u32* d_found = nullptr;    // [STATEMENT_IDS_MAX] 1: the position yields a row
-    u8* d_out = nullptr;       // [STATEMENT_IDS_MAX] the answer's rows (one engine)
-    u64* d_res = nullptr;      // [STATEMENT_RES_WORDS]
-    u64* h_res = nullptr;      // pinned mirror
-    u64* h_bins = nullptr;     // pinned mirrors, read by a node's host only: it adds the shards' bins
-    u8* h_accounts = nullptr;
-    u32* h_found = nullptr;
-};
-#define STATEMENT_BIN_BYTES(n) (((u64)(n) * STATEMENT_BIN_WORDS + 1) * 8)
-
 // tbgpu_get_account_balance_integrals (k_integral.h): the same request, set, records, flags, rows and
-// result words as a statements call, at the same sizes, and both calls are synchronous — it works in
-// StatementBufs.  Only its bins are wider (INTEGRAL_BIN_WORDS), so they are its own.
+// result words as a statements call, at the same sizes — it works in QueryState::qt.  Only its bins are
+// wider (INTEGRAL_BIN_WORDS), so they are its own.
 struct IntegralBufs {
     u64* d_bins = nullptr;  // [INTEGRAL_IDS_MAX][INTEGRAL_BIN_WORDS] the bins by request position, then the flag word
     u64* h_bins = nullptr;  // pinned mirror, read by a node's host only: it adds the shards' bins
@@ -186,7 +174,7 @@ struct IntegralBufs {
 #define INTEGRAL_BIN_BYTES(n) (((u64)(n) * INTEGRAL_BIN_WORDS + 1) * 8)
 
 // tbgpu_get_account_statement_series (k_series.h): a statements call's request, set, records, flags,
-// rows and result words (StatementBufs: n * n_buckets rows are at most STATEMENT_IDS_MAX), its own
+// rows and result words (QueryState::qt: n * n_buckets rows are at most STATEMENT_IDS_MAX), its own
 // bounds and its own bins, one per key.
 struct SeriesBufs {
     u64* d_bounds = nullptr;  // [SERIES_ROWS_MAX + 1] the request's bounds
@@ -203,13 +191,30 @@ struct QueryState {
     AccountQueryBufs qa;
     ChangeBufs qc;
     QueryManyBufs qm;
-    LookupAtBufs ql;
+    AccountScanBufs ql;
     LedgerBufs qg;
     PendingBufs qp;
-    StatementBufs qt;
+    AccountScanBufs qt;
     IntegralBufs qi;
     SeriesBufs qr;
 };
+
+// One AccountScanBufs for `ids` request ids: in this order, which tests/test_gpu_alloc.py counts by.
+static int account_scan_bufs_init(tbgpu* E, AccountScanBufs& B, u64 ids, u64 set_slots, u64 bin_bytes, u64 row_bytes) {
+    HIPCK(tbMalloc(E->own, &B.d_ids, ids * 16));
+    HIPCK(tbHostMalloc(E->own, &B.h_ids, ids * 16, hipHostMallocDefault));
+    HIPCK(tbMalloc(E->own, &B.d_set, set_slots * 4));
+    HIPCK(tbMalloc(E->own, &B.d_bins, bin_bytes));
+    HIPCK(tbMalloc(E->own, &B.d_accounts, ids * 128));
+    HIPCK(tbMalloc(E->own, &B.d_found, ids * 4));
+    HIPCK(tbMalloc(E->own, &B.d_out, ids * row_bytes));
+    HIPCK(tbMalloc(E->own, &B.d_res, SCAN_RES_WORDS * 8));
+    HIPCK(tbHostMalloc(E->own, &B.h_res, SCAN_RES_WORDS * 8, hipHostMallocDefault));
+    HIPCK(tbHostMalloc(E->own, &B.h_bins, bin_bytes, hipHostMallocDefault));
+    HIPCK(tbHostMalloc(E->own, &B.h_accounts, ids * 128, hipHostMallocDefault));
+    HIPCK(tbHostMalloc(E->own, &B.h_found, ids * 4, hipHostMallocDefault));
+    return TBGPU_STATUS_OK;
+}
 
 // Called by engine_init on the engine's device, after every other buffer.  The buffers go into the
 // engine's owner, which releases as many as were made; query_free deletes the host struct only.
@@ -288,22 +293,8 @@ static int query_init(tbgpu* E) {
         HIPCK(tbHostMalloc(E->own, &M.h_stage, (u64)QUERY_MANY_STAGE * 128, hipHostMallocDefault));
         HIPCK(tbMalloc(E->own, &M.d_out, (u64)QUERY_MANY_FILTERS * BATCH_EVENTS_MAX * 128));
     }
-    {  // tbgpu_lookup_accounts_at: the ids, the set, the bins, the accounts, the answer, the result words
-        LookupAtBufs& L = E->qs->ql;
-        const u64 ni = ASOF_IDS_MAX, bin_bytes = (ni + 1) * BALANCE_SLOT_WORDS * 8;
-        HIPCK(tbMalloc(E->own, &L.d_ids, ni * 16));
-        HIPCK(tbHostMalloc(E->own, &L.h_ids, ni * 16, hipHostMallocDefault));
-        HIPCK(tbMalloc(E->own, &L.d_set, (u64)CHANGE_SET_SLOTS_MAX * 4));
-        HIPCK(tbMalloc(E->own, &L.d_bins, bin_bytes));
-        HIPCK(tbMalloc(E->own, &L.d_accounts, ni * 128));
-        HIPCK(tbMalloc(E->own, &L.d_found, ni * 4));
-        HIPCK(tbMalloc(E->own, &L.d_out, ni * 128));
-        HIPCK(tbMalloc(E->own, &L.d_res, ASOF_RES_WORDS * 8));
-        HIPCK(tbHostMalloc(E->own, &L.h_res, ASOF_RES_WORDS * 8, hipHostMallocDefault));
-        HIPCK(tbHostMalloc(E->own, &L.h_bins, bin_bytes, hipHostMallocDefault));
-        HIPCK(tbHostMalloc(E->own, &L.h_accounts, ni * 128, hipHostMallocDefault));
-        HIPCK(tbHostMalloc(E->own, &L.h_found, ni * 4, hipHostMallocDefault));
-    }
+    // tbgpu_lookup_accounts_at: the ids, the set, the bins, the accounts, the answer, the result words
+    if (const int st = account_scan_bufs_init(E, E->qs->ql, ASOF_IDS_MAX, CHANGE_SET_SLOTS_MAX, ASOF_BIN_BYTES(ASOF_IDS_MAX), 128)) return st;
     {  // tbgpu_get_ledger_balances: the set and the bins
         LedgerBufs& G = E->qs->qg;
         const u64 bin_bytes = LEDGER_BINS(LEDGER_SET_SLOTS_MAX) * LEDGER_BIN_WORDS * 8;
@@ -326,21 +317,10 @@ static int query_init(tbgpu* E) {
         HIPCK(tbHostMalloc(E->own, &P.h_slots, nr * 128, hipHostMallocDefault));
         HIPCK(tbHostMalloc(E->own, &P.h_row_of, nr * 4, hipHostMallocDefault));
     }
-    {  // tbgpu_get_account_statements: the ids, the set, the bins, the accounts, the rows, the result words
-        StatementBufs& S = E->qs->qt;
-        const u64 ni = STATEMENT_IDS_MAX, bin_bytes = STATEMENT_BIN_BYTES(ni);
-        HIPCK(tbMalloc(E->own, &S.d_ids, ni * 16));
-        HIPCK(tbHostMalloc(E->own, &S.h_ids, ni * 16, hipHostMallocDefault));
-        HIPCK(tbMalloc(E->own, &S.d_set, (u64)tb_change_set_slots(STATEMENT_IDS_MAX) * 4));
-        HIPCK(tbMalloc(E->own, &S.d_bins, bin_bytes));
-        HIPCK(tbMalloc(E->own, &S.d_accounts, ni * 128));
-        HIPCK(tbMalloc(E->own, &S.d_found, ni * 4));
-        HIPCK(tbMalloc(E->own, &S.d_out, ni * STATEMENT_ROW_BYTES));
-        HIPCK(tbMalloc(E->own, &S.d_res, STATEMENT_RES_WORDS * 8));
-        HIPCK(tbHostMalloc(E->own, &S.h_res, STATEMENT_RES_WORDS * 8, hipHostMallocDefault));
-        HIPCK(tbHostMalloc(E->own, &S.h_bins, bin_bytes, hipHostMallocDefault));
-        HIPCK(tbHostMalloc(E->own, &S.h_accounts, ni * 128, hipHostMallocDefault));
-        HIPCK(tbHostMalloc(E->own, &S.h_found, ni * 4, hipHostMallocDefault));
+    // tbgpu_get_account_statements: the ids, the set, the bins, the accounts, the rows, the result words
+    if (const int st = account_scan_bufs_init(E, E->qs->qt, STATEMENT_IDS_MAX, tb_change_set_slots(STATEMENT_IDS_MAX),
+                                              STATEMENT_BIN_BYTES(STATEMENT_IDS_MAX), STATEMENT_ROW_BYTES)) {
+        return st;
     }
     {  // tbgpu_get_account_balance_integrals: its bins; the rest is the statements call's
         IntegralBufs& I = E->qs->qi;
@@ -1231,541 +1211,341 @@ extern "C" int tbgpu_get_change_events(tbgpu_t* E, const tbgpu_change_events_fil
     return query_end(result, st);
 }
 
-// ---- lookup_accounts_at (k_asof.h, include/tbgpu.h) -----------------------------------------------
-// One engine: ids up, set and bins zeroed, gather -> tb_change_effects -> emit on the engine stream,
-// the result words back; one wait; then the answer's count * 128 bytes.  The set has
-// get_change_events' slots for as many accounts as the request has ids (tb_change_set_slots); a
-// workgroup of the scan keeps it in LDS as it is up to 4,096 ids (at most 8,192 slots) and narrowed to
-// 16-bit entries above (16,384 slots), either way beside ASOF_LDS_BINS claimed bins.
-// T = 0 asks for the records as they are: no set, no scan.
-// A node: every shard gathers (each builds the same set: an id's index is its smallest request
-// position, whatever the order of the inserts; the records come from the owners' tables, as
-// tb_change_gather reads them) and scans its own log on its own device and stream, side by side; the
-// host adds the shards' bins and writes the records.
-static int lookup_at_enqueue(tbgpu* E, const NodeTablesArgs& NT, u32 self, u32 n, u64 T, bool scan, bool emit, u32 cap) {
-    LookupAtBufs& L = E->qs->ql;
-    HIPCK(hipSetDevice(E->device));
-    const u32 slots = tb_change_set_slots(n), mask = slots - 1;
-    const bool narrow = slots > CHANGE_LDS_BINS_SLOTS_MAX;  // 16-bit entries in LDS: the bins keep their room
-    const u64 bin_bytes = ((u64)n + 1) * BALANCE_SLOT_WORDS * 8;
-    const unsigned nb_ids = (n + QUERY_THREADS - 1) / QUERY_THREADS;
-    HIPCK(hipMemcpyAsync(L.d_ids, L.h_ids, (u64)n * 16, hipMemcpyHostToDevice, E->stream));
-    if (scan) {
-        HIPCK(hipMemsetAsync(L.d_set, 0, (u64)slots * 4, E->stream));
-        HIPCK(hipMemsetAsync(L.d_bins, 0, bin_bytes, E->stream));
-    }
-    const bool store = emit || self == 0;  // a node reads the first shard's records only
-    hipLaunchKernelGGL(tb_asof_gather, dim3(nb_ids), dim3(QUERY_THREADS), 0, E->stream, NT, (const u64*)L.d_ids, n, T,
-                       store ? L.d_accounts : nullptr, store ? L.d_found : nullptr, scan ? L.d_set : nullptr, mask);
-    HIPCK(hipGetLastError());
-    const u64 records = E->log_next, per = (u64)CHANGE_THREADS * CHANGE_TILES, nb = (records + per - 1) / per;
-    if (scan && nb) {
-        const size_t lds = (size_t)slots * (narrow ? 2 : 4) + (size_t)ASOF_LDS_BINS * (BALANCE_SLOT_WORDS * 8 + 4);
-        if (narrow) {
-            hipLaunchKernelGGL((tb_change_effects<u16, true>), dim3((unsigned)nb), dim3(CHANGE_THREADS), lds, E->stream, NT, self,
-                               records, T, (const u32*)L.d_set, mask, (const u64*)L.d_ids, n, L.d_bins, ASOF_LDS_BINS);
-        } else {
-            hipLaunchKernelGGL((tb_change_effects<u32, true>), dim3((unsigned)nb), dim3(CHANGE_THREADS), lds, E->stream, NT, self,
-                               records, T, (const u32*)L.d_set, mask, (const u64*)L.d_ids, n, L.d_bins, ASOF_LDS_BINS);
-        }
-        HIPCK(hipGetLastError());
-    }
-    if (emit) {
-        hipLaunchKernelGGL(tb_asof_emit, dim3(nb_ids), dim3(QUERY_THREADS), 0, E->stream, (const u64*)L.d_ids, n,
-                           (const u8*)L.d_accounts, (const u32*)L.d_found, scan ? (const u32*)L.d_set : nullptr, mask,
-                           scan ? (const u64*)L.d_bins : nullptr, cap, L.d_out, L.d_res);
-        HIPCK(hipGetLastError());
-        HIPCK(hipMemcpyAsync(L.h_res, L.d_res, ASOF_RES_WORDS * 8, hipMemcpyDeviceToHost, E->stream));
-        return TBGPU_STATUS_OK;
-    }
-    if (scan) HIPCK(hipMemcpyAsync(L.h_bins, L.d_bins, bin_bytes, hipMemcpyDeviceToHost, E->stream));
-    if (self == 0) {
-        HIPCK(hipMemcpyAsync(L.h_accounts, L.d_accounts, (u64)n * 128, hipMemcpyDeviceToHost, E->stream));
-        HIPCK(hipMemcpyAsync(L.h_found, L.d_found, (u64)n * 4, hipMemcpyDeviceToHost, E->stream));
-    }
-    return TBGPU_STATUS_OK;
-}
+// ---- the account-set scan (k_account_scan.h; k_asof.h, k_statement.h, k_integral.h, k_series.h) ----
+// lookup_accounts_at, get_account_statements, get_account_balance_integrals and
+// get_account_statement_series through one driver.  One engine: ids up, set and bins zeroed,
+// tb_asof_gather -> the call's scan -> the call's emit on the engine stream, the result words back; one
+// wait; then the answer's count rows.  The set has get_change_events' slots for as many accounts as
+// the request has ids (tb_change_set_slots).  A node: every shard gathers (each builds the same set:
+// an id's index is its smallest request position, whatever the order of the inserts; the records come
+// from the owners' tables, as tb_change_gather reads them) and scans its own log on its own device
+// and stream, side by side; the host adds the shards' bins (account_scan_host.h) and writes the rows
+// with the call's row function.  An entry point describes its call in an AccountScan and owns
+// nothing else but its validity test.
 
-// A node's answer from its shards' pinned mirrors: the found positions in request order, each with the
-// balances less every shard's bin of its id (the bin of the smallest position that names the id).
-static void lookup_at_node_records(const QueryCall& c, u32 n, bool scan, u32 cap, u8* out, tbgpu_query_result* result) {
-    const LookupAtBufs& L = c.Es[0]->qs->ql;
-    std::vector<u32> index(n);
-    if (scan) {
-        std::vector<u32> order(n);
-        std::iota(order.begin(), order.end(), 0u);
-        auto id_of = [&](u32 i) { return std::make_pair(L.h_ids[2 * (u64)i + 1], L.h_ids[2 * (u64)i]); };
-        std::sort(order.begin(), order.end(), [&](u32 a, u32 b) { return id_of(a) != id_of(b) ? id_of(a) < id_of(b) : a < b; });
-        for (u32 j = 0; j < n; j++) index[order[j]] = j && id_of(order[j - 1]) == id_of(order[j]) ? index[order[j - 1]] : order[j];
-    }
-    u32 m = 0, written = 0;
-    for (u32 i = 0; i < n; i++) {
-        if (!L.h_found[i]) continue;
-        if (m++ >= cap) continue;
-        u8* rec = out + (u64)written++ * 128;
-        memcpy(rec, L.h_accounts + (u64)i * 128, 128);
-        if (!scan) continue;
-        u128 bal[4];
-        memcpy(bal, rec + 16, sizeof bal);
-        for (u32 d = 0; d < c.world; d++) {
-            const u128* bins = (const u128*)c.Es[d]->qs->ql.h_bins + (u64)index[i] * 4;
-            for (u32 col = 0; col < 4; col++) bal[col] -= bins[col];
-        }
-        memcpy(rec + 16, bal, sizeof bal);
-    }
-    if (scan) {
-        for (u32 d = 0; d < c.world; d++) {
-            if (c.Es[d]->qs->ql.h_bins[(u64)n * BALANCE_SLOT_WORDS + CHANGE_FLAG_ORPHAN]) result->complete = 0;
-        }
-    }
-    result->count = written;
-    result->matched = m;
-}
+// What a call's launch callables get: one engine's part of the call.
+struct ScanLaunch {
+    tbgpu* E;
+    const NodeTablesArgs& NT;
+    u32 self;
+    u64 records;  // the log's end
+    unsigned nb;  // the scan's workgroups
+    u32 slots, mask;
+    AccountScanBufs& B;
+    u64* d_bins;
+    u32 cap;
+};
+struct ScanBins {
+    u64 *d, *h;
+};
 
-extern "C" int tbgpu_lookup_accounts_at(tbgpu_t* E, uint64_t timestamp, const void* ids, uint32_t n, void* out,
-                                        uint32_t out_cap_records, tbgpu_query_result* result) {
-    API_ENTER(E, false);
-    if (n > TBGPU_LOOKUP_AT_MAX) return fail(TBGPU_STATUS_INVALID, "lookup_accounts_at: %u ids (at most %u)", n, TBGPU_LOOKUP_AT_MAX);
-    if (n == 0) return TBGPU_STATUS_OK;
-    if (!ids || !out || !result) return fail(TBGPU_STATUS_INVALID, "lookup_accounts_at: NULL ids, out or result");
-    QueryCall c;
+struct AccountScan {
+    const char* name;                   // in messages
+    const char* unit;                   // what the call returns, in the panic message
+    std::string asked;                  // what it was asked for, likewise
+    AccountScanBufs QueryState::*bufs;  // the ids, set, records, flags, out and res
+    ScanBins (*bins)(QueryState&);      // the bins and their pinned mirror
+    u32 n;                              // request ids
+    u64 T;                              // tb_asof_gather's T
+    bool scan;           // false: the records as they are — no set, no scan, no bins, and a node asks its first shard only
+    u64 bin_bytes;       // the request's bins and their flag word
+    u64 flag_word;       // the orphan flag's word in the bins
+    const ScanBinRun* layout;  // a bin's sums, for a node's adder
+    u32 n_runs;
+    u32 keys_per_id;     // consecutive bins of one id
+    u32 row_bytes;
+    u32 rows_per_id;     // `matched` is at most n * rows_per_id
+    std::function<int(const ScanLaunch&)> launch_scan, launch_emit;
+};
+
+#define SCAN_ANSWERED (-1)  // account_scan_begin: nothing to ask, the result stands as it is
+
+// What every entry point does before it describes its call (after API_ENTER): the checks, the zeroed
+// result, the engine list, `valid()` — false: the zeroed result is the answer — every engine drained,
+// the tables, the ids into every shard's pinned buffer.
+template <typename VALID>
+static int account_scan_begin(tbgpu* E, const char* name, AccountScanBufs QueryState::*bufs, u32 n, u32 n_max, const void* ids,
+                              const void* out, tbgpu_query_result* result, QueryCall* c, NodeTablesArgs* NT, VALID valid) {
+    if (n > n_max) return fail(TBGPU_STATUS_INVALID, "%s: %u ids (at most %u)", name, n, n_max);
+    if (n == 0) return SCAN_ANSWERED;
+    if (!ids || !out || !result) return fail(TBGPU_STATUS_INVALID, "%s: NULL ids, out or result", name);
     result->count = 0;
     result->matched = 0;
-    result->complete = query_engines(E, true, &c);
-    if (timestamp == ~0ULL) return TBGPU_STATUS_OK;
-    const bool scan = timestamp != 0, one = c.world == 1;
-    NodeTablesArgs NT{};
-    NT.world = c.world;
-    for (u32 d = 0; d < c.world; d++) NT.T[d] = c.Es[d]->T;
+    result->complete = query_engines(E, true, c);
+    if (!valid()) return SCAN_ANSWERED;
+    *NT = NodeTablesArgs{};
+    NT->world = c->world;
+    for (u32 d = 0; d < c->world; d++) NT->T[d] = c->Es[d]->T;
     // Every engine is drained before any is asked: a gather reads the owners' tables and a scan its
     // posts' pending transfers on their homes.
-    for (u32 d = 0; d < c.world; d++) {
-        HIPCK(hipSetDevice(c.Es[d]->device));
-        if (c.Es[d]->pending) {
-            const int st = engine_sync(c.Es[d]);
+    for (u32 d = 0; d < c->world; d++) {
+        HIPCK(hipSetDevice(c->Es[d]->device));
+        if (c->Es[d]->pending) {
+            const int st = engine_sync(c->Es[d]);
             if (st) return query_end(result, st);
         }
     }
-    memcpy(c.Es[0]->qs->ql.h_ids, ids, (u64)n * 16);
-    // Without a scan nothing is summed: a node's first shard gathers alone.
-    const u32 asked = scan ? c.world : 1;
-    int st = query_side_by_side(c.Es, asked, [&](u32 d) -> int {
-        if (d) memcpy(c.Es[d]->qs->ql.h_ids, c.Es[0]->qs->ql.h_ids, (u64)n * 16);
-        return lookup_at_enqueue(c.Es[d], NT, d, n, timestamp, scan, one, out_cap_records);
-    });
-    if (st) return query_end(result, st);
-    if (!one) {
-        lookup_at_node_records(c, n, scan, out_cap_records, (u8*)out, result);
-        return TBGPU_STATUS_OK;
-    }
-    tbgpu* S = c.Es[0];
-    const LookupAtBufs& L = S->qs->ql;
-    const u64 matched = L.h_res[ASOF_RES_MATCHED];
-    const u32 m = (u32)std::min<u64>(matched, out_cap_records);
-    if (matched > n) return query_end(result, fail(TBGPU_STATUS_PANIC, "lookup_accounts_at: %llu records for %u ids", (unsigned long long)matched, n));
-    if (m) {
-        HIPCK(hipMemcpyAsync(out, L.d_out, (u64)m * 128, hipMemcpyDeviceToHost, S->stream));
-        HIPCK(hipStreamSynchronize(S->stream));
-    }
-    if (L.h_res[ASOF_RES_ORPHAN]) result->complete = 0;
-    result->count = m;
-    result->matched = matched;
+    for (u32 d = 0; d < c->world; d++) memcpy((c->Es[d]->qs->*bufs).h_ids, ids, (u64)n * 16);
     return TBGPU_STATUS_OK;
 }
 
-// ---- get_account_statements (k_statement.h, include/tbgpu.h) --------------------------------------
-// lookup_accounts_at's shape with T = t_close and a scan of its own.  One engine: ids up, set and bins
-// zeroed, tb_asof_gather -> tb_statement_effects -> tb_statement_emit on the engine stream, the result
-// words back; one wait; then the answer's count * 256 bytes.  The scan always runs: t_close = 0 has
-// nothing above it, but the period's sums are the log's.  The set has at most 8,192 slots and stays
-// 32-bit in LDS beside STATEMENT_LDS_BINS claimed bins.
-// A node: every shard gathers (each builds the same set) and scans its own log on its own device and
-// stream, side by side; the host adds the shards' bins and writes the rows (tb_statement_row).
-static int statements_enqueue(tbgpu* E, const NodeTablesArgs& NT, u32 self, u32 n, u64 t_open, u64 t_close, bool emit, u32 cap) {
-    StatementBufs& S = E->qs->qt;
+static int account_scan_enqueue(tbgpu* E, const AccountScan& s, const NodeTablesArgs& NT, u32 self, bool emit, u32 cap) {
+    AccountScanBufs& B = E->qs->*s.bufs;
+    const ScanBins bins = s.bins(*E->qs);
     HIPCK(hipSetDevice(E->device));
-    const u32 slots = tb_change_set_slots(n), mask = slots - 1;
-    const u64 bin_bytes = STATEMENT_BIN_BYTES(n);
+    const u32 n = s.n, slots = tb_change_set_slots(n), mask = slots - 1;
     const unsigned nb_ids = (n + QUERY_THREADS - 1) / QUERY_THREADS;
-    HIPCK(hipMemcpyAsync(S.d_ids, S.h_ids, (u64)n * 16, hipMemcpyHostToDevice, E->stream));
-    HIPCK(hipMemsetAsync(S.d_set, 0, (u64)slots * 4, E->stream));
-    HIPCK(hipMemsetAsync(S.d_bins, 0, bin_bytes, E->stream));
+    HIPCK(hipMemcpyAsync(B.d_ids, B.h_ids, (u64)n * 16, hipMemcpyHostToDevice, E->stream));
+    if (s.scan) {
+        HIPCK(hipMemsetAsync(B.d_set, 0, (u64)slots * 4, E->stream));
+        HIPCK(hipMemsetAsync(bins.d, 0, s.bin_bytes, E->stream));
+    }
     const bool store = emit || self == 0;  // a node reads the first shard's records only
-    hipLaunchKernelGGL(tb_asof_gather, dim3(nb_ids), dim3(QUERY_THREADS), 0, E->stream, NT, (const u64*)S.d_ids, n, t_close,
-                       store ? S.d_accounts : nullptr, store ? S.d_found : nullptr, S.d_set, mask);
+    hipLaunchKernelGGL(tb_asof_gather, dim3(nb_ids), dim3(QUERY_THREADS), 0, E->stream, NT, (const u64*)B.d_ids, n, s.T,
+                       store ? B.d_accounts : nullptr, store ? B.d_found : nullptr, s.scan ? B.d_set : nullptr, mask);
     HIPCK(hipGetLastError());
     const u64 records = E->log_next, per = (u64)CHANGE_THREADS * CHANGE_TILES, nb = (records + per - 1) / per;
-    if (nb) {
-        const size_t lds = (size_t)slots * 4 + (size_t)STATEMENT_LDS_BINS * (STATEMENT_BIN_WORDS * 8 + 4);
-        hipLaunchKernelGGL(tb_statement_effects, dim3((unsigned)nb), dim3(CHANGE_THREADS), lds, E->stream, NT, self, records, t_open,
-                           t_close, (const u32*)S.d_set, mask, (const u64*)S.d_ids, n, S.d_bins);
+    const ScanLaunch L{E, NT, self, records, (unsigned)nb, slots, mask, B, bins.d, cap};
+    if (s.scan && nb) {
+        if (const int st = s.launch_scan(L)) return st;
         HIPCK(hipGetLastError());
     }
     if (emit) {
-        hipLaunchKernelGGL(tb_statement_emit, dim3(nb_ids), dim3(QUERY_THREADS), 0, E->stream, (const u64*)S.d_ids, n,
-                           (const u8*)S.d_accounts, (const u32*)S.d_found, (const u32*)S.d_set, mask, (const u64*)S.d_bins, cap,
-                           S.d_out, S.d_res);
+        if (const int st = s.launch_emit(L)) return st;
         HIPCK(hipGetLastError());
-        HIPCK(hipMemcpyAsync(S.h_res, S.d_res, STATEMENT_RES_WORDS * 8, hipMemcpyDeviceToHost, E->stream));
+        HIPCK(hipMemcpyAsync(B.h_res, B.d_res, SCAN_RES_WORDS * 8, hipMemcpyDeviceToHost, E->stream));
         return TBGPU_STATUS_OK;
     }
-    HIPCK(hipMemcpyAsync(S.h_bins, S.d_bins, bin_bytes, hipMemcpyDeviceToHost, E->stream));
+    if (s.scan) HIPCK(hipMemcpyAsync(bins.h, bins.d, s.bin_bytes, hipMemcpyDeviceToHost, E->stream));
     if (self == 0) {
-        HIPCK(hipMemcpyAsync(S.h_accounts, S.d_accounts, (u64)n * 128, hipMemcpyDeviceToHost, E->stream));
-        HIPCK(hipMemcpyAsync(S.h_found, S.d_found, (u64)n * 4, hipMemcpyDeviceToHost, E->stream));
+        HIPCK(hipMemcpyAsync(B.h_accounts, B.d_accounts, (u64)n * 128, hipMemcpyDeviceToHost, E->stream));
+        HIPCK(hipMemcpyAsync(B.h_found, B.d_found, (u64)n * 4, hipMemcpyDeviceToHost, E->stream));
     }
     return TBGPU_STATUS_OK;
 }
 
 // A node's answer from its shards' pinned mirrors: the found positions in request order, each from
-// its record and the sum of every shard's bin of its id (the bin of the smallest position that names
-// the id).  The bins' words add as the device added them: the 128-bit sums with their carry, the
-// counts as they are.
-static void statements_node_rows(const QueryCall& c, u32 n, u32 cap, u8* out, tbgpu_query_result* result) {
-    const StatementBufs& S = c.Es[0]->qs->qt;
-    std::vector<u32> index(n), order(n);
-    std::iota(order.begin(), order.end(), 0u);
-    auto id_of = [&](u32 i) { return std::make_pair(S.h_ids[2 * (u64)i + 1], S.h_ids[2 * (u64)i]); };
-    std::sort(order.begin(), order.end(), [&](u32 a, u32 b) { return id_of(a) != id_of(b) ? id_of(a) < id_of(b) : a < b; });
-    for (u32 j = 0; j < n; j++) index[order[j]] = j && id_of(order[j - 1]) == id_of(order[j]) ? index[order[j - 1]] : order[j];
-    u32 m = 0, written = 0;
-    for (u32 i = 0; i < n; i++) {
-        if (!S.h_found[i]) continue;
-        if (m++ >= cap) continue;
-        u64 bin[STATEMENT_BIN_WORDS] = {};
-        for (u32 d = 0; d < c.world; d++) {
-            const u64* b = c.Es[d]->qs->qt.h_bins + (u64)index[i] * STATEMENT_BIN_WORDS;
-            for (u32 w = 0; w < STATEMENT_BIN_WORDS;) {
-                const bool count = w >= STATEMENT_ZONE1 && (w - STATEMENT_ZONE1) % STATEMENT_SIDE_WORDS == 6;
-                if (count) {
-                    bin[w] += b[w];
-                    w += 1;
-                } else {
-                    const u128 v = tb_u128(bin[w], bin[w + 1]) + tb_u128(b[w], b[w + 1]);
-                    bin[w] = tb_lo(v), bin[w + 1] = tb_hi(v);
-                    w += 2;
-                }
-            }
+// its record and the sum of every shard's bins of its id (null without a scan).  `rows(account, bins,
+// first, out)` writes the position's rows — `first` is the first of them, and below `cap` — under the
+// caller's room and returns how many it wrote.
+template <typename ROWS>
+static void account_scan_node_rows(const QueryCall& c, const AccountScan& s, u32 cap, u8* out, tbgpu_query_result* result, ROWS rows) {
+    const AccountScanBufs& B = c.Es[0]->qs->*s.bufs;
+    const u64 id_words = (u64)s.keys_per_id * scan_bin_words(s.layout, s.n_runs);
+    std::vector<u32> index;
+    if (s.scan) index = scan_first_positions(B.h_ids, s.n);
+    std::vector<u64> sum(s.scan ? id_words : 0);
+    u64 m = 0;
+    u32 written = 0;
+    for (u32 i = 0; i < s.n; i++) {
+        if (!B.h_found[i]) continue;
+        const u64 first = m;
+        m += s.rows_per_id;
+        if (first >= cap) continue;
+        std::fill(sum.begin(), sum.end(), 0);
+        for (u32 d = 0; d < c.world && s.scan; d++) {
+            scan_bins_add(sum.data(), s.bins(*c.Es[d]->qs).h + index[i] * id_words, s.layout, s.n_runs, s.keys_per_id);
         }
-        u64 row[STATEMENT_ROW_BYTES / 8];
-        tb_statement_row((const u64*)(S.h_accounts + (u64)i * 128), bin, row);
-        memcpy(out + (u64)written++ * STATEMENT_ROW_BYTES, row, sizeof row);
+        written += rows((const u64*)(B.h_accounts + (u64)i * 128), s.scan ? sum.data() : nullptr, first, out);
     }
-    for (u32 d = 0; d < c.world; d++) {
-        if (c.Es[d]->qs->qt.h_bins[(u64)n * STATEMENT_BIN_WORDS]) result->complete = 0;
+    for (u32 d = 0; d < c.world && s.scan; d++) {
+        if (s.bins(*c.Es[d]->qs).h[s.flag_word]) result->complete = 0;
     }
     result->count = written;
     result->matched = m;
 }
 
+// One engine's answer: the result words are back, the rows follow.
+static int account_scan_finish(tbgpu* E, const AccountScan& s, u32 cap, void* out, tbgpu_query_result* result) {
+    const AccountScanBufs& B = E->qs->*s.bufs;
+    const u64 matched = B.h_res[SCAN_RES_MATCHED];
+    const u32 m = (u32)std::min<u64>(matched, cap);
+    if (matched > (u64)s.n * s.rows_per_id) {
+        return query_end(result, fail(TBGPU_STATUS_PANIC, "%s: %llu %s for %s", s.name, (unsigned long long)matched, s.unit, s.asked.c_str()));
+    }
+    if (m) {
+        HIPCK(hipMemcpyAsync(out, B.d_out, (u64)m * s.row_bytes, hipMemcpyDeviceToHost, E->stream));
+        HIPCK(hipStreamSynchronize(E->stream));
+    }
+    if (B.h_res[SCAN_RES_ORPHAN]) result->complete = 0;
+    result->count = m;
+    result->matched = matched;
+    return TBGPU_STATUS_OK;
+}
+
+template <typename ROWS>
+static int account_scan_run(const QueryCall& c, const AccountScan& s, const NodeTablesArgs& NT, u32 cap, void* out,
+                            tbgpu_query_result* result, ROWS rows) {
+    const bool one = c.world == 1;
+    const u32 asked = s.scan ? c.world : 1;  // without a scan nothing is summed: a node's first shard gathers alone
+    const int st = query_side_by_side(c.Es, asked, [&](u32 d) -> int { return account_scan_enqueue(c.Es[d], s, NT, d, one, cap); });
+    if (st) return query_end(result, st);
+    if (one) return account_scan_finish(c.Es[0], s, cap, out, result);
+    account_scan_node_rows(c, s, cap, (u8*)out, result, rows);
+    return TBGPU_STATUS_OK;
+}
+
+// lookup_accounts_at (k_asof.h).  Its own: T = 0 asks for the records as they are, without a scan; the
+// scan is tb_change_effects with claimed bins, and a workgroup keeps the set in LDS as it is up to
+// 4,096 ids (at most 8,192 slots) and narrowed to 16-bit entries above (16,384 slots), either way
+// beside ASOF_LDS_BINS claimed bins.
+static constexpr ScanBinRun ASOF_BIN_LAYOUT[] = {{2, 4}};
+extern "C" int tbgpu_lookup_accounts_at(tbgpu_t* E, uint64_t timestamp, const void* ids, uint32_t n, void* out,
+                                        uint32_t out_cap_records, tbgpu_query_result* result) {
+    static_assert(ASOF_IDS_MAX == TBGPU_LOOKUP_AT_MAX && scan_bin_words(ASOF_BIN_LAYOUT, 1) == BALANCE_SLOT_WORDS,
+                  "k_asof.h's constants are the header's");
+    static_assert((size_t)CHANGE_SET_SLOTS_MAX * 2 + (size_t)ASOF_LDS_BINS * (BALANCE_SLOT_WORDS * 8 + 4) <= 65536 &&
+                      (size_t)CHANGE_LDS_BINS_SLOTS_MAX * 4 + (size_t)ASOF_LDS_BINS * (BALANCE_SLOT_WORDS * 8 + 4) <= 65536,
+                  "set, bins and tags stay within 64 KB a workgroup");
+    API_ENTER(E, false);
+    QueryCall c;
+    NodeTablesArgs NT;
+    if (const int st = account_scan_begin(E, "lookup_accounts_at", &QueryState::ql, n, TBGPU_LOOKUP_AT_MAX, ids, out, result, &c, &NT,
+                                          [&] { return timestamp != ~0ULL; })) {
+        return st == SCAN_ANSWERED ? TBGPU_STATUS_OK : st;
+    }
+    const bool scan = timestamp != 0;
+    AccountScan s{};
+    s.name = "lookup_accounts_at", s.unit = "records", s.asked = std::to_string(n) + " ids";
+    s.bufs = &QueryState::ql, s.bins = [](QueryState& q) { return ScanBins{q.ql.d_bins, q.ql.h_bins}; };
+    s.n = n, s.T = timestamp, s.scan = scan;
+    s.bin_bytes = ASOF_BIN_BYTES(n), s.flag_word = (u64)n * BALANCE_SLOT_WORDS + CHANGE_FLAG_ORPHAN;
+    s.layout = ASOF_BIN_LAYOUT, s.n_runs = 1, s.keys_per_id = 1, s.row_bytes = 128, s.rows_per_id = 1;
+    s.launch_scan = [=](const ScanLaunch& L) -> int {
+        const bool narrow = L.slots > CHANGE_LDS_BINS_SLOTS_MAX;  // 16-bit entries in LDS: the bins keep their room
+        const size_t lds = (size_t)L.slots * (narrow ? 2 : 4) + (size_t)ASOF_LDS_BINS * (BALANCE_SLOT_WORDS * 8 + 4);
+        hipLaunchKernelGGL((narrow ? tb_change_effects<u16, true> : tb_change_effects<u32, true>), dim3(L.nb), dim3(CHANGE_THREADS), lds,
+                           L.E->stream, L.NT, L.self, L.records, timestamp, (const u32*)L.B.d_set, L.mask, (const u64*)L.B.d_ids, n,
+                           L.d_bins, ASOF_LDS_BINS);
+        return TBGPU_STATUS_OK;
+    };
+    s.launch_emit = [=](const ScanLaunch& L) -> int {
+        hipLaunchKernelGGL(tb_asof_emit, dim3((n + QUERY_THREADS - 1) / QUERY_THREADS), dim3(QUERY_THREADS), 0, L.E->stream,
+                           (const u64*)L.B.d_ids, n, (const u8*)L.B.d_accounts, (const u32*)L.B.d_found,
+                           scan ? (const u32*)L.B.d_set : nullptr, L.mask, scan ? (const u64*)L.d_bins : nullptr, L.cap, L.B.d_out,
+                           L.B.d_res);
+        return TBGPU_STATUS_OK;
+    };
+    return account_scan_run(c, s, NT, out_cap_records, out, result, [&](const u64* account, const u64* bin, u64 first, u8* rows) -> u32 {
+        u8* rec = rows + first * 128;  // the record, its balances less its id's bin
+        memcpy(rec, account, 128);
+        if (!bin) return 1;
+        u128 bal[4];
+        memcpy(bal, rec + 16, sizeof bal);
+        for (u32 col = 0; col < 4; col++) bal[col] -= tb_u128(bin[2 * col], bin[2 * col + 1]);
+        memcpy(rec + 16, bal, sizeof bal);
+        return 1;
+    });
+}
+
+// What the three calls that return 256-B rows from the statements call's buffers have in common.
+static AccountScan account_scan_of_rows(const char* name, u32 n, u64 T) {
+    AccountScan s{};
+    s.name = name, s.unit = "rows", s.asked = std::to_string(n) + " ids";
+    s.bufs = &QueryState::qt;
+    s.n = n, s.T = T, s.scan = true;
+    s.keys_per_id = 1, s.row_bytes = STATEMENT_ROW_BYTES, s.rows_per_id = 1;
+    return s;
+}
+
+// get_account_statements (k_statement.h): T = t_close.  The scan always runs: t_close = 0 has nothing
+// above it, but the period's sums are the log's.  The set has at most 8,192 slots and stays 32-bit in
+// LDS beside STATEMENT_LDS_BINS claimed bins.
+static constexpr ScanBinRun STATEMENT_BIN_LAYOUT[] = {{2, 4}, {2, 3}, {1, 1}, {2, 3}, {1, 1}};
 extern "C" int tbgpu_get_account_statements(tbgpu_t* E, uint64_t t_open, uint64_t t_close, const void* ids, uint32_t n, void* out,
                                             uint32_t out_cap_rows, tbgpu_query_result* result) {
     static_assert(sizeof(tbgpu_account_statement) == STATEMENT_ROW_BYTES && STATEMENT_IDS_MAX == TBGPU_STATEMENTS_MAX &&
-                      STATEMENT_ZONE1 + 2 * STATEMENT_SIDE_WORDS == STATEMENT_BIN_WORDS,
+                      STATEMENT_ZONE1 + 2 * STATEMENT_SIDE_WORDS == STATEMENT_BIN_WORDS &&
+                      scan_bin_words(STATEMENT_BIN_LAYOUT, 5) == STATEMENT_BIN_WORDS,
                   "k_statement.h's constants are the header's");
     static_assert((size_t)CHANGE_LDS_BINS_SLOTS_MAX * 4 + (size_t)STATEMENT_LDS_BINS * (STATEMENT_BIN_WORDS * 8 + 4) <= 65536,
                   "set, bins and tags stay within 64 KB a workgroup");
     API_ENTER(E, false);
-    if (n > TBGPU_STATEMENTS_MAX) return fail(TBGPU_STATUS_INVALID, "get_account_statements: %u ids (at most %u)", n, TBGPU_STATEMENTS_MAX);
-    if (n == 0) return TBGPU_STATUS_OK;
-    if (!ids || !out || !result) return fail(TBGPU_STATUS_INVALID, "get_account_statements: NULL ids, out or result");
     QueryCall c;
-    result->count = 0;
-    result->matched = 0;
-    result->complete = query_engines(E, true, &c);
-    if (t_open == ~0ULL || t_close == ~0ULL || (t_close != 0 && t_close < t_open)) return TBGPU_STATUS_OK;
-    const bool one = c.world == 1;
-    NodeTablesArgs NT{};
-    NT.world = c.world;
-    for (u32 d = 0; d < c.world; d++) NT.T[d] = c.Es[d]->T;
-    // Every engine is drained before any is asked: a gather reads the owners' tables and a scan its
-    // posts' pending transfers on their homes.
-    for (u32 d = 0; d < c.world; d++) {
-        HIPCK(hipSetDevice(c.Es[d]->device));
-        if (c.Es[d]->pending) {
-            const int st = engine_sync(c.Es[d]);
-            if (st) return query_end(result, st);
-        }
+    NodeTablesArgs NT;
+    if (const int st = account_scan_begin(E, "get_account_statements", &QueryState::qt, n, TBGPU_STATEMENTS_MAX, ids, out, result, &c, &NT,
+                                          [&] { return t_open != ~0ULL && t_close != ~0ULL && (t_close == 0 || t_close >= t_open); })) {
+        return st == SCAN_ANSWERED ? TBGPU_STATUS_OK : st;
     }
-    memcpy(c.Es[0]->qs->qt.h_ids, ids, (u64)n * 16);
-    int st = query_side_by_side(c.Es, c.world, [&](u32 d) -> int {
-        if (d) memcpy(c.Es[d]->qs->qt.h_ids, c.Es[0]->qs->qt.h_ids, (u64)n * 16);
-        return statements_enqueue(c.Es[d], NT, d, n, t_open, t_close, one, out_cap_rows);
+    AccountScan s = account_scan_of_rows("get_account_statements", n, t_close);
+    s.bins = [](QueryState& q) { return ScanBins{q.qt.d_bins, q.qt.h_bins}; };
+    s.bin_bytes = STATEMENT_BIN_BYTES(n), s.flag_word = (u64)n * STATEMENT_BIN_WORDS;
+    s.layout = STATEMENT_BIN_LAYOUT, s.n_runs = 5;
+    s.launch_scan = [=](const ScanLaunch& L) -> int {
+        const size_t lds = (size_t)L.slots * 4 + (size_t)STATEMENT_LDS_BINS * (STATEMENT_BIN_WORDS * 8 + 4);
+        hipLaunchKernelGGL(tb_statement_effects, dim3(L.nb), dim3(CHANGE_THREADS), lds, L.E->stream, L.NT, L.self, L.records, t_open,
+                           t_close, (const u32*)L.B.d_set, L.mask, (const u64*)L.B.d_ids, n, L.d_bins);
+        return TBGPU_STATUS_OK;
+    };
+    s.launch_emit = [=](const ScanLaunch& L) -> int {
+        hipLaunchKernelGGL(tb_statement_emit, dim3((n + QUERY_THREADS - 1) / QUERY_THREADS), dim3(QUERY_THREADS), 0, L.E->stream,
+                           (const u64*)L.B.d_ids, n, (const u8*)L.B.d_accounts, (const u32*)L.B.d_found, (const u32*)L.B.d_set, L.mask,
+                           (const u64*)L.d_bins, L.cap, L.B.d_out, L.B.d_res);
+        return TBGPU_STATUS_OK;
+    };
+    return account_scan_run(c, s, NT, out_cap_rows, out, result, [&](const u64* account, const u64* bin, u64 first, u8* rows) -> u32 {
+        u64 row[STATEMENT_ROW_BYTES / 8];
+        tb_statement_row(account, bin, row);
+        memcpy(rows + first * STATEMENT_ROW_BYTES, row, sizeof row);
+        return 1;
     });
-    if (st) return query_end(result, st);
-    if (!one) {
-        statements_node_rows(c, n, out_cap_rows, (u8*)out, result);
-        return TBGPU_STATUS_OK;
-    }
-    tbgpu* S0 = c.Es[0];
-    const StatementBufs& S = S0->qs->qt;
-    const u64 matched = S.h_res[STATEMENT_RES_MATCHED];
-    const u32 m = (u32)std::min<u64>(matched, out_cap_rows);
-    if (matched > n) return query_end(result, fail(TBGPU_STATUS_PANIC, "get_account_statements: %llu rows for %u ids", (unsigned long long)matched, n));
-    if (m) {
-        HIPCK(hipMemcpyAsync(out, S.d_out, (u64)m * STATEMENT_ROW_BYTES, hipMemcpyDeviceToHost, S0->stream));
-        HIPCK(hipStreamSynchronize(S0->stream));
-    }
-    if (S.h_res[STATEMENT_RES_ORPHAN]) result->complete = 0;
-    result->count = m;
-    result->matched = matched;
-    return TBGPU_STATUS_OK;
 }
 
-// ---- get_account_balance_integrals (k_integral.h, include/tbgpu.h) --------------------------------
-// get_account_statements' shape with T = t_end, a scan of its own and wider bins.  One engine: ids up,
-// set and bins zeroed, tb_asof_gather -> tb_integral_effects -> tb_integral_emit on the engine stream,
-// the result words back; one wait; then the answer's count * 256 bytes.  The request, the set, the
-// records, the flags, the rows and the result words are the statements call's buffers (StatementBufs);
-// the bins are IntegralBufs'.  A node: every shard gathers and scans its own log on its own device and
-// stream, side by side; the host adds the shards' bins modulo 2^128 and 2^192 and writes the rows
-// (tb_integral_row).
-static int integrals_enqueue(tbgpu* E, const NodeTablesArgs& NT, u32 self, u32 n, u64 t_open, u64 t_end, bool emit, u32 cap) {
-    StatementBufs& S = E->qs->qt;
-    IntegralBufs& I = E->qs->qi;
-    HIPCK(hipSetDevice(E->device));
-    const u32 slots = tb_change_set_slots(n), mask = slots - 1;
-    const u64 bin_bytes = INTEGRAL_BIN_BYTES(n);
-    const unsigned nb_ids = (n + QUERY_THREADS - 1) / QUERY_THREADS;
-    HIPCK(hipMemcpyAsync(S.d_ids, S.h_ids, (u64)n * 16, hipMemcpyHostToDevice, E->stream));
-    HIPCK(hipMemsetAsync(S.d_set, 0, (u64)slots * 4, E->stream));
-    HIPCK(hipMemsetAsync(I.d_bins, 0, bin_bytes, E->stream));
-    const bool store = emit || self == 0;  // a node reads the first shard's records only
-    hipLaunchKernelGGL(tb_asof_gather, dim3(nb_ids), dim3(QUERY_THREADS), 0, E->stream, NT, (const u64*)S.d_ids, n, t_end,
-                       store ? S.d_accounts : nullptr, store ? S.d_found : nullptr, S.d_set, mask);
-    HIPCK(hipGetLastError());
-    const u64 records = E->log_next, per = (u64)CHANGE_THREADS * CHANGE_TILES, nb = (records + per - 1) / per;
-    if (nb) {
-        const size_t lds = (size_t)slots * 4 + (size_t)INTEGRAL_LDS_BINS * (INTEGRAL_BIN_WORDS * 8 + 4);
-        hipLaunchKernelGGL(tb_integral_effects, dim3((unsigned)nb), dim3(CHANGE_THREADS), lds, E->stream, NT, self, records, t_open,
-                           t_end, (const u32*)S.d_set, mask, (const u64*)S.d_ids, n, I.d_bins);
-        HIPCK(hipGetLastError());
-    }
-    if (emit) {
-        hipLaunchKernelGGL(tb_integral_emit, dim3(nb_ids), dim3(QUERY_THREADS), 0, E->stream, (const u64*)S.d_ids, n,
-                           (const u8*)S.d_accounts, (const u32*)S.d_found, (const u32*)S.d_set, mask, (const u64*)I.d_bins, t_open,
-                           t_end, cap, S.d_out, S.d_res);
-        HIPCK(hipGetLastError());
-        HIPCK(hipMemcpyAsync(S.h_res, S.d_res, INTEGRAL_RES_WORDS * 8, hipMemcpyDeviceToHost, E->stream));
-        return TBGPU_STATUS_OK;
-    }
-    HIPCK(hipMemcpyAsync(I.h_bins, I.d_bins, bin_bytes, hipMemcpyDeviceToHost, E->stream));
-    if (self == 0) {
-        HIPCK(hipMemcpyAsync(S.h_accounts, S.d_accounts, (u64)n * 128, hipMemcpyDeviceToHost, E->stream));
-        HIPCK(hipMemcpyAsync(S.h_found, S.d_found, (u64)n * 4, hipMemcpyDeviceToHost, E->stream));
-    }
-    return TBGPU_STATUS_OK;
-}
-
-// A node's answer from its shards' pinned mirrors, as statements_node_rows builds it: the found
-// positions in request order, each from its record and the sum of every shard's bin of its id (the bin
-// of the smallest position that names the id).  The bins' words add as the device added them: the
-// eight 128-bit sums and the four 192-bit sums, each with its carries.
-static void integrals_node_rows(const QueryCall& c, u32 n, u64 t_open, u64 t_end, u32 cap, u8* out, tbgpu_query_result* result) {
-    const StatementBufs& S = c.Es[0]->qs->qt;
-    std::vector<u32> index(n), order(n);
-    std::iota(order.begin(), order.end(), 0u);
-    auto id_of = [&](u32 i) { return std::make_pair(S.h_ids[2 * (u64)i + 1], S.h_ids[2 * (u64)i]); };
-    std::sort(order.begin(), order.end(), [&](u32 a, u32 b) { return id_of(a) != id_of(b) ? id_of(a) < id_of(b) : a < b; });
-    for (u32 j = 0; j < n; j++) index[order[j]] = j && id_of(order[j - 1]) == id_of(order[j]) ? index[order[j - 1]] : order[j];
-    u32 m = 0, written = 0;
-    for (u32 i = 0; i < n; i++) {
-        if (!S.h_found[i]) continue;
-        if (m++ >= cap) continue;
-        u64 bin[INTEGRAL_BIN_WORDS] = {};
-        for (u32 d = 0; d < c.world; d++) {
-            const u64* b = c.Es[d]->qs->qi.h_bins + (u64)index[i] * INTEGRAL_BIN_WORDS;
-            for (u32 w = 0; w < INTEGRAL_WEIGHTED; w += 2) {
-                const u128 v = tb_u128(bin[w], bin[w + 1]) + tb_u128(b[w], b[w + 1]);
-                bin[w] = tb_lo(v), bin[w + 1] = tb_hi(v);
-            }
-            for (u32 w = INTEGRAL_WEIGHTED; w < INTEGRAL_BIN_WORDS; w += 3) {
-                const U192 v = tb_add192({bin[w], bin[w + 1], bin[w + 2]}, {b[w], b[w + 1], b[w + 2]});
-                bin[w] = v.w0, bin[w + 1] = v.w1, bin[w + 2] = v.w2;
-            }
-        }
-        u64 row[INTEGRAL_ROW_BYTES / 8];
-        tb_integral_row((const u64*)(S.h_accounts + (u64)i * 128), bin, t_open, t_end, row);
-        memcpy(out + (u64)written++ * INTEGRAL_ROW_BYTES, row, sizeof row);
-    }
-    for (u32 d = 0; d < c.world; d++) {
-        if (c.Es[d]->qs->qi.h_bins[(u64)n * INTEGRAL_BIN_WORDS]) result->complete = 0;
-    }
-    result->count = written;
-    result->matched = m;
-}
-
+// get_account_balance_integrals (k_integral.h): T = t_end, and bins of its own (IntegralBufs), wider
+// and with 192-bit sums.
+static constexpr ScanBinRun INTEGRAL_BIN_LAYOUT[] = {{2, 8}, {3, 4}};
 extern "C" int tbgpu_get_account_balance_integrals(tbgpu_t* E, uint64_t t_open, uint64_t t_close, const void* ids, uint32_t n, void* out,
                                                    uint32_t out_cap_rows, tbgpu_query_result* result) {
     static_assert(sizeof(tbgpu_account_balance_integral) == INTEGRAL_ROW_BYTES && INTEGRAL_IDS_MAX == TBGPU_INTEGRALS_MAX &&
                       INTEGRAL_WEIGHTED + 4 * 3 == INTEGRAL_BIN_WORDS && INTEGRAL_IDS_MAX == STATEMENT_IDS_MAX &&
-                      INTEGRAL_ROW_BYTES == STATEMENT_ROW_BYTES && INTEGRAL_RES_WORDS == STATEMENT_RES_WORDS,
+                      INTEGRAL_ROW_BYTES == STATEMENT_ROW_BYTES && scan_bin_words(INTEGRAL_BIN_LAYOUT, 2) == INTEGRAL_BIN_WORDS,
                   "k_integral.h's constants are the header's, and the statements call's buffers fit");
     static_assert((size_t)CHANGE_LDS_BINS_SLOTS_MAX * 4 + (size_t)INTEGRAL_LDS_BINS * (INTEGRAL_BIN_WORDS * 8 + 4) <= 65536,
                   "set, bins and tags stay within 64 KB a workgroup");
     API_ENTER(E, false);
-    if (n > TBGPU_INTEGRALS_MAX) return fail(TBGPU_STATUS_INVALID, "get_account_balance_integrals: %u ids (at most %u)", n, TBGPU_INTEGRALS_MAX);
-    if (n == 0) return TBGPU_STATUS_OK;
-    if (!ids || !out || !result) return fail(TBGPU_STATUS_INVALID, "get_account_balance_integrals: NULL ids, out or result");
     QueryCall c;
-    result->count = 0;
-    result->matched = 0;
-    result->complete = query_engines(E, true, &c);
-    if (t_open == ~0ULL || t_close == ~0ULL) return TBGPU_STATUS_OK;
-    // Every engine is drained before any is asked: a gather reads the owners' tables and a scan its
-    // posts' pending transfers on their homes.
-    for (u32 d = 0; d < c.world; d++) {
-        HIPCK(hipSetDevice(c.Es[d]->device));
-        if (c.Es[d]->pending) {
-            const int st = engine_sync(c.Es[d]);
-            if (st) return query_end(result, st);
-        }
+    NodeTablesArgs NT;
+    if (const int st = account_scan_begin(E, "get_account_balance_integrals", &QueryState::qt, n, TBGPU_INTEGRALS_MAX, ids, out, result, &c,
+                                          &NT, [&] { return t_open != ~0ULL && t_close != ~0ULL; })) {
+        return st == SCAN_ANSWERED ? TBGPU_STATUS_OK : st;
     }
-    // An integral needs a finite end: "now" is commit_timestamp, read once.  No account and no record
-    // has timestamp 0, so an end at 0 (nothing was ever committed) has no rows.
+    // An integral needs a finite end: "now" is commit_timestamp, read once, after the drain.  No account
+    // and no record has timestamp 0, so an end at 0 (nothing was ever committed) has no rows.
     const u64 t_end = t_close ? t_close : tbgpu_commit_timestamp(E);
     if (t_end < t_open || t_end == 0) return TBGPU_STATUS_OK;
-    const bool one = c.world == 1;
-    NodeTablesArgs NT{};
-    NT.world = c.world;
-    for (u32 d = 0; d < c.world; d++) NT.T[d] = c.Es[d]->T;
-    memcpy(c.Es[0]->qs->qt.h_ids, ids, (u64)n * 16);
-    int st = query_side_by_side(c.Es, c.world, [&](u32 d) -> int {
-        if (d) memcpy(c.Es[d]->qs->qt.h_ids, c.Es[0]->qs->qt.h_ids, (u64)n * 16);
-        return integrals_enqueue(c.Es[d], NT, d, n, t_open, t_end, one, out_cap_rows);
+    AccountScan s = account_scan_of_rows("get_account_balance_integrals", n, t_end);
+    s.bins = [](QueryState& q) { return ScanBins{q.qi.d_bins, q.qi.h_bins}; };
+    s.bin_bytes = INTEGRAL_BIN_BYTES(n), s.flag_word = (u64)n * INTEGRAL_BIN_WORDS;
+    s.layout = INTEGRAL_BIN_LAYOUT, s.n_runs = 2;
+    s.launch_scan = [=](const ScanLaunch& L) -> int {
+        const size_t lds = (size_t)L.slots * 4 + (size_t)INTEGRAL_LDS_BINS * (INTEGRAL_BIN_WORDS * 8 + 4);
+        hipLaunchKernelGGL(tb_integral_effects, dim3(L.nb), dim3(CHANGE_THREADS), lds, L.E->stream, L.NT, L.self, L.records, t_open,
+                           t_end, (const u32*)L.B.d_set, L.mask, (const u64*)L.B.d_ids, n, L.d_bins);
+        return TBGPU_STATUS_OK;
+    };
+    s.launch_emit = [=](const ScanLaunch& L) -> int {
+        hipLaunchKernelGGL(tb_integral_emit, dim3((n + QUERY_THREADS - 1) / QUERY_THREADS), dim3(QUERY_THREADS), 0, L.E->stream,
+                           (const u64*)L.B.d_ids, n, (const u8*)L.B.d_accounts, (const u32*)L.B.d_found, (const u32*)L.B.d_set, L.mask,
+                           (const u64*)L.d_bins, t_open, t_end, L.cap, L.B.d_out, L.B.d_res);
+        return TBGPU_STATUS_OK;
+    };
+    return account_scan_run(c, s, NT, out_cap_rows, out, result, [&](const u64* account, const u64* bin, u64 first, u8* rows) -> u32 {
+        u64 row[INTEGRAL_ROW_BYTES / 8];
+        tb_integral_row(account, bin, t_open, t_end, row);
+        memcpy(rows + first * INTEGRAL_ROW_BYTES, row, sizeof row);
+        return 1;
     });
-    if (st) return query_end(result, st);
-    if (!one) {
-        integrals_node_rows(c, n, t_open, t_end, out_cap_rows, (u8*)out, result);
-        return TBGPU_STATUS_OK;
-    }
-    tbgpu* S0 = c.Es[0];
-    const StatementBufs& S = S0->qs->qt;
-    const u64 matched = S.h_res[INTEGRAL_RES_MATCHED];
-    const u32 m = (u32)std::min<u64>(matched, out_cap_rows);
-    if (matched > n) return query_end(result, fail(TBGPU_STATUS_PANIC, "get_account_balance_integrals: %llu rows for %u ids", (unsigned long long)matched, n));
-    if (m) {
-        HIPCK(hipMemcpyAsync(out, S.d_out, (u64)m * INTEGRAL_ROW_BYTES, hipMemcpyDeviceToHost, S0->stream));
-        HIPCK(hipStreamSynchronize(S0->stream));
-    }
-    if (S.h_res[INTEGRAL_RES_ORPHAN]) result->complete = 0;
-    result->count = m;
-    result->matched = matched;
-    return TBGPU_STATUS_OK;
 }
 
-// ---- get_account_statement_series (k_series.h, include/tbgpu.h) -----------------------------------
-// get_account_statements' shape with T = the last bound, B + 1 buckets for its two zones and bins by
-// key.  One engine: ids and bounds up, set and bins zeroed, tb_asof_gather -> tb_series_effects ->
-// tb_series_emit on the engine stream, the result words back; one wait; then the answer's count * 256
-// bytes.  The request, the set, the records, the flags, the rows and the result words are the
-// statements call's buffers (StatementBufs); the bounds and the bins are SeriesBufs'.  A node: every
-// shard gathers and scans its own log on its own device and stream, side by side; the host adds the
-// shards' bins and writes the rows, an account's buckets from the last to the first (tb_series_row).
-static int series_enqueue(tbgpu* E, const NodeTablesArgs& NT, u32 self, u32 n, u32 n_buckets, bool emit, u32 cap) {
-    StatementBufs& S = E->qs->qt;
-    SeriesBufs& R = E->qs->qr;
-    HIPCK(hipSetDevice(E->device));
-    const u32 slots = tb_change_set_slots(n), mask = slots - 1;
-    const u64 keys = (u64)n * (n_buckets + 1), bin_bytes = SERIES_BIN_BYTES(keys);
-    const unsigned nb_ids = (n + QUERY_THREADS - 1) / QUERY_THREADS;
-    const u64 t_last = R.h_bounds[n_buckets];
-    HIPCK(hipMemcpyAsync(S.d_ids, S.h_ids, (u64)n * 16, hipMemcpyHostToDevice, E->stream));
-    HIPCK(hipMemcpyAsync(R.d_bounds, R.h_bounds, ((u64)n_buckets + 1) * 8, hipMemcpyHostToDevice, E->stream));
-    HIPCK(hipMemsetAsync(S.d_set, 0, (u64)slots * 4, E->stream));
-    HIPCK(hipMemsetAsync(R.d_bins, 0, bin_bytes, E->stream));
-    const bool store = emit || self == 0;  // a node reads the first shard's records only
-    hipLaunchKernelGGL(tb_asof_gather, dim3(nb_ids), dim3(QUERY_THREADS), 0, E->stream, NT, (const u64*)S.d_ids, n, t_last,
-                       store ? S.d_accounts : nullptr, store ? S.d_found : nullptr, S.d_set, mask);
-    HIPCK(hipGetLastError());
-    const u64 records = E->log_next, per = (u64)CHANGE_THREADS * CHANGE_TILES, nb = (records + per - 1) / per;
-    if (nb) {
-        const size_t lds = tb_series_lds_bytes(slots, n_buckets);
-        if (lds > 65536) return fail(TBGPU_STATUS_PANIC, "get_account_statement_series: %zu bytes of LDS", lds);
-        hipLaunchKernelGGL(tb_series_effects, dim3((unsigned)nb), dim3(CHANGE_THREADS), lds, E->stream, NT, self, records,
-                           (const u64*)R.d_bounds, n_buckets, (const u32*)S.d_set, mask, (const u64*)S.d_ids, n, R.d_bins);
-        HIPCK(hipGetLastError());
-    }
-    if (emit) {
-        const unsigned nb_rows = (n * n_buckets + QUERY_THREADS - 1) / QUERY_THREADS;
-        hipLaunchKernelGGL(tb_series_emit, dim3(nb_rows), dim3(QUERY_THREADS), 0, E->stream, (const u64*)S.d_ids, n, n_buckets,
-                           (const u8*)S.d_accounts, (const u32*)S.d_found, (const u32*)S.d_set, mask, (const u64*)R.d_bins, cap,
-                           S.d_out, S.d_res);
-        HIPCK(hipGetLastError());
-        HIPCK(hipMemcpyAsync(S.h_res, S.d_res, SERIES_RES_WORDS * 8, hipMemcpyDeviceToHost, E->stream));
-        return TBGPU_STATUS_OK;
-    }
-    HIPCK(hipMemcpyAsync(R.h_bins, R.d_bins, bin_bytes, hipMemcpyDeviceToHost, E->stream));
-    if (self == 0) {
-        HIPCK(hipMemcpyAsync(S.h_accounts, S.d_accounts, (u64)n * 128, hipMemcpyDeviceToHost, E->stream));
-        HIPCK(hipMemcpyAsync(S.h_found, S.d_found, (u64)n * 4, hipMemcpyDeviceToHost, E->stream));
-    }
-    return TBGPU_STATUS_OK;
-}
-
-// A node's answer from its shards' pinned mirrors, as statements_node_rows builds it: the found
-// positions in request order, each with its n_buckets rows from its record and the sums of every
-// shard's bins of its id's keys.  The closing balances run from the tail down: a bucket's opening is
-// the closing of the one before it.
-static void series_node_rows(const QueryCall& c, u32 n, u32 n_buckets, u32 cap, u8* out, tbgpu_query_result* result) {
-    const StatementBufs& S = c.Es[0]->qs->qt;
-    const u32 stride = n_buckets + 1;
-    std::vector<u32> index(n), order(n);
-    std::iota(order.begin(), order.end(), 0u);
-    auto id_of = [&](u32 i) { return std::make_pair(S.h_ids[2 * (u64)i + 1], S.h_ids[2 * (u64)i]); };
-    std::sort(order.begin(), order.end(), [&](u32 a, u32 b) { return id_of(a) != id_of(b) ? id_of(a) < id_of(b) : a < b; });
-    for (u32 j = 0; j < n; j++) index[order[j]] = j && id_of(order[j - 1]) == id_of(order[j]) ? index[order[j - 1]] : order[j];
-    std::vector<u64> bins((u64)stride * SERIES_BIN_WORDS);
-    u64 m = 0;
-    u32 written = 0;
-    for (u32 i = 0; i < n; i++) {
-        if (!S.h_found[i]) continue;
-        const u64 first = m;  // the account's first row
-        m += n_buckets;
-        if (first >= cap) continue;
-        std::fill(bins.begin(), bins.end(), 0);
-        for (u32 d = 0; d < c.world; d++) {
-            const u64* b = c.Es[d]->qs->qr.h_bins + (u64)index[i] * stride * SERIES_BIN_WORDS;
-            for (u32 k = 0; k < stride; k++) {
-                u64* sum = bins.data() + (u64)k * SERIES_BIN_WORDS;
-                const u64* src = b + (u64)k * SERIES_BIN_WORDS;
-                for (u32 w = 0; w < SERIES_BIN_WORDS;) {
-                    if (w % SERIES_SIDE_WORDS == 6) {  // a count
-                        sum[w] += src[w];
-                        w += 1;
-                    } else {
-                        const u128 v = tb_u128(sum[w], sum[w + 1]) + tb_u128(src[w], src[w + 1]);
-                        sum[w] = tb_lo(v), sum[w + 1] = tb_hi(v);
-                        w += 2;
-                    }
-                }
-            }
-        }
-        const u64* account = (const u64*)(S.h_accounts + (u64)i * 128);
-        u128 closing[4], net[4];
-        tb_series_net(bins.data() + (u64)n_buckets * SERIES_BIN_WORDS, net);  // the tail
-        for (u32 col = 0; col < 4; col++) closing[col] = tb_u128(account[2 + 2 * col], account[3 + 2 * col]) - net[col];
-        for (u32 k = n_buckets; k-- > 0;) {
-            u64 row[STATEMENT_ROW_BYTES / 8];
-            tb_series_row(account, bins.data() + (u64)k * SERIES_BIN_WORDS, closing, row);
-            if (first + k < cap) {
-                memcpy(out + (first + k) * STATEMENT_ROW_BYTES, row, sizeof row);
-                written++;
-            }
-            for (u32 col = 0; col < 4; col++) closing[col] = tb_u128(row[2 + 2 * col], row[3 + 2 * col]);  // its opening
-        }
-    }
-    for (u32 d = 0; d < c.world; d++) {
-        if (c.Es[d]->qs->qr.h_bins[(u64)n * stride * SERIES_BIN_WORDS]) result->complete = 0;
-    }
-    result->count = written;
-    result->matched = m;
-}
-
+// get_account_statement_series (k_series.h): T = the last bound, B + 1 buckets for the statements
+// call's two zones, bins by key and the bounds (SeriesBufs), which go up before the scan.  A node's
+// host writes an account's buckets from the last to the first: the closing balances run from the tail
+// down, a bucket's opening is the closing of the one before it.
+static constexpr ScanBinRun SERIES_BIN_LAYOUT[] = {{2, 3}, {1, 1}, {2, 3}, {1, 1}};
 extern "C" int tbgpu_get_account_statement_series(tbgpu_t* E, const uint64_t* bounds, uint32_t n_buckets, const void* ids, uint32_t n,
                                                   void* out, uint32_t out_cap_rows, tbgpu_query_result* result) {
     static_assert(SERIES_ROWS_MAX == TBGPU_SERIES_ROWS_MAX && SERIES_ROWS_MAX == STATEMENT_IDS_MAX &&
-                      2 * SERIES_SIDE_WORDS == SERIES_BIN_WORDS && SERIES_RES_WORDS == STATEMENT_RES_WORDS,
+                      scan_bin_words(SERIES_BIN_LAYOUT, 4) == SERIES_BIN_WORDS,
                   "k_series.h's constants are the header's, and the statements call's buffers fit");
     // n * n_buckets <= 4,095: above 2,048 ids there is one bucket, and 256 slots hold at most 128 ids.
     static_assert((size_t)CHANGE_LDS_BINS_SLOTS_MAX * 4 + 2 * 8 <= SERIES_LDS_FIXED_MAX &&
@@ -1779,61 +1559,57 @@ extern "C" int tbgpu_get_account_statement_series(tbgpu_t* E, const uint64_t* bo
                     TBGPU_SERIES_ROWS_MAX);
     }
     if (!bounds) return fail(TBGPU_STATUS_INVALID, "get_account_statement_series: NULL bounds");
-    if (n == 0) return TBGPU_STATUS_OK;
-    if (!ids || !out || !result) return fail(TBGPU_STATUS_INVALID, "get_account_statement_series: NULL ids, out or result");
     QueryCall c;
-    result->count = 0;
-    result->matched = 0;
-    result->complete = query_engines(E, true, &c);
-    for (u32 k = 0; k <= n_buckets; k++) {
-        if (bounds[k] == ~0ULL) return TBGPU_STATUS_OK;
-        if (k == 0) continue;
-        const bool open_end = k == n_buckets && bounds[k] == 0;
-        if (!open_end && (bounds[k] == 0 || bounds[k] < bounds[k - 1])) return TBGPU_STATUS_OK;
+    NodeTablesArgs NT;
+    if (const int st = account_scan_begin(E, "get_account_statement_series", &QueryState::qt, n, ~0u, ids, out, result, &c, &NT, [&] {
+            for (u32 k = 0; k <= n_buckets; k++) {
+                if (bounds[k] == ~0ULL) return false;
+                if (k == 0) continue;
+                const bool open_end = k == n_buckets && bounds[k] == 0;
+                if (!open_end && (bounds[k] == 0 || bounds[k] < bounds[k - 1])) return false;
+            }
+            return true;
+        })) {
+        return st == SCAN_ANSWERED ? TBGPU_STATUS_OK : st;
     }
-    const bool one = c.world == 1;
-    NodeTablesArgs NT{};
-    NT.world = c.world;
-    for (u32 d = 0; d < c.world; d++) NT.T[d] = c.Es[d]->T;
-    // Every engine is drained before any is asked: a gather reads the owners' tables and a scan its
-    // posts' pending transfers on their homes.
-    for (u32 d = 0; d < c.world; d++) {
-        HIPCK(hipSetDevice(c.Es[d]->device));
-        if (c.Es[d]->pending) {
-            const int st = engine_sync(c.Es[d]);
-            if (st) return query_end(result, st);
-        }
-    }
-    memcpy(c.Es[0]->qs->qt.h_ids, ids, (u64)n * 16);
-    memcpy(c.Es[0]->qs->qr.h_bounds, bounds, ((u64)n_buckets + 1) * 8);
-    int st = query_side_by_side(c.Es, c.world, [&](u32 d) -> int {
-        if (d) {
-            memcpy(c.Es[d]->qs->qt.h_ids, c.Es[0]->qs->qt.h_ids, (u64)n * 16);
-            memcpy(c.Es[d]->qs->qr.h_bounds, c.Es[0]->qs->qr.h_bounds, ((u64)n_buckets + 1) * 8);
-        }
-        return series_enqueue(c.Es[d], NT, d, n, n_buckets, one, out_cap_rows);
-    });
-    if (st) return query_end(result, st);
-    if (!one) {
-        series_node_rows(c, n, n_buckets, out_cap_rows, (u8*)out, result);
+    for (u32 d = 0; d < c.world; d++) memcpy(c.Es[d]->qs->qr.h_bounds, bounds, ((u64)n_buckets + 1) * 8);
+    const u32 stride = n_buckets + 1;
+    AccountScan s = account_scan_of_rows("get_account_statement_series", n, bounds[n_buckets]);
+    s.asked += " x " + std::to_string(n_buckets) + " buckets";
+    s.bins = [](QueryState& q) { return ScanBins{q.qr.d_bins, q.qr.h_bins}; };
+    s.bin_bytes = SERIES_BIN_BYTES((u64)n * stride), s.flag_word = (u64)n * stride * SERIES_BIN_WORDS;
+    s.layout = SERIES_BIN_LAYOUT, s.n_runs = 4, s.keys_per_id = stride, s.rows_per_id = n_buckets;
+    s.launch_scan = [=](const ScanLaunch& L) -> int {
+        const SeriesBufs& R = L.E->qs->qr;
+        const size_t lds = tb_series_lds_bytes(L.slots, n_buckets);
+        if (lds > 65536) return fail(TBGPU_STATUS_PANIC, "get_account_statement_series: %zu bytes of LDS", lds);
+        HIPCK(hipMemcpyAsync(R.d_bounds, R.h_bounds, ((u64)n_buckets + 1) * 8, hipMemcpyHostToDevice, L.E->stream));
+        hipLaunchKernelGGL(tb_series_effects, dim3(L.nb), dim3(CHANGE_THREADS), lds, L.E->stream, L.NT, L.self, L.records,
+                           (const u64*)R.d_bounds, n_buckets, (const u32*)L.B.d_set, L.mask, (const u64*)L.B.d_ids, n, L.d_bins);
         return TBGPU_STATUS_OK;
-    }
-    tbgpu* S0 = c.Es[0];
-    const StatementBufs& S = S0->qs->qt;
-    const u64 matched = S.h_res[SERIES_RES_MATCHED];
-    const u32 m = (u32)std::min<u64>(matched, out_cap_rows);
-    if (matched > (u64)n * n_buckets) {
-        return query_end(result, fail(TBGPU_STATUS_PANIC, "get_account_statement_series: %llu rows for %u ids x %u buckets",
-                                      (unsigned long long)matched, n, n_buckets));
-    }
-    if (m) {
-        HIPCK(hipMemcpyAsync(out, S.d_out, (u64)m * STATEMENT_ROW_BYTES, hipMemcpyDeviceToHost, S0->stream));
-        HIPCK(hipStreamSynchronize(S0->stream));
-    }
-    if (S.h_res[SERIES_RES_ORPHAN]) result->complete = 0;
-    result->count = m;
-    result->matched = matched;
-    return TBGPU_STATUS_OK;
+    };
+    s.launch_emit = [=](const ScanLaunch& L) -> int {
+        hipLaunchKernelGGL(tb_series_emit, dim3((n * n_buckets + QUERY_THREADS - 1) / QUERY_THREADS), dim3(QUERY_THREADS), 0, L.E->stream,
+                           (const u64*)L.B.d_ids, n, n_buckets, (const u8*)L.B.d_accounts, (const u32*)L.B.d_found,
+                           (const u32*)L.B.d_set, L.mask, (const u64*)L.d_bins, L.cap, L.B.d_out, L.B.d_res);
+        return TBGPU_STATUS_OK;
+    };
+    return account_scan_run(c, s, NT, out_cap_rows, out, result, [&](const u64* account, const u64* bins, u64 first, u8* rows) -> u32 {
+        u128 closing[4], net[4];
+        tb_series_net(bins + (u64)n_buckets * SERIES_BIN_WORDS, net);  // the tail
+        for (u32 col = 0; col < 4; col++) closing[col] = tb_u128(account[2 + 2 * col], account[3 + 2 * col]) - net[col];
+        u32 written = 0;
+        for (u32 k = n_buckets; k-- > 0;) {
+            u64 row[STATEMENT_ROW_BYTES / 8];
+            tb_flows_row(account, bins + (u64)k * SERIES_BIN_WORDS, closing, row);
+            if (first + k < out_cap_rows) {
+                memcpy(rows + (first + k) * STATEMENT_ROW_BYTES, row, sizeof row);
+                written++;
+            }
+            for (u32 col = 0; col < 4; col++) closing[col] = tb_u128(row[2 + 2 * col], row[3 + 2 * col]);  // its opening
+        }
+        return written;
+    });
 }
 
 // ---- get_ledger_balances (k_ledgers.h, include/tbgpu.h) -------------------------------------------
