@@ -28,6 +28,7 @@
  *   (no reference: account statements over a period)       tbgpu_get_account_statements (likewise)
  *   (no reference: time-weighted balances over a period)   tbgpu_get_account_balance_integrals (likewise)
  *   (no reference: statements per bucket of a period)      tbgpu_get_account_statement_series (likewise)
+ *   (no reference: who paid whom over a period)            tbgpu_get_account_flow_matrix (likewise)
  *   `setup` action of the table tests (:1398-1407)         tbgpu_test_set_balances (test only)
  *   StateMachine.commit_timestamp field (:251)             tbgpu_commit_timestamp
  *
@@ -875,6 +876,74 @@ int tbgpu_get_account_statement_series(tbgpu_t* engine,
         const uint64_t* bounds /* n_buckets + 1 */, uint32_t n_buckets,
         const void* ids /* n x {lo, hi} */, uint32_t n,
         void* out, uint32_t out_cap_rows, tbgpu_query_result* result);
+
+/* get_account_flow_matrix: who paid whom — for a list of debit accounts and a list of credit accounts
+ * the caller names, over a period the caller names, what each debit account d paid each credit
+ * account c: one cell per pair.  It is what bilateral and multilateral netting, "this merchant's
+ * payers" and "what this bank owes each correspondent" start from.  Every other read call here answers
+ * for an account on its own; paging tbgpu_get_account_transfers per account and grouping on the host is
+ * a log scan per account per page, and tbgpu_query_transfers has no account-pair filter.  This call
+ * derives the whole matrix in one scan of the log in HBM, whatever the number of pairs, and stores
+ * nothing at commit.  No reference has an operation for it.  An entry point of its own, as above; this
+ * comment is its specification.
+ *   The period is (t_open, t_close], exactly tbgpu_get_account_statements': t_open == 0 is read
+ *     literally (from before every record), t_close == 0 means up to now.
+ *   Which accounts: tbgpu_lookup_accounts_at's rules with T = t_close, applied to each list on its
+ *     own — a position counts (is "found") when its owner's account table holds the id and the
+ *     account's own timestamp is not above a non-zero t_close.  Absent ids and the reserved ids (0,
+ *     2^128-1) are skipped; a repeated id is answered once per occurrence; an id may stand in both
+ *     lists (for netting the two lists are the same).
+ *   Rows: dense and row-major.  The found debit position of rank r (among the found debit positions,
+ *     in request order) and the found credit position of rank q give cell r * found_credit + q.
+ *     matched = found_debit * found_credit; count = min(matched, out_cap_cells): the cap cuts in that
+ *     order and may cut inside a debit row.  Bytes past count cells are not written.  A cell with no
+ *     record is present, and zero apart from its two ids.
+ *   A cell (d, c) sums over every live resident record r (liveness: tbgpu_get_account_transfers'
+ *     rule) whose debit account is d and whose credit account is c, with t_open < r.timestamp, and
+ *     r.timestamp <= t_close when t_close != 0.  Post and void records count too: the log holds them
+ *     with their accounts filled in.  Each adds one to `transfers`, and by kind
+ *         pending      pending_in  += amount
+ *         post         pending_out += P,  posted += amount
+ *         void         pending_out += P
+ *         any other    posted      += amount
+ *     modulo 2^128.  P and the orphan rule are tbgpu_get_account_balances': a void's P is its own
+ *     amount, and a post whose pending transfer is not resident uses P = its own amount.  The
+ *     direction matters: a record from c to d belongs to cell (c, d), and only where c is a found
+ *     debit position and d a found credit position.  A loaded record with d == c belongs to cell
+ *     (d, d), once.  With both lists the same, a debit row's sums are that account's debits_* fields
+ *     of tbgpu_get_account_statements less what it paid accounts outside the lists, and a credit
+ *     column's its credits_* fields likewise.
+ *   complete: 0 when any transfer was ever evicted (any shard), or when an orphan post entered a cell
+ *     of the matrix, whether or not that cell lies under the cap; 1 otherwise.  An orphan post outside
+ *     the period, or with a side that was not asked for, does not drop it: narrower than
+ *     tbgpu_get_account_statements' rule, which also sums what lies above t_close and every record
+ *     that names one requested account.
+ *   t_open or t_close equal to 2^64-1, or a non-zero t_close below t_open, returns TBGPU_STATUS_OK
+ *     with count = matched = 0.  n_debit == 0 or n_credit == 0 returns TBGPU_STATUS_OK and writes
+ *     nothing.  n_debit * n_credit > TBGPU_FLOW_MATRIX_CELLS_MAX (computed in 64 bits), or a NULL
+ *     debit_ids, credit_ids, out or result while both counts are non-zero, is TBGPU_STATUS_INVALID and
+ *     writes nothing.  After any failing status the result names no cell.
+ *   The call contract of tbgpu_get_account_statements: synchronous, drains a pending
+ *     tbgpu_commit_device_async first, a read that changes nothing, works on an engine a device panic
+ *     stopped, allocates nothing after tbgpu_init, legal beside an asynchronous write-back.
+ *   A node engine has the same contract: every home shard scans its own log on its own device and
+ *     stream, side by side, reading a post's pending transfer on the home shard of its pending_id;
+ *     whether an account existed at t_close comes from its owner shard only; the host adds the shards'
+ *     sums and builds the cells by the device's cell function. */
+#define TBGPU_FLOW_MATRIX_CELLS_MAX 4095u   /* n_debit * n_credit; 96 B cells in one message body */
+typedef struct tbgpu_flow_cell {            /* 96 bytes, little-endian, no padding */
+    uint64_t debit_id_lo, debit_id_hi;
+    uint64_t credit_id_lo, credit_id_hi;
+    uint64_t posted[2];                     /* amounts posted d -> c: single-phase transfers and posts */
+    uint64_t pending_in[2];                 /* holds placed d -> c */
+    uint64_t pending_out[2];                /* holds released d -> c: P of posts and voids */
+    uint64_t transfers;                     /* records of the period that name d as debit and c as credit */
+    uint64_t reserved;                      /* zero */
+} tbgpu_flow_cell;
+int tbgpu_get_account_flow_matrix(tbgpu_t* engine, uint64_t t_open, uint64_t t_close,
+        const void* debit_ids /* n_debit x {lo, hi} */, uint32_t n_debit,
+        const void* credit_ids /* n_credit x {lo, hi} */, uint32_t n_credit,
+        void* out, uint32_t out_cap_cells, tbgpu_query_result* result);
 
 /* The replica writes StateMachine.commit_timestamp itself: the header timestamp after every commit
  * (src/vsr/replica.zig:3664-3665) and the checkpoint's value on open / state sync.  The wrapper

@@ -123,6 +123,16 @@ INTEGRALS_MAX = 4095  # TBGPU_INTEGRALS_MAX
 SERIES_ROWS_MAX = 4095  # TBGPU_SERIES_ROWS_MAX
 
 
+class tbgpu_flow_cell(ctypes.Structure):
+    _fields_ = [("debit_id_lo", ctypes.c_uint64), ("debit_id_hi", ctypes.c_uint64),
+                ("credit_id_lo", ctypes.c_uint64), ("credit_id_hi", ctypes.c_uint64),
+                ("posted", ctypes.c_uint64 * 2), ("pending_in", ctypes.c_uint64 * 2), ("pending_out", ctypes.c_uint64 * 2),
+                ("transfers", ctypes.c_uint64), ("reserved", ctypes.c_uint64)]
+
+
+FLOW_MATRIX_CELLS_MAX = 4095  # TBGPU_FLOW_MATRIX_CELLS_MAX
+
+
 class tbgpu_stats(ctypes.Structure):
     _fields_ = [
         ("passes", ctypes.c_uint64),
@@ -252,6 +262,7 @@ SIGNATURES = [
     ("tbgpu_get_account_statements", ctypes.c_int, [_P, _U64, _U64, _P, _U32, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_get_account_balance_integrals", ctypes.c_int, [_P, _U64, _U64, _P, _U32, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_get_account_statement_series", ctypes.c_int, [_P, _P, _U32, _P, _U32, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
+    ("tbgpu_get_account_flow_matrix", ctypes.c_int, [_P, _U64, _U64, _P, _U32, _P, _U32, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_query_transfers", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_query_accounts", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_bench_query_keys_max", ctypes.c_int, [_P, _U32]),

@@ -23,6 +23,26 @@ static inline std::vector<uint32_t> scan_first_positions(const uint64_t* ids, ui
     return index;
 }
 
+// The flow matrix's maps (k_matrix.h).  The request is two lists laid end to end, n_debit debit ids and
+// then n_credit credit ids, and `first` is scan_first_positions over all of them.  row_of[index] = the
+// first debit position that names the id whose index is `index`, col_of[index] = its first credit
+// position (counted from the credit list's start), SCAN_PAIR_NONE where that list does not name it.
+// Entries of positions that are no id's index stay SCAN_PAIR_NONE.  row_of, col_of: n_debit + n_credit
+// entries each.
+static constexpr uint16_t SCAN_PAIR_NONE = 0xFFFFu;
+static inline void scan_pair_maps(const std::vector<uint32_t>& first, uint32_t n_debit, uint32_t n_credit, uint16_t* row_of,
+                                  uint16_t* col_of) {
+    const uint32_t n = n_debit + n_credit;
+    std::fill(row_of, row_of + n, SCAN_PAIR_NONE);
+    std::fill(col_of, col_of + n, SCAN_PAIR_NONE);
+    for (uint32_t i = 0; i < n_debit; i++) {
+        if (first[i] == i) row_of[i] = (uint16_t)i;  // (a debit position's first is a debit position)
+    }
+    for (uint32_t i = n_debit; i < n; i++) {  // ascending: the first credit position stays
+        if (col_of[first[i]] == SCAN_PAIR_NONE) col_of[first[i]] = (uint16_t)(i - n_debit);
+    }
+}
+
 // A bin's layout: runs of `count` sums of `words` 64-bit words each, low word first — 2: a 128-bit
 // sum, 3: a 192-bit sum, 1: a plain count.
 struct ScanBinRun {

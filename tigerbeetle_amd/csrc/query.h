@@ -1,7 +1,8 @@
 // query.h — the host side of the queries (include/tbgpu.h): get_account_transfers and its batched form
 // get_account_transfers_many, get_account_balances, query_transfers, query_accounts,
 // get_change_events, lookup_accounts_at, get_ledger_balances, get_pending_transfers,
-// get_account_statements, get_account_balance_integrals and get_account_statement_series; their buffers, made at tbgpu_init, and their entry points.  Included by engine.hip after the engine's own helpers and before node.h.
+// get_account_statements, get_account_balance_integrals, get_account_statement_series and
+// get_account_flow_matrix; their buffers, made at tbgpu_init, and their entry points.  Included by engine.hip after the engine's own helpers and before node.h.
 //
 // Every query is written once, over a list of engines (QueryCall): the one engine, or a node's shards.
 // A transfer lives on its home shard only and an account is answered by its owner only, so every
@@ -184,6 +185,15 @@ struct SeriesBufs {
 };
 #define SERIES_BIN_BYTES(keys) (((u64)(keys) * SERIES_BIN_WORDS + 1) * 8)
 
+// tbgpu_get_account_flow_matrix (k_matrix.h): an AccountScanBufs of its own (QueryState::qx) — its
+// request is two lists, up to MATRIX_IDS_MAX positions, one more than the statements call's hold —
+// with bins by key and 96-B cells, and the two maps that go up with the ids.
+struct MatrixBufs {
+    u16* d_maps = nullptr;  // [2][MATRIX_IDS_MAX] row_of, then col_of, each as long as the request
+    u16* h_maps = nullptr;  // pinned: the host builds them here (a node: in every shard's)
+};
+#define MATRIX_BIN_BYTES(keys) (((u64)(keys) * MATRIX_BIN_WORDS + 1) * 8)
+
 // One engine's query buffers (tbgpu::qs), in the order query_init makes them.
 struct QueryState {
     QueryBufs q;
@@ -197,6 +207,8 @@ struct QueryState {
     AccountScanBufs qt;
     IntegralBufs qi;
     SeriesBufs qr;
+    AccountScanBufs qx;
+    MatrixBufs qxm;
 };
 
 // One AccountScanBufs for `ids` request ids: in this order, which tests/test_gpu_alloc.py counts by.
@@ -333,6 +345,16 @@ static int query_init(tbgpu* E) {
         HIPCK(tbHostMalloc(E->own, &R.h_bounds, (u64)(SERIES_ROWS_MAX + 1) * 8, hipHostMallocDefault));
         HIPCK(tbMalloc(E->own, &R.d_bins, SERIES_BIN_BYTES(SERIES_KEYS_MAX)));
         HIPCK(tbHostMalloc(E->own, &R.h_bins, SERIES_BIN_BYTES(SERIES_KEYS_MAX), hipHostMallocDefault));
+    }
+    // tbgpu_get_account_flow_matrix: the ids of both lists, the set, the bins by key, the accounts, the cells, the result words
+    if (const int st = account_scan_bufs_init(E, E->qs->qx, MATRIX_IDS_MAX, tb_change_set_slots(MATRIX_IDS_MAX),
+                                              MATRIX_BIN_BYTES(MATRIX_CELLS_MAX), MATRIX_CELL_BYTES)) {
+        return st;
+    }
+    {  // ... and its maps
+        MatrixBufs& X = E->qs->qxm;
+        HIPCK(tbMalloc(E->own, &X.d_maps, (u64)MATRIX_IDS_MAX * 4));
+        HIPCK(tbHostMalloc(E->own, &X.h_maps, (u64)MATRIX_IDS_MAX * 4, hipHostMallocDefault));
     }
     return TBGPU_STATUS_OK;
 }
@@ -1373,16 +1395,24 @@ static int account_scan_finish(tbgpu* E, const AccountScan& s, u32 cap, void* ou
     return TBGPU_STATUS_OK;
 }
 
-template <typename ROWS>
-static int account_scan_run(const QueryCall& c, const AccountScan& s, const NodeTablesArgs& NT, u32 cap, void* out,
-                            tbgpu_query_result* result, ROWS rows) {
+// The driver.  `node()` writes a node's answer from its shards' pinned mirrors, once every shard is back.
+template <typename NODE>
+static int account_scan_run_node(const QueryCall& c, const AccountScan& s, const NodeTablesArgs& NT, u32 cap, void* out,
+                                 tbgpu_query_result* result, NODE node) {
     const bool one = c.world == 1;
     const u32 asked = s.scan ? c.world : 1;  // without a scan nothing is summed: a node's first shard gathers alone
     const int st = query_side_by_side(c.Es, asked, [&](u32 d) -> int { return account_scan_enqueue(c.Es[d], s, NT, d, one, cap); });
     if (st) return query_end(result, st);
     if (one) return account_scan_finish(c.Es[0], s, cap, out, result);
-    account_scan_node_rows(c, s, cap, (u8*)out, result, rows);
+    node();
     return TBGPU_STATUS_OK;
+}
+
+// The driver of a call whose rows go by request position: a node's answer is account_scan_node_rows'.
+template <typename ROWS>
+static int account_scan_run(const QueryCall& c, const AccountScan& s, const NodeTablesArgs& NT, u32 cap, void* out,
+                            tbgpu_query_result* result, ROWS rows) {
+    return account_scan_run_node(c, s, NT, cap, out, result, [&] { account_scan_node_rows(c, s, cap, (u8*)out, result, rows); });
 }
 
 // lookup_accounts_at (k_asof.h).  Its own: T = 0 asks for the records as they are, without a scan; the
@@ -1610,6 +1640,110 @@ extern "C" int tbgpu_get_account_statement_series(tbgpu_t* E, const uint64_t* bo
         }
         return written;
     });
+}
+
+// get_account_flow_matrix (k_matrix.h): the request is the two lists laid end to end, T = t_close, the
+// key is the pair.  The host builds the maps from the ids and sends them up before the scan.  Rows
+// are a product of two found lists, so a node's answer has a loop of its own: for every found pair
+// under the cap, the sum of every shard's bin of key (row_of, col_of), written by the device's cell
+// function.
+static constexpr ScanBinRun MATRIX_BIN_LAYOUT[] = {{2, 3}, {1, 1}};
+static void matrix_node_cells(const QueryCall& c, const AccountScan& s, u32 n_debit, u32 n_credit, const std::vector<u32>& first,
+                              u32 cap, u8* out, tbgpu_query_result* result) {
+    const AccountScanBufs& B = c.Es[0]->qs->*s.bufs;
+    const u16 *row_of = c.Es[0]->qs->qxm.h_maps, *col_of = row_of + s.n;
+    u64 found_debit = 0, found_credit = 0;
+    for (u32 i = 0; i < n_debit; i++) found_debit += B.h_found[i] != 0;
+    for (u32 i = n_debit; i < s.n; i++) found_credit += B.h_found[i] != 0;
+    const u64 matched = found_debit * found_credit;
+    u64 at = 0;
+    for (u32 i = 0; i < n_debit && at < cap; i++) {
+        if (!B.h_found[i]) continue;
+        for (u32 j = n_debit; j < s.n && at < cap; j++) {
+            if (!B.h_found[j]) continue;
+            const u64 key = (u64)row_of[first[i]] * n_credit + col_of[first[j]];
+            u64 sum[MATRIX_BIN_WORDS] = {}, cell[MATRIX_CELL_BYTES / 8];
+            for (u32 d = 0; d < c.world; d++) scan_bins_add(sum, s.bins(*c.Es[d]->qs).h + key * MATRIX_BIN_WORDS, s.layout, s.n_runs, 1);
+            tb_matrix_cell(B.h_ids + 2 * (u64)i, B.h_ids + 2 * (u64)j, sum, cell);
+            memcpy(out + at * MATRIX_CELL_BYTES, cell, sizeof cell);
+            at++;
+        }
+    }
+    for (u32 d = 0; d < c.world; d++) {
+        if (s.bins(*c.Es[d]->qs).h[s.flag_word]) result->complete = 0;
+    }
+    result->count = (u32)at;
+    result->matched = matched;
+}
+
+extern "C" int tbgpu_get_account_flow_matrix(tbgpu_t* E, uint64_t t_open, uint64_t t_close, const void* debit_ids, uint32_t n_debit,
+                                             const void* credit_ids, uint32_t n_credit, void* out, uint32_t out_cap_cells,
+                                             tbgpu_query_result* result) {
+    static_assert(sizeof(tbgpu_flow_cell) == MATRIX_CELL_BYTES && MATRIX_CELLS_MAX == TBGPU_FLOW_MATRIX_CELLS_MAX &&
+                      MATRIX_IDS_MAX == MATRIX_CELLS_MAX + 1 && MATRIX_NONE == SCAN_PAIR_NONE && MATRIX_IDS_MAX <= MATRIX_NONE &&
+                      MATRIX_IDS_MAX == MATRIX_EMIT_CHUNK * QUERY_THREADS && scan_bin_words(MATRIX_BIN_LAYOUT, 2) == MATRIX_BIN_WORDS &&
+                      (MATRIX_BIN_WORDS + 5) * 8 == MATRIX_CELL_BYTES,
+                  "k_matrix.h's constants are the header's and account_scan_host.h's");
+    // 4,096 positions: 8,192 slots of 32 bits, as CHANGE_LDS_BINS_SLOTS_MAX, and an index + 1 fits an entry's 16 bits.
+    static_assert((size_t)CHANGE_LDS_BINS_SLOTS_MAX * 4 + (size_t)MATRIX_IDS_MAX * 4 + (size_t)MATRIX_LDS_BINS * (MATRIX_BIN_WORDS * 8 + 4) <=
+                      65536,
+                  "set, maps, bins and tags stay within 64 KB a workgroup");
+    API_ENTER(E, false);
+    if (n_debit == 0 || n_credit == 0) return TBGPU_STATUS_OK;
+    if ((u64)n_debit * n_credit > TBGPU_FLOW_MATRIX_CELLS_MAX) {
+        return fail(TBGPU_STATUS_INVALID, "get_account_flow_matrix: %u x %u ids (at most %u cells)", n_debit, n_credit,
+                    TBGPU_FLOW_MATRIX_CELLS_MAX);
+    }
+    if (!credit_ids) return fail(TBGPU_STATUS_INVALID, "get_account_flow_matrix: NULL ids, out or result");
+    const u32 n = n_debit + n_credit;  // at most MATRIX_IDS_MAX: the product is at most 4,095
+    QueryCall c;
+    NodeTablesArgs NT;
+    if (const int st = account_scan_begin(E, "get_account_flow_matrix", &QueryState::qx, n_debit, MATRIX_IDS_MAX, debit_ids, out, result, &c,
+                                          &NT, [&] { return t_open != ~0ULL && t_close != ~0ULL && (t_close == 0 || t_close >= t_open); })) {
+        return st == SCAN_ANSWERED ? TBGPU_STATUS_OK : st;
+    }
+    // The debit ids are in every shard's pinned buffer; the credit ids go behind them, and the maps beside.
+    const std::vector<u32> first = [&] {
+        u64* h_ids = c.Es[0]->qs->qx.h_ids;
+        memcpy(h_ids + 2 * (u64)n_debit, credit_ids, (u64)n_credit * 16);
+        return scan_first_positions(h_ids, n);
+    }();
+    scan_pair_maps(first, n_debit, n_credit, c.Es[0]->qs->qxm.h_maps, c.Es[0]->qs->qxm.h_maps + n);
+    for (u32 d = 1; d < c.world; d++) {
+        memcpy(c.Es[d]->qs->qx.h_ids + 2 * (u64)n_debit, credit_ids, (u64)n_credit * 16);
+        memcpy(c.Es[d]->qs->qxm.h_maps, c.Es[0]->qs->qxm.h_maps, (u64)n * 4);
+    }
+    const u32 n_keys = n_debit * n_credit;
+    AccountScan s{};
+    s.name = "get_account_flow_matrix", s.unit = "cells", s.asked = std::to_string(n_debit) + " x " + std::to_string(n_credit) + " ids";
+    s.bufs = &QueryState::qx, s.bins = [](QueryState& q) { return ScanBins{q.qx.d_bins, q.qx.h_bins}; };
+    s.n = n, s.T = t_close, s.scan = true;
+    s.bin_bytes = MATRIX_BIN_BYTES(n_keys), s.flag_word = (u64)n_keys * MATRIX_BIN_WORDS;
+    s.layout = MATRIX_BIN_LAYOUT, s.n_runs = 2, s.keys_per_id = 1, s.row_bytes = MATRIX_CELL_BYTES;
+    s.rows_per_id = std::max(n_debit, n_credit);  // matched = found_debit * found_credit <= n * the longer list
+    const auto maps_up = [=](const ScanLaunch& L) -> int {
+        const MatrixBufs& X = L.E->qs->qxm;
+        HIPCK(hipMemcpyAsync(X.d_maps, X.h_maps, (u64)n * 4, hipMemcpyHostToDevice, L.E->stream));
+        return TBGPU_STATUS_OK;
+    };
+    s.launch_scan = [=](const ScanLaunch& L) -> int {
+        if (const int st = maps_up(L)) return st;
+        hipLaunchKernelGGL(tb_matrix_effects, dim3(L.nb), dim3(CHANGE_THREADS), tb_matrix_lds_bytes(L.slots, n), L.E->stream, L.NT, L.self,
+                           L.records, t_open, t_close, (const u32*)L.B.d_set, L.mask, (const u64*)L.B.d_ids, n,
+                           (const u16*)L.E->qs->qxm.d_maps, n_credit, n_keys, L.d_bins);
+        return TBGPU_STATUS_OK;
+    };
+    s.launch_emit = [=](const ScanLaunch& L) -> int {
+        if (L.nb == 0) {  // an empty log: no scan took the maps up
+            if (const int st = maps_up(L)) return st;
+        }
+        hipLaunchKernelGGL(tb_matrix_emit, dim3((n_keys + QUERY_THREADS - 1) / QUERY_THREADS), dim3(QUERY_THREADS), 0, L.E->stream,
+                           (const u64*)L.B.d_ids, n_debit, n_credit, (const u32*)L.B.d_found, (const u32*)L.B.d_set, L.mask,
+                           (const u16*)L.E->qs->qxm.d_maps, (const u64*)L.d_bins, L.cap, L.B.d_out, L.B.d_res);
+        return TBGPU_STATUS_OK;
+    };
+    return account_scan_run_node(c, s, NT, out_cap_cells, out, result,
+                                 [&] { matrix_node_cells(c, s, n_debit, n_credit, first, out_cap_cells, (u8*)out, result); });
 }
 
 // ---- get_ledger_balances (k_ledgers.h, include/tbgpu.h) -------------------------------------------

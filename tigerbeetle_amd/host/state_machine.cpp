@@ -349,6 +349,14 @@ tbgpu_query_result StateMachine::get_account_statement_series(const uint64_t* bo
     return r;
 }
 
+tbgpu_query_result StateMachine::get_account_flow_matrix(uint64_t t_open, uint64_t t_close, const void* debit_ids, uint32_t n_debit,
+                                                         const void* credit_ids, uint32_t n_credit, void* out, uint32_t out_cap_cells) {
+    tbgpu_query_result r{};
+    check(tbgpu_get_account_flow_matrix(engine_, t_open, t_close, debit_ids, n_debit, credit_ids, n_credit, out, out_cap_cells, &r),
+          "get_account_flow_matrix");
+    return r;
+}
+
 tbgpu_query_result StateMachine::query_transfers(const tbgpu_query_filter& filter, void* out, uint32_t out_cap_records) {
     tbgpu_query_result r{};
     check(tbgpu_query_transfers(engine_, &filter, out, out_cap_records, &r), "query_transfers");

@@ -312,6 +312,17 @@ public:
     tbgpu_query_result get_account_statement_series(const uint64_t* bounds, uint32_t n_buckets, const void* ids, uint32_t n, void* out,
                                                     uint32_t out_cap_rows);
 
+    // Who paid whom over (t_open, t_close] (tbgpu_get_account_flow_matrix; a read, and no reference
+    // operation behind it): one tbgpu_flow_cell per pair of a found position of debit_ids and a found
+    // position of credit_ids, dense and row-major (debit rank * found credits + credit rank) — the
+    // amounts posted from the debit to the credit account, the holds placed and released and the number
+    // of records, all from one scan of the log.  Either list: n x {lo, hi}; n_debit * n_credit is at
+    // most TBGPU_FLOW_MATRIX_CELLS_MAX; an id may stand in both.  result.matched is found debit x found
+    // credit positions; result.complete == 0: transfers were evicted or a post in a cell had lost its
+    // pending transfer.
+    tbgpu_query_result get_account_flow_matrix(uint64_t t_open, uint64_t t_close, const void* debit_ids, uint32_t n_debit,
+                                               const void* credit_ids, uint32_t n_credit, void* out, uint32_t out_cap_cells);
+
     // The field-filter queries (tbgpu_query_transfers / tbgpu_query_accounts; reads, not commits): the
     // resident transfers, or the accounts, whose user_data_128 / user_data_64 / user_data_32 / ledger /
     // code equal the filter's non-zero fields, by timestamp (newest first under TBGPU_QUERY_REVERSED),

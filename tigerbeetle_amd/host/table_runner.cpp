@@ -320,8 +320,11 @@ std::string run_table(tb::StateMachine& sm, const std::string& text) {
 // --query-series (tests/test_gpu_series_cpp.py): the prepares ending in {0, 0, the body's length, u32 n_buckets,
 // u32 n_ids, n_buckets + 1 bounds and n_ids ids}, answered by get_account_statement_series (the records are
 // tbgpu_account_statement rows).
+// --query-flow-matrix (tests/test_gpu_matrix_cpp.py): the prepares ending in {0, 0, the body's length, t_open,
+// t_close, u32 n_debit, u32 n_credit, n_debit debit ids and n_credit credit ids}, answered by
+// get_account_flow_matrix (the records are tbgpu_flow_cell cells).
 enum QueryKind { ACCOUNT_TRANSFERS, ACCOUNT_BALANCES, QUERY_TRANSFERS, QUERY_ACCOUNTS, CHANGE_EVENTS, ACCOUNT_TRANSFERS_MANY, ACCOUNTS_AT,
-                 LEDGER_BALANCES, PENDING_TRANSFERS, ACCOUNT_STATEMENTS, ACCOUNT_INTEGRALS, ACCOUNT_SERIES };
+                 LEDGER_BALANCES, PENDING_TRANSFERS, ACCOUNT_STATEMENTS, ACCOUNT_INTEGRALS, ACCOUNT_SERIES, ACCOUNT_FLOW_MATRIX };
 
 int run_query(tb::StateMachine& sm, QueryKind kind, const char* in_path, const char* out_path) {
     std::ifstream in(in_path, std::ios::binary);
@@ -452,6 +455,25 @@ int run_query(tb::StateMachine& sm, QueryKind kind, const char* in_path, const c
         printf("query: %u of %llu rows, complete %u\n", r.count, (unsigned long long)r.matched, r.complete);
         return o ? 0 : 2;
     }
+    if (kind == ACCOUNT_FLOW_MATRIX) {
+        uint64_t period[2] = {0, 0};
+        uint32_t head[2] = {0, 0};  // n_debit, n_credit
+        if (body.size() >= 24) memcpy(period, body.data(), 16), memcpy(head, body.data() + 16, 8);
+        if (body.size() < 24 || (uint64_t)head[0] * head[1] > TBGPU_FLOW_MATRIX_CELLS_MAX ||
+            body.size() != 24 + ((size_t)head[0] + head[1]) * 16) {
+            fprintf(stderr, "%s: t_open, t_close, n_debit, n_credit and the ids of 16 bytes, at most %u cells\n", in_path,
+                    TBGPU_FLOW_MATRIX_CELLS_MAX);
+            return 2;
+        }
+        std::vector<uint8_t> out((size_t)TBGPU_FLOW_MATRIX_CELLS_MAX * sizeof(tbgpu_flow_cell));
+        const tbgpu_query_result r = sm.get_account_flow_matrix(period[0], period[1], body.data() + 24, head[0],
+                                                                body.data() + 24 + (size_t)head[0] * 16, head[1], out.data(),
+                                                                TBGPU_FLOW_MATRIX_CELLS_MAX);
+        std::ofstream o(out_path, std::ios::binary);
+        o.write((const char*)&r, sizeof(r)).write((const char*)out.data(), (size_t)r.count * sizeof(tbgpu_flow_cell));
+        printf("query: %u of %llu cells, complete %u\n", r.count, (unsigned long long)r.matched, r.complete);
+        return o ? 0 : 2;
+    }
     if (kind == PENDING_TRANSFERS) {
         tbgpu_pending_filter pf;
         if (body.size() != sizeof(pf)) {
@@ -500,8 +522,9 @@ int main(int argc, char** argv) {
     const bool statements = argc > 1 && std::string(argv[1]) == "--query-statements";
     const bool integrals = argc > 1 && std::string(argv[1]) == "--query-integrals";
     const bool series = argc > 1 && std::string(argv[1]) == "--query-series";
-    const bool query = fields || balances || changes || many || at || ledgers || pending || statements || integrals || series || (argc > 1 && std::string(argv[1]) == "--query");
-    QueryKind kind = series ? ACCOUNT_SERIES : balances ? ACCOUNT_BALANCES : changes ? CHANGE_EVENTS : many ? ACCOUNT_TRANSFERS_MANY : at ? ACCOUNTS_AT : ledgers ? LEDGER_BALANCES : pending ? PENDING_TRANSFERS : statements ? ACCOUNT_STATEMENTS : integrals ? ACCOUNT_INTEGRALS : ACCOUNT_TRANSFERS;
+    const bool matrix = argc > 1 && std::string(argv[1]) == "--query-flow-matrix";
+    const bool query = matrix || fields || balances || changes || many || at || ledgers || pending || statements || integrals || series || (argc > 1 && std::string(argv[1]) == "--query");
+    QueryKind kind = matrix ? ACCOUNT_FLOW_MATRIX : series ? ACCOUNT_SERIES : balances ? ACCOUNT_BALANCES : changes ? CHANGE_EVENTS : many ? ACCOUNT_TRANSFERS_MANY : at ? ACCOUNTS_AT : ledgers ? LEDGER_BALANCES : pending ? PENDING_TRANSFERS : statements ? ACCOUNT_STATEMENTS : integrals ? ACCOUNT_INTEGRALS : ACCOUNT_TRANSFERS;
     const char* self = argv[0];
     if (fields && argc > 2) {
         const std::string which = argv[2];
@@ -521,8 +544,9 @@ int main(int argc, char** argv) {
                 "       %s --query-statements <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-integrals <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-series <prepares.bin> <answer.bin> [device]\n"
+                "       %s --query-flow-matrix <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-fields <transfers|accounts> <prepares.bin> <answer.bin> [device]\n",
-                self, self, self, self, self, self, self, self, self, self, self, self);
+                self, self, self, self, self, self, self, self, self, self, self, self, self);
         return 2;
     }
     if (query) {

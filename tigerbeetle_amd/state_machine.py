@@ -23,7 +23,7 @@ import numpy as np
 
 from . import _lib
 from .types import (ACCOUNT_BALANCE_DTYPE, ACCOUNT_DTYPE, ACCOUNT_FILTER_DTYPE, BATCH_MAX, CHANGE_EVENT_DTYPE, CHANGE_EVENTS_FILTER_DTYPE,
-                    CHANGE_EVENTS_MAX, LEDGER_BALANCE_DTYPE, LEDGERS_MAX, PENDING_FILTER_DTYPE, PENDING_ROW_DTYPE, PENDING_ROWS_MAX, PENDING_STATES, STATEMENT_DTYPE, INTEGRAL_DTYPE, FILTER_CREDITS, FILTER_DEBITS, FILTER_REVERSED, pack_change_events_filter, QUERY_FILTER_DTYPE, QUERY_REVERSED, TRANSFER_DTYPE, U64_MAX, Operation)
+                    CHANGE_EVENTS_MAX, LEDGER_BALANCE_DTYPE, LEDGERS_MAX, PENDING_FILTER_DTYPE, PENDING_ROW_DTYPE, PENDING_ROWS_MAX, PENDING_STATES, STATEMENT_DTYPE, INTEGRAL_DTYPE, FLOW_CELL_DTYPE, FILTER_CREDITS, FILTER_DEBITS, FILTER_REVERSED, pack_change_events_filter, QUERY_FILTER_DTYPE, QUERY_REVERSED, TRANSFER_DTYPE, U64_MAX, Operation)
 
 
 def average_balances(row):
@@ -35,6 +35,21 @@ def average_balances(row):
         return None
     return tuple(sum(int(row["integral_%s_w%d" % (c, k)]) << (64 * k) for k in range(3)) // length
                  for c in ("debits_pending", "debits_posted", "credits_pending", "credits_posted"))
+
+
+def net_positions(cells):
+    """The multilateral net of get_account_flow_matrix cells: {account id: the posted amount it received
+    minus the posted amount it paid}, as Python ints, over every account the cells name on either side.
+    A cell (d, c) adds its `posted` to c's position and takes it from d's; a cell (d, d) changes nothing.
+    With both lists the same the positions sum to zero."""
+    net = {}
+    for cell in cells:
+        d = int(cell["debit_id_lo"]) | int(cell["debit_id_hi"]) << 64
+        c = int(cell["credit_id_lo"]) | int(cell["credit_id_hi"]) << 64
+        posted = int(cell["posted_lo"]) | int(cell["posted_hi"]) << 64
+        net[d] = net.get(d, 0) - posted
+        net[c] = net.get(c, 0) + posted
+    return net
 
 
 @dataclass
@@ -589,6 +604,48 @@ class Engine:
                                                                ctypes.byref(res)))
         return out[:res.count], int(res.matched), bool(res.complete)
 
+    FLOW_MATRIX_CELLS_MAX = 4095  # TBGPU_FLOW_MATRIX_CELLS_MAX
+
+    def get_account_flow_matrix(self, debit_ids, credit_ids, t_open, t_close, out_cap_cells=None):
+        """Who paid whom over the period (t_open, t_close] (tbgpu_get_account_flow_matrix): one
+        FLOW_CELL_DTYPE cell per pair of a found position of `debit_ids` and a found position of
+        `credit_ids`, dense and row-major (debit rank * found credits + credit rank), with the amounts
+        posted from the debit to the credit account, the holds placed and released, and the number of
+        records.  A position is found as get_account_statements finds it at t_close; a repeated id is
+        answered once per occurrence, and an id may stand in both lists.  len(debit_ids) *
+        len(credit_ids) is at most FLOW_MATRIX_CELLS_MAX.  t_open 0: from before every record;
+        t_close 0: up to now.  Returns (cells, matched, complete); `complete` is False once the
+        engine has evicted transfers or a post in a cell had lost its pending transfer.  An invalid
+        period matches nothing.  net_positions(cells) is the multilateral net."""
+        debit_ids, credit_ids = [int(i) for i in debit_ids], [int(i) for i in credit_ids]
+        if len(debit_ids) * len(credit_ids) > self.FLOW_MATRIX_CELLS_MAX:
+            raise ValueError("at most %d cells in one call" % self.FLOW_MATRIX_CELLS_MAX)
+        return self.get_account_flow_matrix_raw(b"".join(i.to_bytes(16, "little") for i in debit_ids),
+                                                b"".join(i.to_bytes(16, "little") for i in credit_ids), t_open, t_close, out_cap_cells)
+
+    def get_account_flow_matrix_raw(self, debit_id_bytes, credit_id_bytes, t_open, t_close, out_cap_cells=None):
+        """get_account_flow_matrix from the two lists' bytes, 16 an id ({lo, hi}, little-endian)."""
+        debit_id_bytes, credit_id_bytes = bytes(debit_id_bytes), bytes(credit_id_bytes)
+        if len(debit_id_bytes) % 16 != 0 or len(credit_id_bytes) % 16 != 0:
+            raise ValueError("an id is 16 bytes")
+        n_debit, n_credit = len(debit_id_bytes) // 16, len(credit_id_bytes) // 16
+        if n_debit * n_credit > self.FLOW_MATRIX_CELLS_MAX:
+            raise ValueError("at most %d cells in one call" % self.FLOW_MATRIX_CELLS_MAX)
+        if any(int(t) < 0 or int(t) >> 64 for t in (t_open, t_close)):
+            raise ValueError("a timestamp is 64 bits")
+        if n_debit == 0 or n_credit == 0:  # the library returns at once and leaves its result alone
+            return np.zeros(0, dtype=FLOW_CELL_DTYPE), 0, True
+        cap = n_debit * n_credit if out_cap_cells is None else int(out_cap_cells)
+        if cap < 0 or cap >> 32:
+            raise ValueError("out_cap_cells is 32 bits")
+        out = np.zeros(max(cap, 1), dtype=FLOW_CELL_DTYPE)
+        res = _lib.tbgpu_query_result()
+        debit = ctypes.create_string_buffer(debit_id_bytes, len(debit_id_bytes))
+        credit = ctypes.create_string_buffer(credit_id_bytes, len(credit_id_bytes))
+        _lib.check(self.lib.tbgpu_get_account_flow_matrix(self.h, int(t_open), int(t_close), debit, n_debit, credit, n_credit,
+                                                          out.ctypes.data, cap, ctypes.byref(res)))
+        return out[:res.count], int(res.matched), bool(res.complete)
+
     @staticmethod
     def query_filter(user_data_128=0, user_data_64=0, user_data_32=0, ledger=0, code=0, *, reversed=False,
                      timestamp_min=0, timestamp_max=0, limit=8190):
@@ -988,6 +1045,14 @@ class StateMachine:
     def get_account_statement_series(self, ids, bounds, cap=None):
         """Statement headers per bucket (Engine.get_account_statement_series): a read, not a commit."""
         return self.engine.get_account_statement_series(ids, bounds, cap)
+
+    def get_account_flow_matrix(self, debit_ids, credit_ids, t_open, t_close, out_cap_cells=None):
+        """Who paid whom over a period (Engine.get_account_flow_matrix): a read, not a commit."""
+        return self.engine.get_account_flow_matrix(debit_ids, credit_ids, t_open, t_close, out_cap_cells)
+
+    def get_account_flow_matrix_raw(self, debit_id_bytes, credit_id_bytes, t_open, t_close, out_cap_cells=None):
+        """The same from the two lists' bytes (Engine.get_account_flow_matrix_raw)."""
+        return self.engine.get_account_flow_matrix_raw(debit_id_bytes, credit_id_bytes, t_open, t_close, out_cap_cells)
 
     def query_transfers(self, **filter):
         """The field-filter query over transfers (Engine.query_transfers): a read, not a commit."""

@@ -158,6 +158,15 @@ INTEGRALS_MAX = 4095
 # tbgpu_get_account_statement_series: STATEMENT_DTYPE rows, ids x buckets of them at most.
 SERIES_ROWS_MAX = 4095
 
+# tbgpu_flow_cell (include/tbgpu.h tbgpu_get_account_flow_matrix): 96 bytes, no padding; what the debit
+# account paid the credit account over the period — posted amounts, holds placed, holds released — and
+# the number of records.
+FLOW_CELL_DTYPE = np.dtype(
+    _u128("debit_id") + _u128("credit_id") + _u128("posted") + _u128("pending_in") + _u128("pending_out")
+    + [("transfers", "<u8"), ("reserved", "<u8")])
+assert FLOW_CELL_DTYPE.itemsize == 96
+FLOW_MATRIX_CELLS_MAX = 4095
+
 # tbgpu_query_filter (include/tbgpu.h tbgpu_query_transfers / tbgpu_query_accounts): 64 bytes, no padding.
 QUERY_FILTER_DTYPE = np.dtype(
     _u128("user_data_128") + [("user_data_64", "<u8"), ("user_data_32", "<u4"), ("ledger", "<u4"), ("code", "<u2"),

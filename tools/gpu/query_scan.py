@@ -1,7 +1,7 @@
 """The account-filter scan (tbgpu_get_account_transfers, csrc/k_query.h) over a 16M-transfer log (2 GB)
 against a device-to-device copy of the same log range, in one process.
 
-usage: python tools/gpu/query_scan.py [transfers] [runs] [--only account|fields|balances|change_events|many|asof|ledgers|pending|statements|integrals|series]
+usage: python tools/gpu/query_scan.py [transfers] [runs] [--only account|fields|balances|change_events|many|asof|ledgers|pending|statements|integrals|series|matrix]
 
 The log is built by the device generator, committed in place (the way tools/gpu/device_pass.py builds
 a pass): once with uniform C2 ids, where the queried account is a cold one (a few dozen matches), and
@@ -77,6 +77,14 @@ the whole log and --only statements' ids.  The yardsticks run in the same proces
 one tbgpu_get_account_statements call per bucket (three runs for 365 buckets and more), and one such call over
 the whole period.  An older library loaded through TBGPU_AB_LIB lacks the call: the yardsticks alone are
 timed then.
+
+`--only matrix` (tbgpu_get_account_flow_matrix) times the C call alone, into buffers made once,
+on both logs: 63 x 63 over the hottest accounts (both lists the same), 63 x 63 over random accounts of the
+log's middle, 1 x 4,095 and 4,095 x 1, each over the whole log and over its middle half.  The yardstick runs in
+the same process: one tbgpu_get_account_statements call over the same ids and period.  For the hot 63 x 63 leg
+over the whole log the host alternative the call replaces is timed once by the wall clock: every debit
+account's tbgpu_get_account_transfers pages, grouped by credit account in Python, and its cells are compared
+with the call's.  An older library loaded through TBGPU_AB_LIB lacks the call: the yardstick alone is timed then.
 """
 import json
 import os
@@ -667,6 +675,109 @@ def measure_series():
     return out
 
 
+def measure_matrix():
+    """get_account_flow_matrix beside get_account_statements over the same ids and period, on both logs, in one
+    process; and the host alternative for one leg."""
+    import ctypes
+    import time
+
+    from tigerbeetle_amd import _lib
+    os.environ["TBGPU_QUERY_COOP"] = "0"
+    e = Engine(Options(accounts_max=n_acct, transfers_max=n_xfer, pass_events_max=pb * batch, pass_batches_max=pb))
+    a_lens = batches(n_acct, batch)
+    a_ts, t = timestamps(a_lens, 1_000_000_000)
+    acct = e.alloc(n_acct * 128)
+    e.generate_accounts(acct, 0, n_acct, seed=42)
+    res = e.alloc(max(n_acct, n_xfer) * 8)
+    rb = e.alloc((n_xfer // batch + 2) * 4)
+    e.commit_device_async(128, a_ts, a_lens, acct, res, rb)
+    e.sync()
+    cells_max = 4095
+    have = hasattr(e.lib, "tbgpu_get_account_flow_matrix")  # an older library (TBGPU_AB_LIB): the yardstick alone
+    h_out = np.zeros(cells_max * 256, dtype=np.uint8)
+    h_res = _lib.tbgpu_query_result()
+    body_of = lambda ids: b"".join(i.to_bytes(16, "little") for i in ids)
+
+    def raw_matrix(debit, credit, t_open, t_close):
+        d_src = ctypes.create_string_buffer(body_of(debit), 16 * len(debit))
+        c_src = ctypes.create_string_buffer(body_of(credit), 16 * len(credit))
+        return lambda: _lib.check(e.lib.tbgpu_get_account_flow_matrix(e.h, t_open, t_close, d_src, len(debit), c_src, len(credit),
+                                                                      h_out.ctypes.data, cells_max, ctypes.byref(h_res)))
+
+    def raw_statements(ids, t_open, t_close):
+        src = ctypes.create_string_buffer(body_of(ids), 16 * len(ids))
+        return lambda: _lib.check(e.lib.tbgpu_get_account_statements(e.h, t_open, t_close, src, len(ids), h_out.ctypes.data, len(ids),
+                                                                      ctypes.byref(h_res)))
+
+    def paged(debit, credit, t_open, t_close):
+        """The host alternative: {(d, c): records}, from every debit account's pages of its debit side."""
+        wanted, groups = set(credit), {}
+        for d in debit:
+            t_min = t_open + 1
+            while True:
+                page, _, _ = e.get_account_transfers(d, credits=False, timestamp_min=t_min, timestamp_max=t_close, limit=8190)
+                for lo, hi in zip(page["credit_account_id_lo"].tolist(), page["credit_account_id_hi"].tolist()):
+                    c = lo | hi << 64
+                    if c in wanted:
+                        groups[(d, c)] = groups.get((d, c), 0) + 1
+                if len(page) < 8190:
+                    break
+                t_min = int(page["timestamp"][-1]) + 1
+        return groups
+
+    out = {}
+    for name, kind in (("uniform", "c2"), ("zipf", "c3")):
+        if name != "uniform":
+            e.reset_transfers()
+        log = e.log_window(n_xfer)
+        e.generate_transfers(log, 0, n_xfer, n_acct, seed=42, kind=KINDS[kind])
+        e.sync()
+        x_lens = batches(n_xfer, batch)
+        x_ts, t = timestamps(x_lens, t + 10)
+        e.commit_device_async(129, x_ts, x_lens, log, res, rb)
+        e.sync()
+        oldest, _, _ = e.query_transfers(limit=1)
+        newest, _, _ = e.query_transfers(reversed=True, limit=1)
+        t_first, t_last = int(oldest["timestamp"][0]), int(newest["timestamp"][0])
+        quarter = (t_last - t_first) // 4
+        sample = e.to_host(log + (n_xfer // 2) * 128, min(n_xfer // 2, 1 << 16) * 128).view(TRANSFER_DTYPE)
+        accounts, counts = np.unique(sample[["debit_account_id_lo", "debit_account_id_hi"]], return_counts=True)
+        hottest = np.argsort(-counts, kind="stable")[:cells_max]  # the Zipf log's hottest accounts; any of the uniform log's
+        hot = [int(lo) | (int(hi) << 64) for lo, hi in accounts[hottest].tolist()]
+        assert len(hot) == cells_max
+        pick = np.random.default_rng(7).choice(len(accounts), 63, replace=False)
+        anyone = [int(lo) | (int(hi) << 64) for lo, hi in accounts[pick].tolist()]
+        shapes = (("hot_63_x_63", hot[:63], hot[:63]), ("random_63_x_63", anyone, anyone), ("1_x_4095", hot[:1], hot),
+                  ("4095_x_1", hot, hot[:1]))
+        periods = (("whole_log", t_first - 1, t_last), ("middle_half", t_first + quarter, t_last - quarter))
+        for shape, debit, credit in shapes:
+            ids = list(dict.fromkeys(debit + credit))[:cells_max]
+            for leg, t_open, t_close in periods:
+                y_med, y_lo, y_hi = timed(e, raw_statements(ids, t_open, t_close))
+                entry = dict(debit_ids=len(debit), credit_ids=len(credit), statements_ms=round(y_med, 4), statements_min_ms=round(y_lo, 4),
+                             statements_max_ms=round(y_hi, 4))
+                if have:
+                    cells, matched, complete = e.get_account_flow_matrix(debit, credit, t_open, t_close)
+                    assert complete and matched == len(debit) * len(credit) == len(cells)
+                    med, lo_ms, hi_ms = timed(e, raw_matrix(debit, credit, t_open, t_close))
+                    entry = row(med, lo_ms, hi_ms, over_statements=round(med / y_med, 2), records_in_cells=int(cells["transfers"].sum()),
+                                **entry)
+                    if shape == "hot_63_x_63" and leg == "whole_log":
+                        start = time.perf_counter()
+                        groups = paged(debit, credit, t_open, t_close)
+                        entry["paged_on_host_ms"] = round((time.perf_counter() - start) * 1e3, 1)
+                        entry["over_paged_on_host"] = round(med / entry["paged_on_host_ms"], 5)
+                        mine = {}
+                        for c in cells[cells["transfers"] > 0]:
+                            key = (int(c["debit_id_lo"]) | int(c["debit_id_hi"]) << 64, int(c["credit_id_lo"]) | int(c["credit_id_hi"]) << 64)
+                            mine[key] = int(c["transfers"])
+                        assert mine == groups, (len(mine), len(groups))
+                        entry["cells_with_records"] = len(mine)
+                out["%s_matrix_%s_%s" % (name, shape, leg)] = entry
+    e.close()
+    return out
+
+
 def measure_ledgers():
     """get_ledger_balances beside query_accounts, query_transfers and the copies, in one process."""
     import ctypes
@@ -855,6 +966,8 @@ elif only == "integrals":
     result["integrals"] = measure_integrals()
 elif only == "series":
     result["series"] = measure_series()
+elif only == "matrix":
+    result["matrix"] = measure_matrix()
 elif only == "many":
     result["many"] = measure_many()
 elif only == "balances":
@@ -866,6 +979,6 @@ elif only != "fields":
     for shape in ("lane_per_record", "cooperative"):
         r = result[shape]
         r["bar_query_le_copy"] = all(v["ms"] <= r["copy_d2d"]["ms"] for k, v in r.items() if k != "copy_d2d")
-if only not in ("account", "balances", "change_events", "many", "asof", "ledgers", "pending", "statements", "integrals", "series"):
+if only not in ("account", "balances", "change_events", "many", "asof", "ledgers", "pending", "statements", "integrals", "series", "matrix"):
     result["field_filters"] = measure_fields()
 print(json.dumps(result))

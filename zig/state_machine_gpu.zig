@@ -861,6 +861,43 @@ pub fn StateMachineType(
             return @as(usize, result.count) * @sizeOf(tbgpu.tbgpu_account_statement);
         }
 
+        /// Who paid whom over (t_open, t_close] (tbgpu_get_account_flow_matrix; t_open 0: from
+        /// before every record, t_close 0: up to now): a read, with no operation in this reference's
+        /// enum, so nothing in commit() dispatches to it (INTEGRATION.md, "Account flow matrix").
+        /// Every pair of a found position of `debit_ids` and a found position of `credit_ids` yields
+        /// one cell of 96 bytes, dense and row-major, into `output`; returns the bytes written.
+        /// `complete` is false once transfers were evicted or a post in a cell had lost its pending
+        /// transfer.
+        pub fn get_account_flow_matrix(
+            self: *StateMachine,
+            t_open: u64,
+            t_close: u64,
+            debit_ids: []const u128,
+            credit_ids: []const u128,
+            output: []align(16) u8,
+            complete: *bool,
+        ) usize {
+            assert(debit_ids.len * credit_ids.len <= tbgpu.TBGPU_FLOW_MATRIX_CELLS_MAX);
+            var result: tbgpu.tbgpu_query_result = undefined;
+            result.count = 0;
+            result.complete = 1;
+            result.matched = 0;
+            check(tbgpu.tbgpu_get_account_flow_matrix(
+                self.engine,
+                t_open,
+                t_close,
+                debit_ids.ptr,
+                @intCast(debit_ids.len),
+                credit_ids.ptr,
+                @intCast(credit_ids.len),
+                output.ptr,
+                @intCast(output.len / @sizeOf(tbgpu.tbgpu_flow_cell)),
+                &result,
+            ));
+            complete.* = result.complete != 0;
+            return @as(usize, result.count) * @sizeOf(tbgpu.tbgpu_flow_cell);
+        }
+
         pub fn compact(self: *StateMachine, callback: *const fn (*StateMachine) void, op: u64) void {
             assert(self.compact_callback == null);
             assert(self.checkpoint_callback == null);
