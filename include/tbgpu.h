@@ -29,6 +29,7 @@
  *   (no reference: time-weighted balances over a period)   tbgpu_get_account_balance_integrals (likewise)
  *   (no reference: statements per bucket of a period)      tbgpu_get_account_statement_series (likewise)
  *   (no reference: who paid whom over a period)            tbgpu_get_account_flow_matrix (likewise)
+ *   (no reference: who an account dealt with)              tbgpu_get_account_counterparties (likewise)
  *   `setup` action of the table tests (:1398-1407)         tbgpu_test_set_balances (test only)
  *   StateMachine.commit_timestamp field (:251)             tbgpu_commit_timestamp
  *
@@ -944,6 +945,91 @@ int tbgpu_get_account_flow_matrix(tbgpu_t* engine, uint64_t t_open, uint64_t t_c
         const void* debit_ids /* n_debit x {lo, hi} */, uint32_t n_debit,
         const void* credit_ids /* n_credit x {lo, hi} */, uint32_t n_credit,
         void* out, uint32_t out_cap_cells, tbgpu_query_result* result);
+
+/* get_account_counterparties: who an account dealt with — for one subject account a and a period, one
+ * row per distinct account x that a paid or was paid by, with what went each way.  Every other read
+ * call here answers for accounts the caller already names (the flow matrix fills cells only for the
+ * payers it is given); this one discovers them: "who pays this merchant, and how much", "whom did this
+ * account pay last month", "the ten largest counterparties of this bank".  Paging
+ * tbgpu_get_account_transfers for the account and grouping on the host is one log scan per page; this
+ * call groups by the 128-bit counterparty id in one scan of the log in HBM and stores nothing at
+ * commit.  No reference has an operation for it.  An entry point of its own, as above; this comment is
+ * its specification.
+ *   The period is (t_open, t_close], exactly tbgpu_get_account_statements': t_open == 0 is read
+ *     literally (from before every record), t_close == 0 means up to now.
+ *   What matches: a live resident record r (liveness: tbgpu_get_account_transfers' rule) with
+ *     t_open < r.timestamp, and r.timestamp <= t_close when t_close != 0, that names a on a wanted
+ *     side.  TBGPU_FILTER_DEBITS wants the records whose debit account is a: each feeds `to` of the
+ *     row of its credit account.  TBGPU_FILTER_CREDITS wants the records whose credit account is a:
+ *     each feeds `from` of the row of its debit account.  Post and void records count too, as in the
+ *     flow matrix.  A record adds one to `transfers`, and by kind
+ *         pending      pending_in  += amount
+ *         post         pending_out += P,  posted += amount
+ *         void         pending_out += P
+ *         any other    posted      += amount
+ *     modulo 2^128, exactly as a tbgpu_flow_cell; P and the orphan rule are
+ *     tbgpu_get_account_balances' (a void's P is its own amount; a post whose pending transfer is not
+ *     resident uses P = its own amount).  A loaded record with debit == credit == a belongs to row a:
+ *     it enters `to` when DEBITS is wanted and `from` when CREDITS is wanted.  The half of a side that
+ *     is not wanted is all zero.
+ *   No account table is read: the subject and the counterparties are ids as the records carry them.
+ *     A subject no record names gives no rows; a counterparty need not be in the account table; on a
+ *     node engine nothing depends on account owners.
+ *   A group is a distinct counterparty id x >= id_min (as 128-bit numbers; id_min 0: all) with at
+ *     least one matching record.  matched is the number of groups.
+ *   Order: by default by x ascending as a 128-bit number; a consumer pages with id_min = the last
+ *     id + 1.  Under TBGPU_COUNTERPARTIES_BY_VOLUME by volume = (to.posted + from.posted) mod 2^128,
+ *     descending, equal volumes by x ascending; that order has no cursor, id_min still narrows the
+ *     groups.
+ *   Rows: count = min(limit, out_cap_rows, TBGPU_COUNTERPARTIES_ROWS_MAX, matched) rows, the first in
+ *     that order.  Bytes past count rows are not written.
+ *   complete: 0 when any transfer was ever evicted (any shard), or when an orphan post matched —
+ *     whether or not its group is returned, and whether or not its counterparty is at or above
+ *     id_min; 1 otherwise.  An orphan post outside the period or on a side that is not wanted does
+ *     not drop it.
+ *   Identities.  For a returned x that the account table holds with a timestamp at or below a
+ *     non-zero t_close, `to` is byte for byte the seven sum words {posted, pending_in, pending_out,
+ *     transfers} of tbgpu_get_account_flow_matrix's cell (a, x) for the same period, and `from` those
+ *     of cell (x, a).  With id_min 0 and DEBITS, the sums of `to` over every group are a's
+ *     debits_pending_in, debits_pending_out, debits_posted_in and debit_transfers of
+ *     tbgpu_get_account_statements; `from` and CREDITS give the credits_* fields likewise.
+ *   An invalid filter is never a status: an account_id of 0 or 2^128-1, neither side bit, an unknown
+ *     flag bit (TBGPU_FILTER_REVERSED included), a non-zero reserved byte, t_open or t_close equal to
+ *     2^64-1, a non-zero t_close below t_open, or limit 0 return TBGPU_STATUS_OK with
+ *     count = matched = 0 and write nothing.  A NULL filter, out or result is TBGPU_STATUS_INVALID.
+ *     After any failing status the result names no row.
+ *   Capacity: an engine has room for at least accounts_max groups (a node engine: the node's
+ *     accounts_max).  Committed records name only accounts the table holds, so a committed log never
+ *     exceeds it.  A log built with tbgpu_load_transfers whose matching records name more distinct
+ *     counterparties than the engine has room for returns TBGPU_STATUS_INVALID, tbgpu_last_error
+ *     names the capacity, and nothing is written: never a partial answer.
+ *   The call contract of tbgpu_get_account_statements: synchronous, drains a pending
+ *     tbgpu_commit_device_async first, a read that changes nothing, works on an engine a device panic
+ *     stopped, allocates nothing after tbgpu_init, legal beside an asynchronous write-back.
+ *   A node engine returns the same bytes: every home shard scans its own log on its own device and
+ *     stream, side by side; a group's sums are the shards' sums added before the order is applied (a
+ *     counterparty's volume rank is a property of its total, not of any shard's part). */
+#define TBGPU_COUNTERPARTIES_BY_VOLUME (1u << 8)   /* order by volume descending; default: by id ascending */
+#define TBGPU_COUNTERPARTIES_ROWS_MAX 8191u        /* 128 B rows in one message body */
+typedef struct tbgpu_counterparty_filter {  /* 64 bytes, little-endian, no padding */
+    uint64_t account_id_lo, account_id_hi;  /* the subject account a */
+    uint64_t t_open, t_close;               /* the period (t_open, t_close] */
+    uint64_t id_min_lo, id_min_hi;          /* only counterparties with id >= id_min; 0: all */
+    uint32_t limit;
+    uint32_t flags;  /* TBGPU_FILTER_DEBITS | TBGPU_FILTER_CREDITS | TBGPU_COUNTERPARTIES_BY_VOLUME */
+    uint8_t  reserved[8];                   /* must be zero */
+} tbgpu_counterparty_filter;
+typedef struct tbgpu_counterparty_flow {    /* 56 bytes: a tbgpu_flow_cell without its ids and reserved word */
+    uint64_t posted[2], pending_in[2], pending_out[2];
+    uint64_t transfers;
+} tbgpu_counterparty_flow;
+typedef struct tbgpu_counterparty {         /* 128 bytes */
+    uint64_t id_lo, id_hi;                  /* the counterparty x */
+    tbgpu_counterparty_flow to;             /* a -> x: records whose debit account is a and credit account is x */
+    tbgpu_counterparty_flow from;           /* x -> a */
+} tbgpu_counterparty;
+int tbgpu_get_account_counterparties(tbgpu_t* engine, const tbgpu_counterparty_filter* filter,
+                                     void* out, uint32_t out_cap_rows, tbgpu_query_result* result);
 
 /* The replica writes StateMachine.commit_timestamp itself: the header timestamp after every commit
  * (src/vsr/replica.zig:3664-3665) and the checkpoint's value on open / state sync.  The wrapper

@@ -133,6 +133,27 @@ class tbgpu_flow_cell(ctypes.Structure):
 FLOW_MATRIX_CELLS_MAX = 4095  # TBGPU_FLOW_MATRIX_CELLS_MAX
 
 
+class tbgpu_counterparty_filter(ctypes.Structure):
+    _fields_ = [("account_id_lo", ctypes.c_uint64), ("account_id_hi", ctypes.c_uint64),
+                ("t_open", ctypes.c_uint64), ("t_close", ctypes.c_uint64),
+                ("id_min_lo", ctypes.c_uint64), ("id_min_hi", ctypes.c_uint64),
+                ("limit", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint8 * 8)]
+
+
+class tbgpu_counterparty_flow(ctypes.Structure):
+    _fields_ = [("posted", ctypes.c_uint64 * 2), ("pending_in", ctypes.c_uint64 * 2), ("pending_out", ctypes.c_uint64 * 2),
+                ("transfers", ctypes.c_uint64)]
+
+
+class tbgpu_counterparty(ctypes.Structure):
+    _fields_ = [("id_lo", ctypes.c_uint64), ("id_hi", ctypes.c_uint64),
+                ("to", tbgpu_counterparty_flow), ("from_", tbgpu_counterparty_flow)]
+
+
+COUNTERPARTIES_BY_VOLUME = 1 << 8  # TBGPU_COUNTERPARTIES_BY_VOLUME
+COUNTERPARTIES_ROWS_MAX = 8191  # TBGPU_COUNTERPARTIES_ROWS_MAX
+
+
 class tbgpu_stats(ctypes.Structure):
     _fields_ = [
         ("passes", ctypes.c_uint64),
@@ -263,6 +284,7 @@ SIGNATURES = [
     ("tbgpu_get_account_balance_integrals", ctypes.c_int, [_P, _U64, _U64, _P, _U32, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_get_account_statement_series", ctypes.c_int, [_P, _P, _U32, _P, _U32, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_get_account_flow_matrix", ctypes.c_int, [_P, _U64, _U64, _P, _U32, _P, _U32, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
+    ("tbgpu_get_account_counterparties", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_query_transfers", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_query_accounts", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_bench_query_keys_max", ctypes.c_int, [_P, _U32]),

@@ -364,7 +364,10 @@ static int node_init(TbNode* N, const tbgpu_config* config) {
         NodeDev& D = N->D[d];
         D.device = config->devices[d];
         sc.device = D.device;
-        if (const int st = tbgpu_init(&sc, &D.E)) return st;
+        query_groups_hint = config->accounts_max;  // get_account_counterparties groups over the node's accounts
+        const int st = tbgpu_init(&sc, &D.E);
+        query_groups_hint = 0;
+        if (st) return st;
     }
     // Peer access between distinct devices (a kernel on one reads the other's HBM over xGMI).
     for (u32 a = 0; a < W; a++) {

@@ -1,8 +1,8 @@
 // query.h — the host side of the queries (include/tbgpu.h): get_account_transfers and its batched form
 // get_account_transfers_many, get_account_balances, query_transfers, query_accounts,
 // get_change_events, lookup_accounts_at, get_ledger_balances, get_pending_transfers,
-// get_account_statements, get_account_balance_integrals, get_account_statement_series and
-// get_account_flow_matrix; their buffers, made at tbgpu_init, and their entry points.  Included by engine.hip after the engine's own helpers and before node.h.
+// get_account_statements, get_account_balance_integrals, get_account_statement_series,
+// get_account_flow_matrix and get_account_counterparties; their buffers, made at tbgpu_init, and their entry points.  Included by engine.hip after the engine's own helpers and before node.h.
 //
 // Every query is written once, over a list of engines (QueryCall): the one engine, or a node's shards.
 // A transfer lives on its home shard only and an account is answered by its owner only, so every
@@ -194,6 +194,24 @@ struct MatrixBufs {
 };
 #define MATRIX_BIN_BYTES(keys) (((u64)(keys) * MATRIX_BIN_WORDS + 1) * 8)
 
+// tbgpu_get_account_counterparties (k_counterparties.h): the group table, the select's per-tile counts,
+// state words and histograms, the collected keys and the answer; made by query_init and shared with
+// nothing.  The table has room for `groups` counterparties at a load of at most one half: the engine's
+// accounts_max, on a node's shard the node's (query_groups_hint: a peer's table is folded into the
+// first shard's slot for slot, and a group's sums must be whole before the order is applied).
+struct CounterpartyBufs {
+    u64 groups = 0;           // the capacity the header promises
+    u64 slots = 0;            // a power of two, at least 2 * groups
+    u64* d_table = nullptr;   // [slots][CP_SLOT_WORDS]
+    u32* d_counts = nullptr;  // [slots / QUERY_THREADS, rounded up] occupied slots per tile
+    u64* d_state = nullptr;   // [CP_WORDS], then the select's histograms: u32 [CP_PASSES_MAX][CP_BINS]
+    u64* h_state = nullptr;   // pinned mirror of the CP_WORDS
+    u64* d_keys = nullptr;    // [CP_ROWS_MAX][CP_KEY_STRIDE] the selected groups' keys and slots
+    u8* d_out = nullptr;      // [CP_ROWS_MAX] the answer's rows
+};
+// Set by node_init around its shards' tbgpu_init: the groups a shard's table must hold (0: its own accounts_max).
+static thread_local u64 query_groups_hint = 0;
+
 // One engine's query buffers (tbgpu::qs), in the order query_init makes them.
 struct QueryState {
     QueryBufs q;
@@ -209,6 +227,7 @@ struct QueryState {
     SeriesBufs qr;
     AccountScanBufs qx;
     MatrixBufs qxm;
+    CounterpartyBufs qk;
 };
 
 // One AccountScanBufs for `ids` request ids: in this order, which tests/test_gpu_alloc.py counts by.
@@ -355,6 +374,17 @@ static int query_init(tbgpu* E) {
         MatrixBufs& X = E->qs->qxm;
         HIPCK(tbMalloc(E->own, &X.d_maps, (u64)MATRIX_IDS_MAX * 4));
         HIPCK(tbHostMalloc(E->own, &X.h_maps, (u64)MATRIX_IDS_MAX * 4, hipHostMallocDefault));
+    }
+    {  // tbgpu_get_account_counterparties: the group table, the select's counts, state and keys, the rows
+        CounterpartyBufs& K = E->qs->qk;
+        K.groups = std::min<u64>(query_groups_hint ? query_groups_hint : E->cfg.accounts_max, 1ULL << 29);
+        K.slots = pow2_at_least(2 * K.groups);
+        HIPCK(tbMalloc(E->own, &K.d_table, K.slots * CP_SLOT_WORDS * 8));
+        HIPCK(tbMalloc(E->own, &K.d_counts, (K.slots + QUERY_THREADS - 1) / QUERY_THREADS * 4));
+        HIPCK(tbMalloc(E->own, &K.d_state, CP_STATE_BYTES));
+        HIPCK(tbHostMalloc(E->own, &K.h_state, (u64)CP_WORDS * 8, hipHostMallocDefault));
+        HIPCK(tbMalloc(E->own, &K.d_keys, (u64)CP_ROWS_MAX * CP_KEY_STRIDE * 8));
+        HIPCK(tbMalloc(E->own, &K.d_out, (u64)CP_ROWS_MAX * CP_ROW_BYTES));
     }
     return TBGPU_STATUS_OK;
 }
@@ -1744,6 +1774,140 @@ extern "C" int tbgpu_get_account_flow_matrix(tbgpu_t* E, uint64_t t_open, uint64
     };
     return account_scan_run_node(c, s, NT, out_cap_cells, out, result,
                                  [&] { matrix_node_cells(c, s, n_debit, n_credit, first, out_cap_cells, (u8*)out, result); });
+}
+
+// ---- get_account_counterparties (k_counterparties.h, include/tbgpu.h) ------------------------------
+// The groups are discovered on the device, so the call has a driver of its own: every engine zeroes
+// its group table and scans its own log, side by side; a node's first shard then folds its peers'
+// tables into its own, one merge kernel a peer, once every stream is idle; the select's passes, the
+// collect and the emit follow back to back on the first engine's stream, and only the state words and
+// the answer's rows cross PCIe.  One engine enqueues all of it at once.
+static bool counterparty_filter_valid(const tbgpu_counterparty_filter* f) {
+    if (tb_id_reserved(f->account_id_lo, f->account_id_hi)) return false;
+    if ((f->flags & (TBGPU_FILTER_DEBITS | TBGPU_FILTER_CREDITS)) == 0) return false;
+    if (f->flags & ~(u32)(TBGPU_FILTER_DEBITS | TBGPU_FILTER_CREDITS | TBGPU_COUNTERPARTIES_BY_VOLUME)) return false;
+    for (u32 i = 0; i < sizeof f->reserved; i++) {
+        if (f->reserved[i]) return false;
+    }
+    if (f->t_open == ~0ULL || f->t_close == ~0ULL || (f->t_close != 0 && f->t_close < f->t_open)) return false;
+    return f->limit != 0;
+}
+
+static int counterparty_enqueue_scan(tbgpu* E, const NodeTablesArgs& NT, u32 self, const CpFilter& F, bool mirror) {
+    CounterpartyBufs& K = E->qs->qk;
+    HIPCK(hipSetDevice(E->device));
+    HIPCK(hipMemsetAsync(K.d_table, 0, K.slots * CP_SLOT_WORDS * 8, E->stream));
+    HIPCK(hipMemsetAsync(K.d_state, 0, CP_STATE_BYTES, E->stream));
+    const u64 records = E->log_next, per = (u64)CHANGE_THREADS * CHANGE_TILES, nb = (records + per - 1) / per;
+    if (nb) {
+        hipLaunchKernelGGL(tb_cp_scan, dim3((unsigned)nb), dim3(CHANGE_THREADS), 0, E->stream, NT, self, records, F, K.d_table,
+                           (u32)(K.slots - 1), K.d_state);
+        HIPCK(hipGetLastError());
+    }
+    if (mirror) HIPCK(hipMemcpyAsync(K.h_state, K.d_state, (u64)CP_WORDS * 8, hipMemcpyDeviceToHost, E->stream));
+    return TBGPU_STATUS_OK;
+}
+
+// On the first engine's stream: the peers' tables folded in (a node), then count -> begin -> the
+// select's passes -> collect -> emit, and the state words on their way back.
+static int counterparty_enqueue_select(const QueryCall& c, const NodeTablesArgs& NT, u32 by_volume) {
+    tbgpu* E = c.Es[0];
+    CounterpartyBufs& K = E->qs->qk;
+    HIPCK(hipSetDevice(E->device));
+    const u32 mask = (u32)(K.slots - 1), k = c.k;
+    const unsigned nb = (unsigned)((K.slots + QUERY_THREADS - 1) / QUERY_THREADS), wide = (nb + CP_TILES - 1) / CP_TILES;
+    for (u32 d = 1; d < c.world; d++) {
+        hipLaunchKernelGGL(tb_cp_merge, dim3(nb), dim3(QUERY_THREADS), 0, E->stream, NT, (const u64*)c.Es[d]->qs->qk.d_table, K.d_table,
+                           mask, K.d_state);
+    }
+    u32* hist = (u32*)(K.d_state + CP_WORDS);
+    hipLaunchKernelGGL(tb_cp_count, dim3(nb), dim3(QUERY_THREADS), 0, E->stream, NT, (const u64*)K.d_table, mask, by_volume, K.d_counts,
+                       K.d_state);
+    if (k) {
+        hipLaunchKernelGGL(tb_cp_begin, dim3(1), dim3(64), 0, E->stream, k, K.d_state);
+        const u32 passes = (by_volume ? CP_KEY_WORDS : 2) * CP_WORD_PASSES;  // by id the key is two words
+        for (u32 pass = 0; pass < passes; pass++) {
+            hipLaunchKernelGGL(tb_cp_hist, dim3(wide), dim3(QUERY_THREADS), 0, E->stream, NT, (const u64*)K.d_table, mask, by_volume,
+                               (const u32*)K.d_counts, nb, k, pass, (const u64*)K.d_state, hist);
+            hipLaunchKernelGGL(tb_cp_pick, dim3(1), dim3(1024), 0, E->stream, k, pass, (const u32*)hist, K.d_state);
+        }
+        hipLaunchKernelGGL(tb_cp_collect, dim3(wide), dim3(QUERY_THREADS), 0, E->stream, NT, (const u64*)K.d_table, mask, by_volume,
+                           (const u32*)K.d_counts, nb, k, K.d_state, K.d_keys);
+        hipLaunchKernelGGL(tb_cp_emit, dim3((k + CP_EMIT_KEYS - 1) / CP_EMIT_KEYS), dim3(QUERY_THREADS), 0, E->stream, NT,
+                           (const u64*)K.d_table, mask, k, (const u64*)K.d_state, (const u64*)K.d_keys, K.d_out);
+    }
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpyAsync(K.h_state, K.d_state, (u64)CP_WORDS * 8, hipMemcpyDeviceToHost, E->stream));
+    return TBGPU_STATUS_OK;
+}
+
+extern "C" int tbgpu_get_account_counterparties(tbgpu_t* E, const tbgpu_counterparty_filter* filter, void* out, uint32_t out_cap_rows,
+                                                tbgpu_query_result* result) {
+    static_assert(sizeof(tbgpu_counterparty_filter) == 64 && sizeof(tbgpu_counterparty_flow) == CP_FLOW_WORDS * 8 &&
+                      sizeof(tbgpu_counterparty) == CP_ROW_BYTES && CP_ROWS_MAX == TBGPU_COUNTERPARTIES_ROWS_MAX &&
+                      CP_FLOW_WORDS == MATRIX_BIN_WORDS && CP_TO + 2 * CP_FLOW_WORDS == CP_SLOT_WORDS &&
+                      CP_SIDE_DEBITS == TBGPU_FILTER_DEBITS && CP_SIDE_CREDITS == TBGPU_FILTER_CREDITS && NODE_WORLD_MAX <= (1u << 22),
+                  "k_counterparties.h's constants are the header's");
+    QueryCall c;
+    if (const int st = query_begin(E, "get_account_counterparties", filter, out, out_cap_rows, TBGPU_COUNTERPARTIES_ROWS_MAX, true, result,
+                                   &c)) {
+        return st;
+    }
+    if (!counterparty_filter_valid(filter)) return TBGPU_STATUS_OK;
+    NodeTablesArgs NT{};
+    NT.world = c.world;
+    for (u32 d = 0; d < c.world; d++) NT.T[d] = c.Es[d]->T;
+    // Every engine is drained before any is asked: a scan reads its posts' pending transfers on their homes.
+    for (u32 d = 0; d < c.world; d++) {
+        HIPCK(hipSetDevice(c.Es[d]->device));
+        if (c.Es[d]->pending) {
+            const int st = engine_sync(c.Es[d]);
+            if (st) return query_end(result, st);
+        }
+    }
+    CpFilter F{};
+    F.a_lo = filter->account_id_lo, F.a_hi = filter->account_id_hi;
+    F.t_open = filter->t_open, F.t_close = filter->t_close;
+    F.min_lo = filter->id_min_lo, F.min_hi = filter->id_min_hi;
+    F.sides = filter->flags & (TBGPU_FILTER_DEBITS | TBGPU_FILTER_CREDITS);
+    F.by_volume = (filter->flags & TBGPU_COUNTERPARTIES_BY_VOLUME) != 0;
+    const bool one = c.world == 1;
+    int st = query_side_by_side(c.Es, c.world, [&](u32 d) -> int {
+        if (const int s = counterparty_enqueue_scan(c.Es[d], NT, d, F, !one)) return s;
+        return one ? counterparty_enqueue_select(c, NT, F.by_volume) : TBGPU_STATUS_OK;
+    });
+    if (st) return query_end(result, st);
+    u64 orphan = 0, overflow = 0;
+    if (!one) {  // the peers' flags are back; the first shard's follow with the select's words
+        for (u32 d = 1; d < c.world; d++) orphan |= c.Es[d]->qs->qk.h_state[CP_ORPHAN], overflow |= c.Es[d]->qs->qk.h_state[CP_OVERFLOW];
+        st = counterparty_enqueue_select(c, NT, F.by_volume);
+        if (st == TBGPU_STATUS_OK) st = query_wait(c.Es[0]);
+        if (st) return query_end(result, st);
+    }
+    tbgpu* E0 = c.Es[0];
+    const CounterpartyBufs& K = E0->qs->qk;
+    orphan |= K.h_state[CP_ORPHAN], overflow |= K.h_state[CP_OVERFLOW];
+    if (overflow) {
+        return query_end(result, fail(TBGPU_STATUS_INVALID,
+                                      "get_account_counterparties: the matching records name more distinct counterparties than the "
+                                      "group table holds (capacity: %llu groups, %llu slots)",
+                                      (unsigned long long)K.groups, (unsigned long long)K.slots));
+    }
+    const u64 matched = K.h_state[CP_TOTAL];
+    const u32 m = (u32)std::min<u64>(c.k, matched);
+    if (m && std::min<u64>(c.k, K.h_state[CP_NKEYS]) != m) {
+        return query_end(result, fail(TBGPU_STATUS_PANIC, "get_account_counterparties: %llu keys selected for %u of %llu groups",
+                                      (unsigned long long)K.h_state[CP_NKEYS], m, (unsigned long long)matched));
+    }
+    if (m) {
+        HIPCK(hipSetDevice(E0->device));
+        HIPCK(hipMemcpyAsync(out, K.d_out, (u64)m * CP_ROW_BYTES, hipMemcpyDeviceToHost, E0->stream));
+        HIPCK(hipStreamSynchronize(E0->stream));
+    }
+    if (orphan) result->complete = 0;
+    result->count = m;
+    result->matched = matched;
+    return TBGPU_STATUS_OK;
 }
 
 // ---- get_ledger_balances (k_ledgers.h, include/tbgpu.h) -------------------------------------------

@@ -357,6 +357,12 @@ tbgpu_query_result StateMachine::get_account_flow_matrix(uint64_t t_open, uint64
     return r;
 }
 
+tbgpu_query_result StateMachine::get_account_counterparties(const tbgpu_counterparty_filter& filter, void* out, uint32_t out_cap_rows) {
+    tbgpu_query_result r{};
+    check(tbgpu_get_account_counterparties(engine_, &filter, out, out_cap_rows, &r), "get_account_counterparties");
+    return r;
+}
+
 tbgpu_query_result StateMachine::query_transfers(const tbgpu_query_filter& filter, void* out, uint32_t out_cap_records) {
     tbgpu_query_result r{};
     check(tbgpu_query_transfers(engine_, &filter, out, out_cap_records, &r), "query_transfers");

@@ -323,6 +323,15 @@ public:
     tbgpu_query_result get_account_flow_matrix(uint64_t t_open, uint64_t t_close, const void* debit_ids, uint32_t n_debit,
                                                const void* credit_ids, uint32_t n_credit, void* out, uint32_t out_cap_cells);
 
+    // Who an account dealt with over (filter.t_open, filter.t_close] (tbgpu_get_account_counterparties; a
+    // read, and no reference operation behind it): one tbgpu_counterparty per distinct counterparty id at
+    // or above filter.id_min — what the subject paid it (`to`) and what it paid the subject (`from`),
+    // each a flow cell's sums — by id ascending, or under TBGPU_COUNTERPARTIES_BY_VOLUME by posted volume
+    // descending, at most filter.limit and TBGPU_COUNTERPARTIES_ROWS_MAX, all from one scan of the log.
+    // result.matched is the number of groups; result.complete == 0: transfers were evicted or a matching
+    // post had lost its pending transfer.
+    tbgpu_query_result get_account_counterparties(const tbgpu_counterparty_filter& filter, void* out, uint32_t out_cap_rows);
+
     // The field-filter queries (tbgpu_query_transfers / tbgpu_query_accounts; reads, not commits): the
     // resident transfers, or the accounts, whose user_data_128 / user_data_64 / user_data_32 / ledger /
     // code equal the filter's non-zero fields, by timestamp (newest first under TBGPU_QUERY_REVERSED),

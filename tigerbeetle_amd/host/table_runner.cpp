@@ -323,8 +323,11 @@ std::string run_table(tb::StateMachine& sm, const std::string& text) {
 // --query-flow-matrix (tests/test_gpu_matrix_cpp.py): the prepares ending in {0, 0, the body's length, t_open,
 // t_close, u32 n_debit, u32 n_credit, n_debit debit ids and n_credit credit ids}, answered by
 // get_account_flow_matrix (the records are tbgpu_flow_cell cells).
+// --query-counterparties (tests/test_gpu_counterparties_cpp.py): the prepares ending in {0, 0, 64, a
+// tbgpu_counterparty_filter}, answered by get_account_counterparties (the records are tbgpu_counterparty rows).
 enum QueryKind { ACCOUNT_TRANSFERS, ACCOUNT_BALANCES, QUERY_TRANSFERS, QUERY_ACCOUNTS, CHANGE_EVENTS, ACCOUNT_TRANSFERS_MANY, ACCOUNTS_AT,
-                 LEDGER_BALANCES, PENDING_TRANSFERS, ACCOUNT_STATEMENTS, ACCOUNT_INTEGRALS, ACCOUNT_SERIES, ACCOUNT_FLOW_MATRIX };
+                 LEDGER_BALANCES, PENDING_TRANSFERS, ACCOUNT_STATEMENTS, ACCOUNT_INTEGRALS, ACCOUNT_SERIES, ACCOUNT_FLOW_MATRIX,
+                 ACCOUNT_COUNTERPARTIES };
 
 int run_query(tb::StateMachine& sm, QueryKind kind, const char* in_path, const char* out_path) {
     std::ifstream in(in_path, std::ios::binary);
@@ -474,6 +477,20 @@ int run_query(tb::StateMachine& sm, QueryKind kind, const char* in_path, const c
         printf("query: %u of %llu cells, complete %u\n", r.count, (unsigned long long)r.matched, r.complete);
         return o ? 0 : 2;
     }
+    if (kind == ACCOUNT_COUNTERPARTIES) {
+        tbgpu_counterparty_filter cf;
+        if (body.size() != sizeof(cf)) {
+            fprintf(stderr, "%s: a counterparty filter is %zu bytes\n", in_path, sizeof(cf));
+            return 2;
+        }
+        memcpy(&cf, body.data(), sizeof(cf));
+        std::vector<uint8_t> out((size_t)TBGPU_COUNTERPARTIES_ROWS_MAX * sizeof(tbgpu_counterparty));
+        const tbgpu_query_result r = sm.get_account_counterparties(cf, out.data(), TBGPU_COUNTERPARTIES_ROWS_MAX);
+        std::ofstream o(out_path, std::ios::binary);
+        o.write((const char*)&r, sizeof(r)).write((const char*)out.data(), (size_t)r.count * sizeof(tbgpu_counterparty));
+        printf("query: %u of %llu rows, complete %u\n", r.count, (unsigned long long)r.matched, r.complete);
+        return o ? 0 : 2;
+    }
     if (kind == PENDING_TRANSFERS) {
         tbgpu_pending_filter pf;
         if (body.size() != sizeof(pf)) {
@@ -523,8 +540,9 @@ int main(int argc, char** argv) {
     const bool integrals = argc > 1 && std::string(argv[1]) == "--query-integrals";
     const bool series = argc > 1 && std::string(argv[1]) == "--query-series";
     const bool matrix = argc > 1 && std::string(argv[1]) == "--query-flow-matrix";
-    const bool query = matrix || fields || balances || changes || many || at || ledgers || pending || statements || integrals || series || (argc > 1 && std::string(argv[1]) == "--query");
-    QueryKind kind = matrix ? ACCOUNT_FLOW_MATRIX : series ? ACCOUNT_SERIES : balances ? ACCOUNT_BALANCES : changes ? CHANGE_EVENTS : many ? ACCOUNT_TRANSFERS_MANY : at ? ACCOUNTS_AT : ledgers ? LEDGER_BALANCES : pending ? PENDING_TRANSFERS : statements ? ACCOUNT_STATEMENTS : integrals ? ACCOUNT_INTEGRALS : ACCOUNT_TRANSFERS;
+    const bool counterparties = argc > 1 && std::string(argv[1]) == "--query-counterparties";
+    const bool query = counterparties || matrix || fields || balances || changes || many || at || ledgers || pending || statements || integrals || series || (argc > 1 && std::string(argv[1]) == "--query");
+    QueryKind kind = counterparties ? ACCOUNT_COUNTERPARTIES : matrix ? ACCOUNT_FLOW_MATRIX : series ? ACCOUNT_SERIES : balances ? ACCOUNT_BALANCES : changes ? CHANGE_EVENTS : many ? ACCOUNT_TRANSFERS_MANY : at ? ACCOUNTS_AT : ledgers ? LEDGER_BALANCES : pending ? PENDING_TRANSFERS : statements ? ACCOUNT_STATEMENTS : integrals ? ACCOUNT_INTEGRALS : ACCOUNT_TRANSFERS;
     const char* self = argv[0];
     if (fields && argc > 2) {
         const std::string which = argv[2];
@@ -545,8 +563,9 @@ int main(int argc, char** argv) {
                 "       %s --query-integrals <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-series <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-flow-matrix <prepares.bin> <answer.bin> [device]\n"
+                "       %s --query-counterparties <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-fields <transfers|accounts> <prepares.bin> <answer.bin> [device]\n",
-                self, self, self, self, self, self, self, self, self, self, self, self, self);
+                self, self, self, self, self, self, self, self, self, self, self, self, self, self);
         return 2;
     }
     if (query) {

@@ -23,7 +23,7 @@ import numpy as np
 
 from . import _lib
 from .types import (ACCOUNT_BALANCE_DTYPE, ACCOUNT_DTYPE, ACCOUNT_FILTER_DTYPE, BATCH_MAX, CHANGE_EVENT_DTYPE, CHANGE_EVENTS_FILTER_DTYPE,
-                    CHANGE_EVENTS_MAX, LEDGER_BALANCE_DTYPE, LEDGERS_MAX, PENDING_FILTER_DTYPE, PENDING_ROW_DTYPE, PENDING_ROWS_MAX, PENDING_STATES, STATEMENT_DTYPE, INTEGRAL_DTYPE, FLOW_CELL_DTYPE, FILTER_CREDITS, FILTER_DEBITS, FILTER_REVERSED, pack_change_events_filter, QUERY_FILTER_DTYPE, QUERY_REVERSED, TRANSFER_DTYPE, U64_MAX, Operation)
+                    CHANGE_EVENTS_MAX, LEDGER_BALANCE_DTYPE, LEDGERS_MAX, PENDING_FILTER_DTYPE, PENDING_ROW_DTYPE, PENDING_ROWS_MAX, PENDING_STATES, STATEMENT_DTYPE, INTEGRAL_DTYPE, FLOW_CELL_DTYPE, COUNTERPARTY_DTYPE, COUNTERPARTIES_BY_VOLUME, COUNTERPARTIES_ROWS_MAX, pack_counterparty_filter, FILTER_CREDITS, FILTER_DEBITS, FILTER_REVERSED, pack_change_events_filter, QUERY_FILTER_DTYPE, QUERY_REVERSED, TRANSFER_DTYPE, U64_MAX, Operation)
 
 
 def average_balances(row):
@@ -646,6 +646,46 @@ class Engine:
                                                           out.ctypes.data, cap, ctypes.byref(res)))
         return out[:res.count], int(res.matched), bool(res.complete)
 
+    COUNTERPARTIES_ROWS_MAX = COUNTERPARTIES_ROWS_MAX  # TBGPU_COUNTERPARTIES_ROWS_MAX
+
+    def get_account_counterparties(self, account_id, t_open=0, t_close=0, *, debits=True, credits=True, by_volume=False,
+                                   id_min=0, limit=COUNTERPARTIES_ROWS_MAX, out_cap_rows=None):
+        """Who `account_id` dealt with over the period (t_open, t_close] (tbgpu_get_account_counterparties):
+        one COUNTERPARTY_DTYPE row per distinct counterparty at or above `id_min`, with what the account
+        paid it (to_*: `debits`) and what it paid the account (from_*: `credits`) — amounts posted, holds
+        placed and released, and the number of records, as a flow-matrix cell has them.  Rows come by
+        counterparty id ascending (page with id_min = the last id + 1), or with `by_volume` by
+        to_posted + from_posted descending, equal volumes by id.  t_open 0: from before every record;
+        t_close 0: up to now.  Returns (rows, matched, complete): `matched` is the number of groups,
+        `complete` is False once the engine has evicted transfers or a matching post had lost its
+        pending transfer.  An invalid filter matches nothing."""
+        flags = (FILTER_DEBITS if debits else 0) | (FILTER_CREDITS if credits else 0) | (COUNTERPARTIES_BY_VOLUME if by_volume else 0)
+        return self.get_account_counterparties_raw(
+            pack_counterparty_filter(int(account_id), int(t_open), int(t_close), int(id_min), int(limit), flags), out_cap_rows)
+
+    def get_account_counterparties_raw(self, filter_bytes, out_cap_rows=None):
+        """get_account_counterparties from the 64 bytes of a tbgpu_counterparty_filter."""
+        filter_bytes = bytes(filter_bytes)
+        if len(filter_bytes) != 64:
+            raise ValueError("a tbgpu_counterparty_filter is 64 bytes")
+        limit = int.from_bytes(filter_bytes[48:52], "little")
+        cap = min(limit, COUNTERPARTIES_ROWS_MAX) if out_cap_rows is None else int(out_cap_rows)
+        if cap < 0 or cap >> 32:
+            raise ValueError("out_cap_rows is 32 bits")
+        out = np.zeros(max(cap, 1), dtype=COUNTERPARTY_DTYPE)
+        res = _lib.tbgpu_query_result()
+        src = ctypes.create_string_buffer(filter_bytes, 64)
+        _lib.check(self.lib.tbgpu_get_account_counterparties(self.h, src, out.ctypes.data, cap, ctypes.byref(res)))
+        return out[:res.count], int(res.matched), bool(res.complete)
+
+    def top_counterparties(self, account_id, k=10, t_open=0, t_close=0, *, debits=True, credits=True):
+        """The `k` largest counterparties of `account_id` over the period by posted volume, as
+        [(counterparty id, posted to it, posted from it)] of Python ints, largest first."""
+        rows, _, _ = self.get_account_counterparties(account_id, t_open, t_close, debits=debits, credits=credits, by_volume=True,
+                                                     limit=k)
+        return [(int(r["id_lo"]) | int(r["id_hi"]) << 64, int(r["to_posted_lo"]) | int(r["to_posted_hi"]) << 64,
+                 int(r["from_posted_lo"]) | int(r["from_posted_hi"]) << 64) for r in rows]
+
     @staticmethod
     def query_filter(user_data_128=0, user_data_64=0, user_data_32=0, ledger=0, code=0, *, reversed=False,
                      timestamp_min=0, timestamp_max=0, limit=8190):
@@ -1053,6 +1093,14 @@ class StateMachine:
     def get_account_flow_matrix_raw(self, debit_id_bytes, credit_id_bytes, t_open, t_close, out_cap_cells=None):
         """The same from the two lists' bytes (Engine.get_account_flow_matrix_raw)."""
         return self.engine.get_account_flow_matrix_raw(debit_id_bytes, credit_id_bytes, t_open, t_close, out_cap_cells)
+
+    def get_account_counterparties(self, account_id, t_open=0, t_close=0, **kwargs):
+        """Who an account dealt with over a period (Engine.get_account_counterparties): a read, not a commit."""
+        return self.engine.get_account_counterparties(account_id, t_open, t_close, **kwargs)
+
+    def top_counterparties(self, account_id, k=10, t_open=0, t_close=0, **kwargs):
+        """The k largest counterparties by posted volume (Engine.top_counterparties)."""
+        return self.engine.top_counterparties(account_id, k, t_open, t_close, **kwargs)
 
     def query_transfers(self, **filter):
         """The field-filter query over transfers (Engine.query_transfers): a read, not a commit."""

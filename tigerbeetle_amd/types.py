@@ -167,6 +167,34 @@ FLOW_CELL_DTYPE = np.dtype(
 assert FLOW_CELL_DTYPE.itemsize == 96
 FLOW_MATRIX_CELLS_MAX = 4095
 
+# tbgpu_counterparty_filter and tbgpu_counterparty (include/tbgpu.h tbgpu_get_account_counterparties): 64
+# and 128 bytes, no padding; a row is a counterparty's id, what the subject paid it (`to`) and what it
+# paid the subject (`from`), each a flow cell's seven sum words.
+COUNTERPARTY_FILTER_DTYPE = np.dtype(
+    _u128("account_id") + [("t_open", "<u8"), ("t_close", "<u8")] + _u128("id_min")
+    + [("limit", "<u4"), ("flags", "<u4"), ("reserved", "u1", (8,))])
+COUNTERPARTY_DTYPE = np.dtype(
+    _u128("id")
+    + [f for d in ("to", "from") for c in ("posted", "pending_in", "pending_out") for f in _u128(d + "_" + c)][:6]
+    + [("to_transfers", "<u8")]
+    + [f for c in ("posted", "pending_in", "pending_out") for f in _u128("from_" + c)]
+    + [("from_transfers", "<u8")])
+assert COUNTERPARTY_FILTER_DTYPE.itemsize == 64 and COUNTERPARTY_DTYPE.itemsize == 128
+COUNTERPARTIES_BY_VOLUME = 1 << 8
+COUNTERPARTIES_ROWS_MAX = 8191
+
+
+def pack_counterparty_filter(account_id, t_open=0, t_close=0, id_min=0, limit=COUNTERPARTIES_ROWS_MAX,
+                             flags=FILTER_DEBITS | FILTER_CREDITS):
+    """The 64 bytes of a tbgpu_counterparty_filter."""
+    f = np.zeros(1, dtype=COUNTERPARTY_FILTER_DTYPE)
+    f["account_id_lo"], f["account_id_hi"] = account_id & U64_MAX, account_id >> 64
+    f["t_open"], f["t_close"] = t_open, t_close
+    f["id_min_lo"], f["id_min_hi"] = id_min & U64_MAX, id_min >> 64
+    f["limit"], f["flags"] = limit, flags
+    return f.tobytes()
+
+
 # tbgpu_query_filter (include/tbgpu.h tbgpu_query_transfers / tbgpu_query_accounts): 64 bytes, no padding.
 QUERY_FILTER_DTYPE = np.dtype(
     _u128("user_data_128") + [("user_data_64", "<u8"), ("user_data_32", "<u4"), ("ledger", "<u4"), ("code", "<u2"),

@@ -85,6 +85,15 @@ the same process: one tbgpu_get_account_statements call over the same ids and pe
 over the whole log the host alternative the call replaces is timed once by the wall clock: every debit
 account's tbgpu_get_account_transfers pages, grouped by credit account in Python, and its cells are compared
 with the call's.  An older library loaded through TBGPU_AB_LIB lacks the call: the yardstick alone is timed then.
+
+`--only counterparties` (tbgpu_get_account_counterparties) times the C call alone, into buffers
+made once, on both logs: the Zipf log's hottest account and a cold one and an account of the uniform log, both
+sides, by id and by volume, limit 10 and 8,191, over the whole log; and the call's fixed cost — the group table
+zeroed and selected over, whatever the log holds — as the same call over an empty period.  The yardsticks run in
+the same process: one tbgpu_get_account_statements call for that one account and period (what one scan costs),
+and, once per subject by the wall clock, the host alternative the call replaces: the account's
+tbgpu_get_account_transfers pages grouped by counterparty in Python, whose groups are compared with the call's.
+An older library loaded through TBGPU_AB_LIB lacks the call: the yardsticks alone are timed then.
 """
 import json
 import os
@@ -778,6 +787,109 @@ def measure_matrix():
     return out
 
 
+def measure_counterparties():
+    """get_account_counterparties beside get_account_statements for the same account and period, and beside the
+    account's pages grouped on the host, on both logs, in one process."""
+    import ctypes
+    import time
+
+    from tigerbeetle_amd import _lib
+    from tigerbeetle_amd.types import pack_counterparty_filter
+    os.environ["TBGPU_QUERY_COOP"] = "0"
+    e = Engine(Options(accounts_max=n_acct, transfers_max=n_xfer, pass_events_max=pb * batch, pass_batches_max=pb))
+    a_lens = batches(n_acct, batch)
+    a_ts, t = timestamps(a_lens, 1_000_000_000)
+    acct = e.alloc(n_acct * 128)
+    e.generate_accounts(acct, 0, n_acct, seed=42)
+    res = e.alloc(max(n_acct, n_xfer) * 8)
+    rb = e.alloc((n_xfer // batch + 2) * 4)
+    e.commit_device_async(128, a_ts, a_lens, acct, res, rb)
+    e.sync()
+    rows_max = 8191
+    have = hasattr(e.lib, "tbgpu_get_account_counterparties")  # an older library (TBGPU_AB_LIB): the yardsticks alone
+    h_out = np.zeros(rows_max * 256, dtype=np.uint8)
+    h_res = _lib.tbgpu_query_result()
+
+    def raw_counterparties(account, t_open, t_close, limit, by_volume):
+        f = pack_counterparty_filter(account, t_open, t_close, 0, limit, 3 | (256 if by_volume else 0))
+        src = ctypes.create_string_buffer(f, 64)
+        return lambda: _lib.check(e.lib.tbgpu_get_account_counterparties(e.h, src, h_out.ctypes.data, rows_max, ctypes.byref(h_res)))
+
+    def raw_statements(account, t_open, t_close):
+        src = ctypes.create_string_buffer(account.to_bytes(16, "little"), 16)
+        return lambda: _lib.check(e.lib.tbgpu_get_account_statements(e.h, t_open, t_close, src, 1, h_out.ctypes.data, 1, ctypes.byref(h_res)))
+
+    def paged(account, t_open, t_close):
+        """The host alternative: {counterparty: [records to it, records from it]}, from the account's pages."""
+        groups = {}
+        t_min = t_open + 1
+        while True:
+            page, _, _ = e.get_account_transfers(account, timestamp_min=t_min, timestamp_max=t_close, limit=8190)
+            ids = zip(page["debit_account_id_lo"].tolist(), page["debit_account_id_hi"].tolist(), page["credit_account_id_lo"].tolist(),
+                      page["credit_account_id_hi"].tolist())
+            for dl, dh, cl, ch in ids:
+                d, c = dl | dh << 64, cl | ch << 64
+                if d == account:
+                    groups.setdefault(c, [0, 0])[0] += 1
+                if c == account:
+                    groups.setdefault(d, [0, 0])[1] += 1
+            if len(page) < 8190:
+                break
+            t_min = int(page["timestamp"][-1]) + 1
+        return groups
+
+    out = {}
+    if have:
+        out["group_table_bytes"] = 128 * (1 << (2 * n_acct - 1).bit_length())  # 128-B slots, 2 x accounts_max rounded up to a power of two
+    for name, kind in (("uniform", "c2"), ("zipf", "c3")):
+        if name != "uniform":
+            e.reset_transfers()
+        log = e.log_window(n_xfer)
+        e.generate_transfers(log, 0, n_xfer, n_acct, seed=42, kind=KINDS[kind])
+        e.sync()
+        x_lens = batches(n_xfer, batch)
+        x_ts, t = timestamps(x_lens, t + 10)
+        e.commit_device_async(129, x_ts, x_lens, log, res, rb)
+        e.sync()
+        oldest, _, _ = e.query_transfers(limit=1)
+        newest, _, _ = e.query_transfers(reversed=True, limit=1)
+        t_first, t_last = int(oldest["timestamp"][0]), int(newest["timestamp"][0])
+        sample = e.to_host(log + (n_xfer // 2) * 128, min(n_xfer // 2, 1 << 16) * 128).view(TRANSFER_DTYPE)
+        accounts, counts = np.unique(sample[["debit_account_id_lo", "debit_account_id_hi"]], return_counts=True)
+        order = np.argsort(-counts, kind="stable")
+        id_at = lambda k: int(accounts[order[k]][0]) | (int(accounts[order[k]][1]) << 64)
+        subjects = (("hot", id_at(0)), ("cold", id_at(len(order) - 1))) if name == "zipf" else (("account", id_at(0)),)
+        for who, account in subjects:
+            t_open, t_close = t_first - 1, t_last
+            y_med, y_lo, y_hi = timed(e, raw_statements(account, t_open, t_close))
+            start = time.perf_counter()
+            groups = paged(account, t_open, t_close)
+            paged_ms = round((time.perf_counter() - start) * 1e3, 1)
+            base = dict(statements_ms=round(y_med, 4), statements_min_ms=round(y_lo, 4), statements_max_ms=round(y_hi, 4),
+                        paged_on_host_ms=paged_ms, groups=len(groups), records=sum(a + b for a, b in groups.values()))
+            if not have:
+                out["%s_counterparties_%s" % (name, who)] = base
+                continue
+            rows, matched, complete = e.get_account_counterparties(account, t_open, t_close)
+            assert complete and matched == len(groups)
+            mine = {int(r["id_lo"]) | int(r["id_hi"]) << 64: [int(r["to_transfers"]), int(r["from_transfers"])] for r in rows}
+            assert all(groups[x] == v for x, v in mine.items()) and len(mine) == min(matched, rows_max)
+            for order_name, by_volume in (("by_id", False), ("by_volume", True)):
+                for limit in (10, rows_max):
+                    med, lo_ms, hi_ms = timed(e, raw_counterparties(account, t_open, t_close, limit, by_volume))
+                    out["%s_counterparties_%s_%s_limit_%d" % (name, who, order_name, limit)] = row(
+                        med, lo_ms, hi_ms, over_statements=round(med / y_med, 2), over_paged_on_host=round(med / paged_ms, 5), **base)
+            # The fixed cost: the same call over an empty period (the scan reads timestamps only).
+            y_med, y_lo, y_hi = timed(e, raw_statements(account, t_last, t_last + 1))
+            for order_name, by_volume in (("by_id", False), ("by_volume", True)):
+                med, lo_ms, hi_ms = timed(e, raw_counterparties(account, t_last, t_last + 1, rows_max, by_volume))
+                out["%s_counterparties_%s_%s_empty_period" % (name, who, order_name)] = row(
+                    med, lo_ms, hi_ms, statements_ms=round(y_med, 4), statements_min_ms=round(y_lo, 4), statements_max_ms=round(y_hi, 4),
+                    over_statements=round(med / y_med, 2))
+    e.close()
+    return out
+
+
 def measure_ledgers():
     """get_ledger_balances beside query_accounts, query_transfers and the copies, in one process."""
     import ctypes
@@ -968,6 +1080,8 @@ elif only == "series":
     result["series"] = measure_series()
 elif only == "matrix":
     result["matrix"] = measure_matrix()
+elif only == "counterparties":
+    result["counterparties"] = measure_counterparties()
 elif only == "many":
     result["many"] = measure_many()
 elif only == "balances":
@@ -979,6 +1093,6 @@ elif only != "fields":
     for shape in ("lane_per_record", "cooperative"):
         r = result[shape]
         r["bar_query_le_copy"] = all(v["ms"] <= r["copy_d2d"]["ms"] for k, v in r.items() if k != "copy_d2d")
-if only not in ("account", "balances", "change_events", "many", "asof", "ledgers", "pending", "statements", "integrals", "series", "matrix"):
+if only not in ("account", "balances", "change_events", "many", "asof", "ledgers", "pending", "statements", "integrals", "series", "matrix", "counterparties"):
     result["field_filters"] = measure_fields()
 print(json.dumps(result))

@@ -898,6 +898,36 @@ pub fn StateMachineType(
             return @as(usize, result.count) * @sizeOf(tbgpu.tbgpu_flow_cell);
         }
 
+        /// Who `filter.account_id` dealt with over (t_open, t_close] (tbgpu_get_account_counterparties):
+        /// a read, with no operation in this reference's enum, so nothing in commit() dispatches to it
+        /// (INTEGRATION.md, "Account counterparties"). Every distinct counterparty id at or above
+        /// `filter.id_min` yields one row of 128 bytes into `output`, by id ascending or, under
+        /// TBGPU_COUNTERPARTIES_BY_VOLUME, by posted volume descending; returns the bytes written.
+        /// `matched` receives the number of groups; `complete` is false once transfers were evicted or
+        /// a matching post had lost its pending transfer.
+        pub fn get_account_counterparties(
+            self: *StateMachine,
+            filter: *const tbgpu.tbgpu_counterparty_filter,
+            output: []align(16) u8,
+            matched: *u64,
+            complete: *bool,
+        ) usize {
+            var result: tbgpu.tbgpu_query_result = undefined;
+            result.count = 0;
+            result.complete = 1;
+            result.matched = 0;
+            check(tbgpu.tbgpu_get_account_counterparties(
+                self.engine,
+                filter,
+                output.ptr,
+                @intCast(output.len / @sizeOf(tbgpu.tbgpu_counterparty)),
+                &result,
+            ));
+            matched.* = result.matched;
+            complete.* = result.complete != 0;
+            return @as(usize, result.count) * @sizeOf(tbgpu.tbgpu_counterparty);
+        }
+
         pub fn compact(self: *StateMachine, callback: *const fn (*StateMachine) void, op: u64) void {
             assert(self.compact_callback == null);
             assert(self.checkpoint_callback == null);
