@@ -30,6 +30,7 @@
  *   (no reference: statements per bucket of a period)      tbgpu_get_account_statement_series (likewise)
  *   (no reference: who paid whom over a period)            tbgpu_get_account_flow_matrix (likewise)
  *   (no reference: who an account dealt with)              tbgpu_get_account_counterparties (likewise)
+ *   (no reference: the accounts a period's records name)   tbgpu_get_active_accounts (likewise)
  *   `setup` action of the table tests (:1398-1407)         tbgpu_test_set_balances (test only)
  *   StateMachine.commit_timestamp field (:251)             tbgpu_commit_timestamp
  *
@@ -1030,6 +1031,91 @@ typedef struct tbgpu_counterparty {         /* 128 bytes */
 } tbgpu_counterparty;
 int tbgpu_get_account_counterparties(tbgpu_t* engine, const tbgpu_counterparty_filter* filter,
                                      void* out, uint32_t out_cap_rows, tbgpu_query_result* result);
+
+/* get_active_accounts: the accounts a period's records name, ranked — one row per distinct account x
+ * that a record of the period (t_open, t_close] names, with what x paid (`debits`) and what it was
+ * paid (`credits`).  Every other read call answers for accounts the caller names, and
+ * tbgpu_get_account_counterparties discovers accounts only around one subject; this one answers
+ * "which accounts moved money in the last hour", "which ten moved the most", "which accounts on ledger
+ * 7 had the most transfers under code 12 yesterday".  Paging the whole log out with
+ * tbgpu_query_transfers and grouping on the host is one log scan per 8,190 records; this call groups by
+ * the 128-bit account id in one scan of the log in HBM and stores nothing at commit.  No reference has
+ * an operation for it.  An entry point of its own, as above; this comment is its specification.
+ *   The period is (t_open, t_close], exactly tbgpu_get_account_statements': t_open == 0 is read
+ *     literally (from before every record), t_close == 0 means up to now.
+ *   What matches: a live resident record r (liveness: tbgpu_get_account_transfers' rule) with
+ *     t_open < r.timestamp, and r.timestamp <= t_close when t_close != 0, and r.ledger == ledger when
+ *     ledger != 0, and r.code == code when code != 0.  Ledger and code are read as the record carries
+ *     them.  Post and void records count too, as in the flow matrix.
+ *   Sides and sums: under TBGPU_FILTER_DEBITS a matching record feeds `debits` of the row of its debit
+ *     account; under TBGPU_FILTER_CREDITS it feeds `credits` of the row of its credit account.  A
+ *     loaded record with debit == credit feeds both halves of one row.  The half of a side that is not
+ *     wanted is all zero.  A record adds one to `transfers`, and by kind
+ *         pending      pending_in  += amount
+ *         post         pending_out += P,  posted += amount
+ *         void         pending_out += P
+ *         any other    posted      += amount
+ *     modulo 2^128, exactly as a tbgpu_flow_cell; P and the orphan rule are
+ *     tbgpu_get_account_balances' (a void's P is its own amount; a post whose pending transfer is not
+ *     resident uses P = its own amount).
+ *   No account table is read: accounts are ids as the records carry them, an account need not be in
+ *     the account table, and on a node engine nothing depends on account owners.
+ *   A group is a distinct id x >= id_min (as 128-bit numbers; id_min 0: all) with at least one
+ *     matching record on a wanted side.  matched is the number of groups.
+ *   Order: by default by x ascending as a 128-bit number; a consumer pages with id_min = the last
+ *     id + 1.  Under TBGPU_ACTIVE_BY_VOLUME by volume = (debits.posted + credits.posted) mod 2^128,
+ *     descending, equal volumes by x ascending.  Under TBGPU_ACTIVE_BY_TRANSFERS by
+ *     debits.transfers + credits.transfers descending, equal counts by x ascending.  The last two have
+ *     no cursor; id_min still narrows the groups.
+ *   Rows: count = min(limit, out_cap_rows, TBGPU_ACTIVE_ROWS_MAX, matched) rows, the first in that
+ *     order.  Bytes past count rows are not written.
+ *   complete: 0 when any transfer was ever evicted (any shard), or when an orphan post matched —
+ *     whether or not its groups are returned, and whether or not they are at or above id_min; 1
+ *     otherwise.  A post outside the period, or failing the ledger or code test, does not drop it.
+ *   Identities, with ledger == code == 0 and both sides wanted.  Statement identity: for a returned x
+ *     that the account table holds with a timestamp at or below a non-zero t_close, `debits` is
+ *     {debits_posted_in, debits_pending_in, debits_pending_out, debit_transfers} of
+ *     tbgpu_get_account_statements for x and the same period, and `credits` the credits_* fields.
+ *     Counterparty identity: the same `debits` is the sum of `to` over
+ *     tbgpu_get_account_counterparties(x, TBGPU_FILTER_DEBITS).  Double entry: with every group
+ *     returned, the four sums of `debits` over all rows equal those of `credits`, modulo 2^128 and
+ *     2^64.  Ledger identity: on a committed log a transfer carries its accounts' ledger, so the rows
+ *     under ledger = L are exactly the unfiltered rows of the accounts whose ledger is L.
+ *   An invalid filter is never a status: neither side bit, both BY_* bits, an unknown flag bit
+ *     (TBGPU_FILTER_REVERSED included), a non-zero reserved byte, t_open or t_close equal to 2^64-1, a
+ *     non-zero t_close below t_open, or limit 0 return TBGPU_STATUS_OK with count = matched = 0 and
+ *     write nothing.  A NULL filter, out or result is TBGPU_STATUS_INVALID.  After any failing status
+ *     the result names no row.
+ *   Capacity: an engine has room for at least accounts_max groups (a node engine: the node's
+ *     accounts_max).  Committed records name only accounts the table holds, so a committed log never
+ *     exceeds it.  A log built with tbgpu_load_transfers whose matching records name more distinct
+ *     accounts than the engine has room for returns TBGPU_STATUS_INVALID, tbgpu_last_error names the
+ *     capacity, and nothing is written: never a partial answer.
+ *   The call contract of tbgpu_get_account_statements: synchronous, drains a pending
+ *     tbgpu_commit_device_async first, a read that changes nothing, works on an engine a device panic
+ *     stopped, allocates nothing after tbgpu_init, legal beside an asynchronous write-back.
+ *   A node engine returns the same bytes: every home shard scans its own log on its own device and
+ *     stream, side by side; a group's sums are the shards' sums added before any order is applied. */
+#define TBGPU_ACTIVE_BY_VOLUME    (1u << 8)   /* order by volume descending */
+#define TBGPU_ACTIVE_BY_TRANSFERS (1u << 9)   /* order by record count descending */
+#define TBGPU_ACTIVE_ROWS_MAX 8191u           /* 128 B rows in one message body */
+typedef struct tbgpu_activity_filter {   /* 64 bytes, little-endian, no padding */
+    uint64_t t_open, t_close;            /* the period (t_open, t_close] */
+    uint64_t id_min_lo, id_min_hi;       /* only accounts with id >= id_min; 0: all */
+    uint32_t ledger;                     /* 0: any */
+    uint16_t code;                       /* 0: any */
+    uint8_t  reserved0[2];               /* must be zero */
+    uint32_t limit;
+    uint32_t flags;   /* TBGPU_FILTER_DEBITS | TBGPU_FILTER_CREDITS | one TBGPU_ACTIVE_BY_* at most */
+    uint8_t  reserved[16];               /* must be zero */
+} tbgpu_activity_filter;
+typedef struct tbgpu_account_activity {  /* 128 bytes */
+    uint64_t id_lo, id_hi;               /* the account x */
+    tbgpu_counterparty_flow debits;      /* records whose debit account is x */
+    tbgpu_counterparty_flow credits;     /* records whose credit account is x */
+} tbgpu_account_activity;
+int tbgpu_get_active_accounts(tbgpu_t* engine, const tbgpu_activity_filter* filter,
+                              void* out, uint32_t out_cap_rows, tbgpu_query_result* result);
 
 /* The replica writes StateMachine.commit_timestamp itself: the header timestamp after every commit
  * (src/vsr/replica.zig:3664-3665) and the checkpoint's value on open / state sync.  The wrapper

@@ -154,6 +154,22 @@ COUNTERPARTIES_BY_VOLUME = 1 << 8  # TBGPU_COUNTERPARTIES_BY_VOLUME
 COUNTERPARTIES_ROWS_MAX = 8191  # TBGPU_COUNTERPARTIES_ROWS_MAX
 
 
+class tbgpu_activity_filter(ctypes.Structure):
+    _fields_ = [("t_open", ctypes.c_uint64), ("t_close", ctypes.c_uint64),
+                ("id_min_lo", ctypes.c_uint64), ("id_min_hi", ctypes.c_uint64),
+                ("ledger", ctypes.c_uint32), ("code", ctypes.c_uint16), ("reserved0", ctypes.c_uint8 * 2),
+                ("limit", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint8 * 16)]
+
+
+class tbgpu_account_activity(ctypes.Structure):
+    _fields_ = [("id_lo", ctypes.c_uint64), ("id_hi", ctypes.c_uint64),
+                ("debits", tbgpu_counterparty_flow), ("credits", tbgpu_counterparty_flow)]
+
+
+ACTIVE_BY_VOLUME = 1 << 8  # TBGPU_ACTIVE_BY_VOLUME
+ACTIVE_BY_TRANSFERS = 1 << 9  # TBGPU_ACTIVE_BY_TRANSFERS
+ACTIVE_ROWS_MAX = 8191  # TBGPU_ACTIVE_ROWS_MAX
+
 class tbgpu_stats(ctypes.Structure):
     _fields_ = [
         ("passes", ctypes.c_uint64),
@@ -285,6 +301,7 @@ SIGNATURES = [
     ("tbgpu_get_account_statement_series", ctypes.c_int, [_P, _P, _U32, _P, _U32, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_get_account_flow_matrix", ctypes.c_int, [_P, _U64, _U64, _P, _U32, _P, _U32, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_get_account_counterparties", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
+    ("tbgpu_get_active_accounts", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_query_transfers", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_query_accounts", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_bench_query_keys_max", ctypes.c_int, [_P, _U32]),

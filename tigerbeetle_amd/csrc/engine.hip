@@ -43,6 +43,7 @@
 #include "k_series.h"
 #include "k_matrix.h"
 #include "k_counterparties.h"
+#include "k_activity.h"
 #include "k_ledgers.h"
 #include "k_pending.h"
 #include "checksum.h"

@@ -14,7 +14,7 @@
 //                  workgroup LDS bin claimed by {slot, direction} (tb_change_bin_claim), else into the
 //                  slot in HBM;
 //   the select     the first k of the occupied slots by a multi-word key — {id} by default, {~volume,
-//                  id} under BY_VOLUME — by k_query_filter.h's most-significant-digit radix select,
+//                  id} under BY_VOLUME, {~count, id} for k_activity.h's BY_TRANSFERS — by k_query_filter.h's most-significant-digit radix select,
 //                  over a key of up to four 64-bit words: tb_cp_count, tb_cp_begin, tb_cp_hist /
 //                  tb_cp_pick, tb_cp_collect;
 //   tb_cp_emit     ranks the collected keys by counting and writes the rows.
@@ -224,15 +224,23 @@ __global__ __launch_bounds__(QUERY_THREADS) void tb_cp_merge(NodeTablesArgs N, c
 // ---- the select --------------------------------------------------------------------------------------
 // The key of slot `slot`, most significant word first, or false: the slot is free.  By id: {id.hi,
 // id.lo, 0, 0}.  By volume: {~volume.hi, ~volume.lo, id.hi, id.lo}, volume = to.posted + from.posted
-// modulo 2^128, so that ascending keys are descending volumes and equal volumes go by id.
-__device__ static inline bool tb_cp_key(const NodeTablesArgs& N, const u64* table, u64 slot, u32 mask, u32 by_volume, u64 (&K)[CP_KEY_WORDS]) {
+// modulo 2^128, so that ascending keys are descending volumes and equal volumes go by id.  By transfers
+// (k_activity.h): {~count, id.hi, id.lo, 0}, count = to.transfers + from.transfers.  `order` is a
+// CP_ORDER_*.
+#define CP_ORDER_ID 0u
+#define CP_ORDER_VOLUME 1u
+#define CP_ORDER_TRANSFERS 2u
+__host__ __device__ static inline u32 tb_cp_order_words(u32 order) { return order == CP_ORDER_VOLUME ? 4 : order == CP_ORDER_TRANSFERS ? 3 : 2; }
+__device__ static inline bool tb_cp_key(const NodeTablesArgs& N, const u64* table, u64 slot, u32 mask, u32 order, u64 (&K)[CP_KEY_WORDS]) {
     if (slot > mask) return false;
     const u64* e = table + slot * CP_SLOT_WORDS;
     u64 lo, hi;
     if (!tb_cp_tag_id(N, e[0], lo, hi)) return false;
-    if (by_volume) {
+    if (order == CP_ORDER_VOLUME) {
         const u128 volume = tb_u128(e[CP_TO], e[CP_TO + 1]) + tb_u128(e[CP_TO + CP_FLOW_WORDS], e[CP_TO + CP_FLOW_WORDS + 1]);
         K[0] = ~tb_hi(volume), K[1] = ~tb_lo(volume), K[2] = hi, K[3] = lo;
+    } else if (order == CP_ORDER_TRANSFERS) {
+        K[0] = ~(e[CP_TO + 6] + e[CP_TO + CP_FLOW_WORDS + 6]), K[1] = hi, K[2] = lo, K[3] = 0;
     } else {
         K[0] = hi, K[1] = lo, K[2] = 0, K[3] = 0;
     }
@@ -244,12 +252,12 @@ __device__ static inline u32 cp_shift(u32 pass) { return CP_BITS * (CP_WORD_PASS
 
 // A tile of QUERY_THREADS slots per workgroup: how many are occupied, into counts[b] and the total, and
 // which bits of the keys are ever one and ever zero.
-__global__ __launch_bounds__(QUERY_THREADS) void tb_cp_count(NodeTablesArgs N, const u64* table, u32 mask, u32 by_volume, u32* counts,
+__global__ __launch_bounds__(QUERY_THREADS) void tb_cp_count(NodeTablesArgs N, const u64* table, u32 mask, u32 order, u32* counts,
                                                              u64* st) {
     __shared__ u32 s_cnt[QUERY_WAVES];
     const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     u64 K[CP_KEY_WORDS];
-    const bool have = tb_cp_key(N, table, (u64)blockIdx.x * QUERY_THREADS + threadIdx.x, mask, by_volume, K);
+    const bool have = tb_cp_key(N, table, (u64)blockIdx.x * QUERY_THREADS + threadIdx.x, mask, order, K);
     const u64 m = __ballot(have);
     if (lane == 0) s_cnt[wave] = (u32)__popcll(m);
     if (m) {  // the whole wave alike
@@ -301,7 +309,7 @@ __device__ static inline bool cp_has_prefix(const u64 (&K)[CP_KEY_WORDS], const 
     return above >= 64 || (K[w] >> above) == (prefix[w] >> above);
 }
 
-__global__ __launch_bounds__(QUERY_THREADS) void tb_cp_hist(NodeTablesArgs N, const u64* table, u32 mask, u32 by_volume,
+__global__ __launch_bounds__(QUERY_THREADS) void tb_cp_hist(NodeTablesArgs N, const u64* table, u32 mask, u32 order,
                                                             const u32* counts, u32 nblocks, u32 k, u32 pass, const u64* st, u32* hist) {
     __shared__ u32 s_hist[CP_BINS];
     if (!cp_pass_runs(st, k, pass)) return;
@@ -317,7 +325,7 @@ __global__ __launch_bounds__(QUERY_THREADS) void tb_cp_hist(NodeTablesArgs N, co
         if (b >= nblocks || counts[b] == 0) continue;  // the whole workgroup alike
         any = true;
         u64 K[CP_KEY_WORDS];
-        if (!tb_cp_key(N, table, (u64)b * QUERY_THREADS + threadIdx.x, mask, by_volume, K)) continue;
+        if (!tb_cp_key(N, table, (u64)b * QUERY_THREADS + threadIdx.x, mask, order, K)) continue;
         if (cp_has_prefix(K, prefix, pass)) atomicAdd(&s_hist[(K[w] >> shift) & (CP_BINS - 1)], 1u);
     }
     if (!any) return;
@@ -360,7 +368,7 @@ __global__ __launch_bounds__(1024) void tb_cp_pick(u32 k, u32 pass, const u32* h
 
 // The groups whose key is at or below the selected one append {key, slot} to the k-entry key buffer
 // through one counter.  Ids are unique, so exactly min(k, M) qualify; the store is guarded all the same.
-__global__ __launch_bounds__(QUERY_THREADS) void tb_cp_collect(NodeTablesArgs N, const u64* table, u32 mask, u32 by_volume,
+__global__ __launch_bounds__(QUERY_THREADS) void tb_cp_collect(NodeTablesArgs N, const u64* table, u32 mask, u32 order,
                                                                const u32* counts, u32 nblocks, u32 k, u64* st, u64* keys) {
     const bool all = st[CP_TOTAL] <= k;  // every group
     u64 limit[CP_KEY_WORDS];
@@ -371,7 +379,7 @@ __global__ __launch_bounds__(QUERY_THREADS) void tb_cp_collect(NodeTablesArgs N,
         if (b >= nblocks || counts[b] == 0) continue;
         const u64 slot = (u64)b * QUERY_THREADS + threadIdx.x;
         u64 K[CP_KEY_WORDS];
-        if (!tb_cp_key(N, table, slot, mask, by_volume, K)) continue;
+        if (!tb_cp_key(N, table, slot, mask, order, K)) continue;
         bool above = false, decided = false;
 #pragma unroll
         for (u32 q = 0; q < CP_KEY_WORDS; q++) {

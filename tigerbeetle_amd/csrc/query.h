@@ -2,7 +2,7 @@
 // get_account_transfers_many, get_account_balances, query_transfers, query_accounts,
 // get_change_events, lookup_accounts_at, get_ledger_balances, get_pending_transfers,
 // get_account_statements, get_account_balance_integrals, get_account_statement_series,
-// get_account_flow_matrix and get_account_counterparties; their buffers, made at tbgpu_init, and their entry points.  Included by engine.hip after the engine's own helpers and before node.h.
+// get_account_flow_matrix, get_account_counterparties and get_active_accounts; their buffers, made at tbgpu_init, and their entry points.  Included by engine.hip after the engine's own helpers and before node.h.
 //
 // Every query is written once, over a list of engines (QueryCall): the one engine, or a node's shards.
 // A transfer lives on its home shard only and an account is answered by its owner only, so every
@@ -194,9 +194,10 @@ struct MatrixBufs {
 };
 #define MATRIX_BIN_BYTES(keys) (((u64)(keys) * MATRIX_BIN_WORDS + 1) * 8)
 
-// tbgpu_get_account_counterparties (k_counterparties.h): the group table, the select's per-tile counts,
-// state words and histograms, the collected keys and the answer; made by query_init and shared with
-// nothing.  The table has room for `groups` counterparties at a load of at most one half: the engine's
+// tbgpu_get_account_counterparties (k_counterparties.h) and tbgpu_get_active_accounts (k_activity.h): the
+// group table, the select's per-tile counts, state words and histograms, the collected keys and the
+// answer; made by query_init and shared by the two calls alone (calls are synchronous, so two never
+// overlap).  The table has room for `groups` counterparties, or accounts, at a load of at most one half: the engine's
 // accounts_max, on a node's shard the node's (query_groups_hint: a peer's table is folded into the
 // first shard's slot for slot, and a group's sums must be whole before the order is applied).
 struct CounterpartyBufs {
@@ -1793,15 +1794,16 @@ static bool counterparty_filter_valid(const tbgpu_counterparty_filter* f) {
     return f->limit != 0;
 }
 
-static int counterparty_enqueue_scan(tbgpu* E, const NodeTablesArgs& NT, u32 self, const CpFilter& F, bool mirror) {
+// launch(nb, records, K): the member's scan kernel over E's log, on E's stream.
+template <typename LAUNCH>
+static int counterparty_enqueue_scan(tbgpu* E, bool mirror, LAUNCH launch) {
     CounterpartyBufs& K = E->qs->qk;
     HIPCK(hipSetDevice(E->device));
     HIPCK(hipMemsetAsync(K.d_table, 0, K.slots * CP_SLOT_WORDS * 8, E->stream));
     HIPCK(hipMemsetAsync(K.d_state, 0, CP_STATE_BYTES, E->stream));
     const u64 records = E->log_next, per = (u64)CHANGE_THREADS * CHANGE_TILES, nb = (records + per - 1) / per;
     if (nb) {
-        hipLaunchKernelGGL(tb_cp_scan, dim3((unsigned)nb), dim3(CHANGE_THREADS), 0, E->stream, NT, self, records, F, K.d_table,
-                           (u32)(K.slots - 1), K.d_state);
+        launch((unsigned)nb, records, K);
         HIPCK(hipGetLastError());
     }
     if (mirror) HIPCK(hipMemcpyAsync(K.h_state, K.d_state, (u64)CP_WORDS * 8, hipMemcpyDeviceToHost, E->stream));
@@ -1809,8 +1811,8 @@ static int counterparty_enqueue_scan(tbgpu* E, const NodeTablesArgs& NT, u32 sel
 }
 
 // On the first engine's stream: the peers' tables folded in (a node), then count -> begin -> the
-// select's passes -> collect -> emit, and the state words on their way back.
-static int counterparty_enqueue_select(const QueryCall& c, const NodeTablesArgs& NT, u32 by_volume) {
+// select's passes -> collect -> emit, and the state words on their way back.  order: a CP_ORDER_*.
+static int counterparty_enqueue_select(const QueryCall& c, const NodeTablesArgs& NT, u32 order) {
     tbgpu* E = c.Es[0];
     CounterpartyBufs& K = E->qs->qk;
     HIPCK(hipSetDevice(E->device));
@@ -1821,23 +1823,79 @@ static int counterparty_enqueue_select(const QueryCall& c, const NodeTablesArgs&
                            mask, K.d_state);
     }
     u32* hist = (u32*)(K.d_state + CP_WORDS);
-    hipLaunchKernelGGL(tb_cp_count, dim3(nb), dim3(QUERY_THREADS), 0, E->stream, NT, (const u64*)K.d_table, mask, by_volume, K.d_counts,
+    hipLaunchKernelGGL(tb_cp_count, dim3(nb), dim3(QUERY_THREADS), 0, E->stream, NT, (const u64*)K.d_table, mask, order, K.d_counts,
                        K.d_state);
     if (k) {
         hipLaunchKernelGGL(tb_cp_begin, dim3(1), dim3(64), 0, E->stream, k, K.d_state);
-        const u32 passes = (by_volume ? CP_KEY_WORDS : 2) * CP_WORD_PASSES;  // by id the key is two words
+        const u32 passes = tb_cp_order_words(order) * CP_WORD_PASSES;  // by id the key is two words
         for (u32 pass = 0; pass < passes; pass++) {
-            hipLaunchKernelGGL(tb_cp_hist, dim3(wide), dim3(QUERY_THREADS), 0, E->stream, NT, (const u64*)K.d_table, mask, by_volume,
+            hipLaunchKernelGGL(tb_cp_hist, dim3(wide), dim3(QUERY_THREADS), 0, E->stream, NT, (const u64*)K.d_table, mask, order,
                                (const u32*)K.d_counts, nb, k, pass, (const u64*)K.d_state, hist);
             hipLaunchKernelGGL(tb_cp_pick, dim3(1), dim3(1024), 0, E->stream, k, pass, (const u32*)hist, K.d_state);
         }
-        hipLaunchKernelGGL(tb_cp_collect, dim3(wide), dim3(QUERY_THREADS), 0, E->stream, NT, (const u64*)K.d_table, mask, by_volume,
+        hipLaunchKernelGGL(tb_cp_collect, dim3(wide), dim3(QUERY_THREADS), 0, E->stream, NT, (const u64*)K.d_table, mask, order,
                            (const u32*)K.d_counts, nb, k, K.d_state, K.d_keys);
         hipLaunchKernelGGL(tb_cp_emit, dim3((k + CP_EMIT_KEYS - 1) / CP_EMIT_KEYS), dim3(QUERY_THREADS), 0, E->stream, NT,
                            (const u64*)K.d_table, mask, k, (const u64*)K.d_state, (const u64*)K.d_keys, K.d_out);
     }
     HIPCK(hipGetLastError());
     HIPCK(hipMemcpyAsync(K.h_state, K.d_state, (u64)CP_WORDS * 8, hipMemcpyDeviceToHost, E->stream));
+    return TBGPU_STATUS_OK;
+}
+
+// The driver after query_begin and the filter's checks, shared with get_active_accounts: every engine
+// drained, the scans side by side (launch(d, nb, records, K): shard d's scan kernel), the select, the
+// flags, the rows.  `name` is the call's, `what` what its groups are, for the capacity message.
+template <typename LAUNCH>
+static int counterparty_answer(QueryCall& c, NodeTablesArgs& NT, u32 order, const char* name, const char* what, void* out,
+                               tbgpu_query_result* result, LAUNCH launch) {
+    NT.world = c.world;
+    for (u32 d = 0; d < c.world; d++) NT.T[d] = c.Es[d]->T;
+    // Every engine is drained before any is asked: a scan reads its posts' pending transfers on their homes.
+    for (u32 d = 0; d < c.world; d++) {
+        HIPCK(hipSetDevice(c.Es[d]->device));
+        if (c.Es[d]->pending) {
+            const int st = engine_sync(c.Es[d]);
+            if (st) return query_end(result, st);
+        }
+    }
+    const bool one = c.world == 1;
+    int st = query_side_by_side(c.Es, c.world, [&](u32 d) -> int {
+        const int s = counterparty_enqueue_scan(c.Es[d], !one, [&](unsigned nb, u64 records, CounterpartyBufs& K) { launch(d, nb, records, K); });
+        if (s) return s;
+        return one ? counterparty_enqueue_select(c, NT, order) : TBGPU_STATUS_OK;
+    });
+    if (st) return query_end(result, st);
+    u64 orphan = 0, overflow = 0;
+    if (!one) {  // the peers' flags are back; the first shard's follow with the select's words
+        for (u32 d = 1; d < c.world; d++) orphan |= c.Es[d]->qs->qk.h_state[CP_ORPHAN], overflow |= c.Es[d]->qs->qk.h_state[CP_OVERFLOW];
+        st = counterparty_enqueue_select(c, NT, order);
+        if (st == TBGPU_STATUS_OK) st = query_wait(c.Es[0]);
+        if (st) return query_end(result, st);
+    }
+    tbgpu* E0 = c.Es[0];
+    const CounterpartyBufs& K = E0->qs->qk;
+    orphan |= K.h_state[CP_ORPHAN], overflow |= K.h_state[CP_OVERFLOW];
+    if (overflow) {
+        return query_end(result, fail(TBGPU_STATUS_INVALID,
+                                      "%s: the matching records name more distinct %s than the "
+                                      "group table holds (capacity: %llu groups, %llu slots)",
+                                      name, what, (unsigned long long)K.groups, (unsigned long long)K.slots));
+    }
+    const u64 matched = K.h_state[CP_TOTAL];
+    const u32 m = (u32)std::min<u64>(c.k, matched);
+    if (m && std::min<u64>(c.k, K.h_state[CP_NKEYS]) != m) {
+        return query_end(result, fail(TBGPU_STATUS_PANIC, "%s: %llu keys selected for %u of %llu groups", name,
+                                      (unsigned long long)K.h_state[CP_NKEYS], m, (unsigned long long)matched));
+    }
+    if (m) {
+        HIPCK(hipSetDevice(E0->device));
+        HIPCK(hipMemcpyAsync(out, K.d_out, (u64)m * CP_ROW_BYTES, hipMemcpyDeviceToHost, E0->stream));
+        HIPCK(hipStreamSynchronize(E0->stream));
+    }
+    if (orphan) result->complete = 0;
+    result->count = m;
+    result->matched = matched;
     return TBGPU_STATUS_OK;
 }
 
@@ -1854,60 +1912,59 @@ extern "C" int tbgpu_get_account_counterparties(tbgpu_t* E, const tbgpu_counterp
         return st;
     }
     if (!counterparty_filter_valid(filter)) return TBGPU_STATUS_OK;
-    NodeTablesArgs NT{};
-    NT.world = c.world;
-    for (u32 d = 0; d < c.world; d++) NT.T[d] = c.Es[d]->T;
-    // Every engine is drained before any is asked: a scan reads its posts' pending transfers on their homes.
-    for (u32 d = 0; d < c.world; d++) {
-        HIPCK(hipSetDevice(c.Es[d]->device));
-        if (c.Es[d]->pending) {
-            const int st = engine_sync(c.Es[d]);
-            if (st) return query_end(result, st);
-        }
-    }
     CpFilter F{};
     F.a_lo = filter->account_id_lo, F.a_hi = filter->account_id_hi;
     F.t_open = filter->t_open, F.t_close = filter->t_close;
     F.min_lo = filter->id_min_lo, F.min_hi = filter->id_min_hi;
     F.sides = filter->flags & (TBGPU_FILTER_DEBITS | TBGPU_FILTER_CREDITS);
     F.by_volume = (filter->flags & TBGPU_COUNTERPARTIES_BY_VOLUME) != 0;
-    const bool one = c.world == 1;
-    int st = query_side_by_side(c.Es, c.world, [&](u32 d) -> int {
-        if (const int s = counterparty_enqueue_scan(c.Es[d], NT, d, F, !one)) return s;
-        return one ? counterparty_enqueue_select(c, NT, F.by_volume) : TBGPU_STATUS_OK;
-    });
-    if (st) return query_end(result, st);
-    u64 orphan = 0, overflow = 0;
-    if (!one) {  // the peers' flags are back; the first shard's follow with the select's words
-        for (u32 d = 1; d < c.world; d++) orphan |= c.Es[d]->qs->qk.h_state[CP_ORPHAN], overflow |= c.Es[d]->qs->qk.h_state[CP_OVERFLOW];
-        st = counterparty_enqueue_select(c, NT, F.by_volume);
-        if (st == TBGPU_STATUS_OK) st = query_wait(c.Es[0]);
-        if (st) return query_end(result, st);
+    NodeTablesArgs NT{};
+    return counterparty_answer(c, NT, F.by_volume ? CP_ORDER_VOLUME : CP_ORDER_ID, "get_account_counterparties", "counterparties", out, result,
+                               [&](u32 d, unsigned nb, u64 records, CounterpartyBufs& K) {
+                                   hipLaunchKernelGGL(tb_cp_scan, dim3(nb), dim3(CHANGE_THREADS), 0, c.Es[d]->stream, NT, d, records, F,
+                                                      K.d_table, (u32)(K.slots - 1), K.d_state);
+                               });
+}
+
+// ---- get_active_accounts (k_activity.h, include/tbgpu.h) -------------------------------------------
+// get_account_counterparties' driver, buffers and select with another scan: nobody is the subject.
+static bool activity_filter_valid(const tbgpu_activity_filter* f) {
+    if ((f->flags & (TBGPU_FILTER_DEBITS | TBGPU_FILTER_CREDITS)) == 0) return false;
+    if (f->flags & ~(u32)(TBGPU_FILTER_DEBITS | TBGPU_FILTER_CREDITS | TBGPU_ACTIVE_BY_VOLUME | TBGPU_ACTIVE_BY_TRANSFERS)) return false;
+    if ((f->flags & TBGPU_ACTIVE_BY_VOLUME) && (f->flags & TBGPU_ACTIVE_BY_TRANSFERS)) return false;
+    for (u32 i = 0; i < sizeof f->reserved0; i++) {
+        if (f->reserved0[i]) return false;
     }
-    tbgpu* E0 = c.Es[0];
-    const CounterpartyBufs& K = E0->qs->qk;
-    orphan |= K.h_state[CP_ORPHAN], overflow |= K.h_state[CP_OVERFLOW];
-    if (overflow) {
-        return query_end(result, fail(TBGPU_STATUS_INVALID,
-                                      "get_account_counterparties: the matching records name more distinct counterparties than the "
-                                      "group table holds (capacity: %llu groups, %llu slots)",
-                                      (unsigned long long)K.groups, (unsigned long long)K.slots));
+    for (u32 i = 0; i < sizeof f->reserved; i++) {
+        if (f->reserved[i]) return false;
     }
-    const u64 matched = K.h_state[CP_TOTAL];
-    const u32 m = (u32)std::min<u64>(c.k, matched);
-    if (m && std::min<u64>(c.k, K.h_state[CP_NKEYS]) != m) {
-        return query_end(result, fail(TBGPU_STATUS_PANIC, "get_account_counterparties: %llu keys selected for %u of %llu groups",
-                                      (unsigned long long)K.h_state[CP_NKEYS], m, (unsigned long long)matched));
-    }
-    if (m) {
-        HIPCK(hipSetDevice(E0->device));
-        HIPCK(hipMemcpyAsync(out, K.d_out, (u64)m * CP_ROW_BYTES, hipMemcpyDeviceToHost, E0->stream));
-        HIPCK(hipStreamSynchronize(E0->stream));
-    }
-    if (orphan) result->complete = 0;
-    result->count = m;
-    result->matched = matched;
-    return TBGPU_STATUS_OK;
+    if (f->t_open == ~0ULL || f->t_close == ~0ULL || (f->t_close != 0 && f->t_close < f->t_open)) return false;
+    return f->limit != 0;
+}
+
+extern "C" int tbgpu_get_active_accounts(tbgpu_t* E, const tbgpu_activity_filter* filter, void* out, uint32_t out_cap_rows,
+                                         tbgpu_query_result* result) {
+    static_assert(sizeof(tbgpu_activity_filter) == 64 && sizeof(tbgpu_account_activity) == ACT_ROW_BYTES &&
+                      offsetof(tbgpu_account_activity, debits) == CP_TO * 8 &&
+                      offsetof(tbgpu_account_activity, credits) == (CP_TO + CP_FLOW_WORDS) * 8 && ACT_ROWS_MAX == TBGPU_ACTIVE_ROWS_MAX &&
+                      ACT_ROWS_MAX <= CP_ROWS_MAX && offsetof(tbgpu_activity_filter, ledger) == 32 &&
+                      offsetof(tbgpu_activity_filter, limit) == 40,
+                  "k_activity.h's constants are the header's");
+    QueryCall c;
+    if (const int st = query_begin(E, "get_active_accounts", filter, out, out_cap_rows, TBGPU_ACTIVE_ROWS_MAX, true, result, &c)) return st;
+    if (!activity_filter_valid(filter)) return TBGPU_STATUS_OK;
+    ActFilter F{};
+    F.t_open = filter->t_open, F.t_close = filter->t_close;
+    F.min_lo = filter->id_min_lo, F.min_hi = filter->id_min_hi;
+    tb_activity_w14(filter->ledger, filter->code, F.w14_mask, F.w14);
+    F.sides = filter->flags & (TBGPU_FILTER_DEBITS | TBGPU_FILTER_CREDITS);
+    const u32 order = (filter->flags & TBGPU_ACTIVE_BY_VOLUME) ? CP_ORDER_VOLUME : (filter->flags & TBGPU_ACTIVE_BY_TRANSFERS) ? CP_ORDER_TRANSFERS : CP_ORDER_ID;
+    NodeTablesArgs NT{};
+    return counterparty_answer(c, NT, order, "get_active_accounts", "accounts", out, result,
+                               [&](u32 d, unsigned nb, u64 records, CounterpartyBufs& K) {
+                                   hipLaunchKernelGGL(tb_activity_scan, dim3(nb), dim3(CHANGE_THREADS), 0, c.Es[d]->stream, NT, d, records,
+                                                      F, K.d_table, (u32)(K.slots - 1), K.d_state);
+                               });
 }
 
 // ---- get_ledger_balances (k_ledgers.h, include/tbgpu.h) -------------------------------------------

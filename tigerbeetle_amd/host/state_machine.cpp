@@ -363,6 +363,12 @@ tbgpu_query_result StateMachine::get_account_counterparties(const tbgpu_counterp
     return r;
 }
 
+tbgpu_query_result StateMachine::get_active_accounts(const tbgpu_activity_filter& filter, void* out, uint32_t out_cap_rows) {
+    tbgpu_query_result r{};
+    check(tbgpu_get_active_accounts(engine_, &filter, out, out_cap_rows, &r), "get_active_accounts");
+    return r;
+}
+
 tbgpu_query_result StateMachine::query_transfers(const tbgpu_query_filter& filter, void* out, uint32_t out_cap_records) {
     tbgpu_query_result r{};
     check(tbgpu_query_transfers(engine_, &filter, out, out_cap_records, &r), "query_transfers");

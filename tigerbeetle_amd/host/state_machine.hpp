@@ -332,6 +332,16 @@ public:
     // post had lost its pending transfer.
     tbgpu_query_result get_account_counterparties(const tbgpu_counterparty_filter& filter, void* out, uint32_t out_cap_rows);
 
+    // The accounts the records of (filter.t_open, filter.t_close] name (tbgpu_get_active_accounts; a read,
+    // and no reference operation behind it): one tbgpu_account_activity per distinct account id at or above
+    // filter.id_min — what it paid (`debits`) and what it was paid (`credits`), each a flow cell's sums,
+    // over the records that carry filter.ledger and filter.code (0: any) — by id ascending, or under
+    // TBGPU_ACTIVE_BY_VOLUME by posted volume descending, or under TBGPU_ACTIVE_BY_TRANSFERS by record
+    // count descending, at most filter.limit and TBGPU_ACTIVE_ROWS_MAX, all from one scan of the log.
+    // result.matched is the number of groups; result.complete == 0: transfers were evicted or a matching
+    // post had lost its pending transfer.
+    tbgpu_query_result get_active_accounts(const tbgpu_activity_filter& filter, void* out, uint32_t out_cap_rows);
+
     // The field-filter queries (tbgpu_query_transfers / tbgpu_query_accounts; reads, not commits): the
     // resident transfers, or the accounts, whose user_data_128 / user_data_64 / user_data_32 / ledger /
     // code equal the filter's non-zero fields, by timestamp (newest first under TBGPU_QUERY_REVERSED),

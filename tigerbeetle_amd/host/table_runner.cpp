@@ -325,9 +325,11 @@ std::string run_table(tb::StateMachine& sm, const std::string& text) {
 // get_account_flow_matrix (the records are tbgpu_flow_cell cells).
 // --query-counterparties (tests/test_gpu_counterparties_cpp.py): the prepares ending in {0, 0, 64, a
 // tbgpu_counterparty_filter}, answered by get_account_counterparties (the records are tbgpu_counterparty rows).
+// --query-active (tests/test_gpu_activity_cpp.py): the prepares ending in {0, 0, 64, a tbgpu_activity_filter},
+// answered by get_active_accounts (the records are tbgpu_account_activity rows).
 enum QueryKind { ACCOUNT_TRANSFERS, ACCOUNT_BALANCES, QUERY_TRANSFERS, QUERY_ACCOUNTS, CHANGE_EVENTS, ACCOUNT_TRANSFERS_MANY, ACCOUNTS_AT,
                  LEDGER_BALANCES, PENDING_TRANSFERS, ACCOUNT_STATEMENTS, ACCOUNT_INTEGRALS, ACCOUNT_SERIES, ACCOUNT_FLOW_MATRIX,
-                 ACCOUNT_COUNTERPARTIES };
+                 ACCOUNT_COUNTERPARTIES, ACTIVE_ACCOUNTS };
 
 int run_query(tb::StateMachine& sm, QueryKind kind, const char* in_path, const char* out_path) {
     std::ifstream in(in_path, std::ios::binary);
@@ -491,6 +493,20 @@ int run_query(tb::StateMachine& sm, QueryKind kind, const char* in_path, const c
         printf("query: %u of %llu rows, complete %u\n", r.count, (unsigned long long)r.matched, r.complete);
         return o ? 0 : 2;
     }
+    if (kind == ACTIVE_ACCOUNTS) {
+        tbgpu_activity_filter af;
+        if (body.size() != sizeof(af)) {
+            fprintf(stderr, "%s: an activity filter is %zu bytes\n", in_path, sizeof(af));
+            return 2;
+        }
+        memcpy(&af, body.data(), sizeof(af));
+        std::vector<uint8_t> out((size_t)TBGPU_ACTIVE_ROWS_MAX * sizeof(tbgpu_account_activity));
+        const tbgpu_query_result r = sm.get_active_accounts(af, out.data(), TBGPU_ACTIVE_ROWS_MAX);
+        std::ofstream o(out_path, std::ios::binary);
+        o.write((const char*)&r, sizeof(r)).write((const char*)out.data(), (size_t)r.count * sizeof(tbgpu_account_activity));
+        printf("query: %u of %llu rows, complete %u\n", r.count, (unsigned long long)r.matched, r.complete);
+        return o ? 0 : 2;
+    }
     if (kind == PENDING_TRANSFERS) {
         tbgpu_pending_filter pf;
         if (body.size() != sizeof(pf)) {
@@ -541,8 +557,9 @@ int main(int argc, char** argv) {
     const bool series = argc > 1 && std::string(argv[1]) == "--query-series";
     const bool matrix = argc > 1 && std::string(argv[1]) == "--query-flow-matrix";
     const bool counterparties = argc > 1 && std::string(argv[1]) == "--query-counterparties";
-    const bool query = counterparties || matrix || fields || balances || changes || many || at || ledgers || pending || statements || integrals || series || (argc > 1 && std::string(argv[1]) == "--query");
-    QueryKind kind = counterparties ? ACCOUNT_COUNTERPARTIES : matrix ? ACCOUNT_FLOW_MATRIX : series ? ACCOUNT_SERIES : balances ? ACCOUNT_BALANCES : changes ? CHANGE_EVENTS : many ? ACCOUNT_TRANSFERS_MANY : at ? ACCOUNTS_AT : ledgers ? LEDGER_BALANCES : pending ? PENDING_TRANSFERS : statements ? ACCOUNT_STATEMENTS : integrals ? ACCOUNT_INTEGRALS : ACCOUNT_TRANSFERS;
+    const bool active = argc > 1 && std::string(argv[1]) == "--query-active";
+    const bool query = active || counterparties || matrix || fields || balances || changes || many || at || ledgers || pending || statements || integrals || series || (argc > 1 && std::string(argv[1]) == "--query");
+    QueryKind kind = active ? ACTIVE_ACCOUNTS : counterparties ? ACCOUNT_COUNTERPARTIES : matrix ? ACCOUNT_FLOW_MATRIX : series ? ACCOUNT_SERIES : balances ? ACCOUNT_BALANCES : changes ? CHANGE_EVENTS : many ? ACCOUNT_TRANSFERS_MANY : at ? ACCOUNTS_AT : ledgers ? LEDGER_BALANCES : pending ? PENDING_TRANSFERS : statements ? ACCOUNT_STATEMENTS : integrals ? ACCOUNT_INTEGRALS : ACCOUNT_TRANSFERS;
     const char* self = argv[0];
     if (fields && argc > 2) {
         const std::string which = argv[2];
@@ -564,8 +581,9 @@ int main(int argc, char** argv) {
                 "       %s --query-series <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-flow-matrix <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-counterparties <prepares.bin> <answer.bin> [device]\n"
+                "       %s --query-active <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-fields <transfers|accounts> <prepares.bin> <answer.bin> [device]\n",
-                self, self, self, self, self, self, self, self, self, self, self, self, self, self);
+                self, self, self, self, self, self, self, self, self, self, self, self, self, self, self);
         return 2;
     }
     if (query) {

@@ -23,7 +23,7 @@ import numpy as np
 
 from . import _lib
 from .types import (ACCOUNT_BALANCE_DTYPE, ACCOUNT_DTYPE, ACCOUNT_FILTER_DTYPE, BATCH_MAX, CHANGE_EVENT_DTYPE, CHANGE_EVENTS_FILTER_DTYPE,
-                    CHANGE_EVENTS_MAX, LEDGER_BALANCE_DTYPE, LEDGERS_MAX, PENDING_FILTER_DTYPE, PENDING_ROW_DTYPE, PENDING_ROWS_MAX, PENDING_STATES, STATEMENT_DTYPE, INTEGRAL_DTYPE, FLOW_CELL_DTYPE, COUNTERPARTY_DTYPE, COUNTERPARTIES_BY_VOLUME, COUNTERPARTIES_ROWS_MAX, pack_counterparty_filter, FILTER_CREDITS, FILTER_DEBITS, FILTER_REVERSED, pack_change_events_filter, QUERY_FILTER_DTYPE, QUERY_REVERSED, TRANSFER_DTYPE, U64_MAX, Operation)
+                    CHANGE_EVENTS_MAX, LEDGER_BALANCE_DTYPE, LEDGERS_MAX, PENDING_FILTER_DTYPE, PENDING_ROW_DTYPE, PENDING_ROWS_MAX, PENDING_STATES, STATEMENT_DTYPE, INTEGRAL_DTYPE, FLOW_CELL_DTYPE, COUNTERPARTY_DTYPE, COUNTERPARTIES_BY_VOLUME, COUNTERPARTIES_ROWS_MAX, pack_counterparty_filter, ACCOUNT_ACTIVITY_DTYPE, ACTIVE_BY_TRANSFERS, ACTIVE_BY_VOLUME, ACTIVE_ROWS_MAX, pack_activity_filter, FILTER_CREDITS, FILTER_DEBITS, FILTER_REVERSED, pack_change_events_filter, QUERY_FILTER_DTYPE, QUERY_REVERSED, TRANSFER_DTYPE, U64_MAX, Operation)
 
 
 def average_balances(row):
@@ -686,6 +686,51 @@ class Engine:
         return [(int(r["id_lo"]) | int(r["id_hi"]) << 64, int(r["to_posted_lo"]) | int(r["to_posted_hi"]) << 64,
                  int(r["from_posted_lo"]) | int(r["from_posted_hi"]) << 64) for r in rows]
 
+    ACTIVE_ROWS_MAX = ACTIVE_ROWS_MAX  # TBGPU_ACTIVE_ROWS_MAX
+
+    def get_active_accounts(self, t_open=0, t_close=0, *, ledger=0, code=0, debits=True, credits=True, by=None, id_min=0,
+                            limit=ACTIVE_ROWS_MAX, out_cap_rows=None):
+        """The accounts the records of the period (t_open, t_close] name (tbgpu_get_active_accounts): one
+        ACCOUNT_ACTIVITY_DTYPE row per distinct account at or above `id_min`, with what it paid
+        (debits_*) and what it was paid (credits_*) — amounts posted, holds placed and released, and the
+        number of records, as a flow-matrix cell has them.  `ledger` and `code` narrow the records (0:
+        any).  Rows come by account id ascending (page with id_min = the last id + 1), or with
+        by="volume" by debits_posted + credits_posted descending, or with by="transfers" by
+        debits_transfers + credits_transfers descending, ties by id.  t_open 0: from before every
+        record; t_close 0: up to now.  Returns (rows, matched, complete): `matched` is the number of
+        groups, `complete` is False once the engine has evicted transfers or a matching post had lost
+        its pending transfer.  An invalid filter matches nothing."""
+        if by not in (None, "id", "volume", "transfers"):
+            raise ValueError("by is None, 'id', 'volume' or 'transfers'")
+        flags = (FILTER_DEBITS if debits else 0) | (FILTER_CREDITS if credits else 0)
+        flags |= ACTIVE_BY_VOLUME if by == "volume" else ACTIVE_BY_TRANSFERS if by == "transfers" else 0
+        return self.get_active_accounts_raw(
+            pack_activity_filter(int(t_open), int(t_close), int(id_min), int(ledger), int(code), int(limit), flags), out_cap_rows)
+
+    def get_active_accounts_raw(self, filter_bytes, out_cap_rows=None):
+        """get_active_accounts from the 64 bytes of a tbgpu_activity_filter."""
+        filter_bytes = bytes(filter_bytes)
+        if len(filter_bytes) != 64:
+            raise ValueError("a tbgpu_activity_filter is 64 bytes")
+        limit = int.from_bytes(filter_bytes[40:44], "little")
+        cap = min(limit, ACTIVE_ROWS_MAX) if out_cap_rows is None else int(out_cap_rows)
+        if cap < 0 or cap >> 32:
+            raise ValueError("out_cap_rows is 32 bits")
+        out = np.zeros(max(cap, 1), dtype=ACCOUNT_ACTIVITY_DTYPE)
+        res = _lib.tbgpu_query_result()
+        src = ctypes.create_string_buffer(filter_bytes, 64)
+        _lib.check(self.lib.tbgpu_get_active_accounts(self.h, src, out.ctypes.data, cap, ctypes.byref(res)))
+        return out[:res.count], int(res.matched), bool(res.complete)
+
+    def top_accounts(self, t_open=0, t_close=0, k=10, by="volume", *, ledger=0, code=0, debits=True, credits=True):
+        """The `k` most active accounts of the period, by posted volume or (by="transfers") by record
+        count, as [(account id, posted as debit account, posted as credit account, records)] of Python
+        ints, the most active first."""
+        rows, _, _ = self.get_active_accounts(t_open, t_close, ledger=ledger, code=code, debits=debits, credits=credits, by=by, limit=k)
+        return [(int(r["id_lo"]) | int(r["id_hi"]) << 64, int(r["debits_posted_lo"]) | int(r["debits_posted_hi"]) << 64,
+                 int(r["credits_posted_lo"]) | int(r["credits_posted_hi"]) << 64,
+                 int(r["debits_transfers"]) + int(r["credits_transfers"])) for r in rows]
+
     @staticmethod
     def query_filter(user_data_128=0, user_data_64=0, user_data_32=0, ledger=0, code=0, *, reversed=False,
                      timestamp_min=0, timestamp_max=0, limit=8190):
@@ -1101,6 +1146,14 @@ class StateMachine:
     def top_counterparties(self, account_id, k=10, t_open=0, t_close=0, **kwargs):
         """The k largest counterparties by posted volume (Engine.top_counterparties)."""
         return self.engine.top_counterparties(account_id, k, t_open, t_close, **kwargs)
+
+    def get_active_accounts(self, t_open=0, t_close=0, **kwargs):
+        """The accounts a period's records name (Engine.get_active_accounts): a read, not a commit."""
+        return self.engine.get_active_accounts(t_open, t_close, **kwargs)
+
+    def top_accounts(self, t_open=0, t_close=0, k=10, by="volume", **kwargs):
+        """The k most active accounts by posted volume or record count (Engine.top_accounts)."""
+        return self.engine.top_accounts(t_open, t_close, k, by, **kwargs)
 
     def query_transfers(self, **filter):
         """The field-filter query over transfers (Engine.query_transfers): a read, not a commit."""

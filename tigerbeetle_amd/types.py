@@ -195,6 +195,31 @@ def pack_counterparty_filter(account_id, t_open=0, t_close=0, id_min=0, limit=CO
     return f.tobytes()
 
 
+# tbgpu_activity_filter and tbgpu_account_activity (include/tbgpu.h tbgpu_get_active_accounts): 64 and
+# 128 bytes, no padding; a row is an account's id, what it paid (`debits`) and what it was paid
+# (`credits`), each a flow cell's seven sum words.
+ACTIVITY_FILTER_DTYPE = np.dtype(
+    [("t_open", "<u8"), ("t_close", "<u8")] + _u128("id_min")
+    + [("ledger", "<u4"), ("code", "<u2"), ("reserved0", "u1", (2,)), ("limit", "<u4"), ("flags", "<u4"), ("reserved", "u1", (16,))])
+ACCOUNT_ACTIVITY_DTYPE = np.dtype(
+    _u128("id")
+    + [f for c in ("posted", "pending_in", "pending_out") for f in _u128("debits_" + c)] + [("debits_transfers", "<u8")]
+    + [f for c in ("posted", "pending_in", "pending_out") for f in _u128("credits_" + c)] + [("credits_transfers", "<u8")])
+assert ACTIVITY_FILTER_DTYPE.itemsize == 64 and ACCOUNT_ACTIVITY_DTYPE.itemsize == 128
+ACTIVE_BY_VOLUME = 1 << 8
+ACTIVE_BY_TRANSFERS = 1 << 9
+ACTIVE_ROWS_MAX = 8191
+
+
+def pack_activity_filter(t_open=0, t_close=0, id_min=0, ledger=0, code=0, limit=ACTIVE_ROWS_MAX, flags=FILTER_DEBITS | FILTER_CREDITS):
+    """The 64 bytes of a tbgpu_activity_filter."""
+    f = np.zeros(1, dtype=ACTIVITY_FILTER_DTYPE)
+    f["t_open"], f["t_close"] = t_open, t_close
+    f["id_min_lo"], f["id_min_hi"] = id_min & U64_MAX, id_min >> 64
+    f["ledger"], f["code"], f["limit"], f["flags"] = ledger, code, limit, flags
+    return f.tobytes()
+
+
 # tbgpu_query_filter (include/tbgpu.h tbgpu_query_transfers / tbgpu_query_accounts): 64 bytes, no padding.
 QUERY_FILTER_DTYPE = np.dtype(
     _u128("user_data_128") + [("user_data_64", "<u8"), ("user_data_32", "<u4"), ("ledger", "<u4"), ("code", "<u2"),

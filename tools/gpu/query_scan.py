@@ -94,6 +94,18 @@ the same process: one tbgpu_get_account_statements call for that one account and
 and, once per subject by the wall clock, the host alternative the call replaces: the account's
 tbgpu_get_account_transfers pages grouped by counterparty in Python, whose groups are compared with the call's.
 An older library loaded through TBGPU_AB_LIB lacks the call: the yardsticks alone are timed then.
+
+`--only activity` (tbgpu_get_active_accounts) times the C call alone, into buffers made once, on
+the uniform and the Zipf log and on a log whose records all name one pair of accounts (the combine's other
+extreme): the whole log by id at limit 8,191, by volume and by record count at limit 10, a period newer than every
+record, a ledger no record carries (the generator's codes cover all 65,535 values, so the word-14 test that
+nothing passes is on the ledger) and one code (a few hundred records).  The yardsticks run in the same process:
+tbgpu_query_transfers with an all-zero filter, timestamp_min = t_open + 1 and limit 1 (the same liveness probe on
+every record of the window), tbgpu_get_account_counterparties for the Zipf log's hottest account and over an empty
+period (what its scan reads for an empty window), and a device-to-device copy of the log.  The host alternative is
+timed once by the wall clock on the uniform log: tbgpu_query_transfers pages over the whole log, grouped by account
+in numpy, whose groups are compared with the call's (--skip-host leaves it out).  An older library loaded through TBGPU_AB_LIB lacks the
+call: the yardsticks and the host alternative alone are timed then.
 """
 import json
 import os
@@ -890,6 +902,122 @@ def measure_counterparties():
     return out
 
 
+def measure_activity():
+    """get_active_accounts beside query_transfers over the same window, get_account_counterparties and the log's
+    copy, on three logs, in one process."""
+    import ctypes
+    import time
+
+    from tigerbeetle_amd import _lib
+    from tigerbeetle_amd.types import pack_counterparty_filter
+    os.environ["TBGPU_QUERY_COOP"] = "0"
+    e = Engine(Options(accounts_max=n_acct, transfers_max=n_xfer, pass_events_max=pb * batch, pass_batches_max=pb))
+    a_lens = batches(n_acct, batch)
+    a_ts, t = timestamps(a_lens, 1_000_000_000)
+    acct = e.alloc(n_acct * 128)
+    e.generate_accounts(acct, 0, n_acct, seed=42)
+    res = e.alloc(max(n_acct, n_xfer) * 8)
+    rb = e.alloc((n_xfer // batch + 2) * 4)
+    e.commit_device_async(128, a_ts, a_lens, acct, res, rb)
+    e.sync()
+    spare = e.alloc(n_xfer * 128)
+    rows_max = 8191
+    have = hasattr(e.lib, "tbgpu_get_active_accounts")  # an older library (TBGPU_AB_LIB): the yardsticks alone
+    h_out = np.zeros(rows_max * 128, dtype=np.uint8)
+    h_recs = np.zeros(8190, dtype=TRANSFER_DTYPE)
+    h_res = _lib.tbgpu_query_result()
+
+    def raw_active(t_open, t_close, limit, order=0, ledger=0, code=0):
+        from tigerbeetle_amd.types import pack_activity_filter
+        f = pack_activity_filter(t_open, t_close, 0, ledger, code, limit, 3 | order)
+        src = ctypes.create_string_buffer(f, 64)
+        return lambda: _lib.check(e.lib.tbgpu_get_active_accounts(e.h, src, h_out.ctypes.data, rows_max, ctypes.byref(h_res)))
+
+    def raw_counterparties(account, t_open, t_close, limit):
+        f = pack_counterparty_filter(account, t_open, t_close, 0, limit, 3)
+        src = ctypes.create_string_buffer(f, 64)
+        return lambda: _lib.check(e.lib.tbgpu_get_account_counterparties(e.h, src, h_out.ctypes.data, rows_max, ctypes.byref(h_res)))
+
+    def raw_query(**filter):
+        f = Engine.query_filter(**filter)
+        src = ctypes.create_string_buffer(f, len(f))
+        return lambda: _lib.check(e.lib.tbgpu_query_transfers(e.h, src, h_recs.ctypes.data, 8190, ctypes.byref(h_res)))
+
+    def paged(t_open):
+        """The host alternative: {account: records that name it}, from the whole log's pages."""
+        names = []
+        t_min = t_open + 1
+        while True:
+            page, _, _ = e.query_transfers(timestamp_min=t_min, limit=8190)
+            for side in ("debit_account_id", "credit_account_id"):
+                names.append(np.stack([page[side + "_lo"], page[side + "_hi"]], axis=1))
+            if len(page) < 8190:
+                break
+            t_min = int(page["timestamp"][-1]) + 1
+        ids, counts = np.unique(np.concatenate(names), axis=0, return_counts=True)
+        return {int(lo) | int(hi) << 64: int(c) for (lo, hi), c in zip(ids.tolist(), counts.tolist())}
+
+    out = {}
+    for name, kind, accounts in (("uniform", "c2", n_acct), ("zipf", "c3", n_acct), ("one_pair", "c2", 2)):
+        if name != "uniform":
+            e.reset_transfers()
+        log = e.log_window(n_xfer)
+        e.generate_transfers(log, 0, n_xfer, accounts, seed=42, kind=KINDS[kind])
+        e.sync()
+        x_lens = batches(n_xfer, batch)
+        x_ts, t = timestamps(x_lens, t + 10)
+        e.commit_device_async(129, x_ts, x_lens, log, res, rb)
+        e.sync()
+        oldest, _, _ = e.query_transfers(limit=1)
+        newest, _, _ = e.query_transfers(reversed=True, limit=1)
+        t_first, t_last = int(oldest["timestamp"][0]), int(newest["timestamp"][0])
+        t_open = t_first - 1
+        sample = e.to_host(log + (n_xfer // 2) * 128, min(n_xfer // 2, 1 << 16) * 128).view(TRANSFER_DTYPE)
+        ids, counts = np.unique(sample[["debit_account_id_lo", "debit_account_id_hi"]], return_counts=True)
+        hot = int(ids[np.argmax(counts)][0]) | int(ids[np.argmax(counts)][1]) << 64
+        code = int(sample["code"][0])
+        if name == "uniform":
+            med, lo_ms, hi_ms = timed(e, lambda: e.copy_device_async(spare, log, n_xfer * 128))
+            out["copy_log_d2d"] = row(med, lo_ms, hi_ms, bytes=n_xfer * 128)
+            groups = None
+            if "--skip-host" not in sys.argv:
+                start = time.perf_counter()
+                groups = paged(t_open)
+                out["uniform_paged_on_host"] = dict(ms=round((time.perf_counter() - start) * 1e3, 1), groups=len(groups),
+                                                    records=sum(groups.values()) // 2)
+        _, q_matched, _ = e.query_transfers(timestamp_min=t_open + 1, limit=1)
+        q_med, q_lo, q_hi = timed(e, raw_query(timestamp_min=t_open + 1, limit=1))
+        out["%s_query_transfers_limit_1" % name] = row(q_med, q_lo, q_hi, matched=q_matched)
+        c_med, c_lo, c_hi = timed(e, raw_counterparties(hot, t_open, t_last, rows_max))
+        out["%s_counterparties_hottest" % name] = row(c_med, c_lo, c_hi, matched=int(h_res.matched))
+        ce_med, ce_lo, ce_hi = timed(e, raw_counterparties(hot, t_last, t_last + 1, rows_max))
+        out["%s_counterparties_empty_period" % name] = row(ce_med, ce_lo, ce_hi)
+        if not have:
+            continue
+        rows, matched, complete = e.get_active_accounts(t_open, t_last)
+        assert complete and len(rows) == min(matched, rows_max)
+        if name == "uniform" and groups is not None:
+            assert matched == len(groups)
+            mine = {int(r["id_lo"]) | int(r["id_hi"]) << 64: int(r["debits_transfers"]) + int(r["credits_transfers"]) for r in rows}
+            assert all(groups[x] == v for x, v in mine.items())
+        out["%s_most_active" % name] = [list(r) for r in e.top_accounts(t_open, t_last, 3, "transfers")]
+        for leg, fn in (("by_id_limit_8191", raw_active(t_open, t_last, rows_max)),
+                        ("by_volume_limit_10", raw_active(t_open, t_last, 10, 1 << 8)),
+                        ("by_transfers_limit_10", raw_active(t_open, t_last, 10, 1 << 9)),
+                        ("one_code", raw_active(t_open, t_last, rows_max, code=code))):
+            med, lo_ms, hi_ms = timed(e, fn)
+            out["%s_active_%s" % (name, leg)] = row(med, lo_ms, hi_ms, matched=int(h_res.matched), over_query_transfers=round(med / q_med, 2),
+                                                     over_counterparties_hottest=round(med / c_med, 2))
+        for leg, fn in (("empty_period", raw_active(t_last, t_last + 1, rows_max)),
+                        ("ledger_no_record_carries", raw_active(t_open, t_last, rows_max, ledger=3))):
+            med, lo_ms, hi_ms = timed(e, fn)
+            assert h_res.matched == 0
+            out["%s_active_%s" % (name, leg)] = row(med, lo_ms, hi_ms, counterparties_empty_period_ms=round(ce_med, 4),
+                                                     over_counterparties_empty_period=round(med / ce_med, 2))
+    e.close()
+    return out
+
+
 def measure_ledgers():
     """get_ledger_balances beside query_accounts, query_transfers and the copies, in one process."""
     import ctypes
@@ -1082,6 +1210,8 @@ elif only == "matrix":
     result["matrix"] = measure_matrix()
 elif only == "counterparties":
     result["counterparties"] = measure_counterparties()
+elif only == "activity":
+    result["activity"] = measure_activity()
 elif only == "many":
     result["many"] = measure_many()
 elif only == "balances":
@@ -1093,6 +1223,6 @@ elif only != "fields":
     for shape in ("lane_per_record", "cooperative"):
         r = result[shape]
         r["bar_query_le_copy"] = all(v["ms"] <= r["copy_d2d"]["ms"] for k, v in r.items() if k != "copy_d2d")
-if only not in ("account", "balances", "change_events", "many", "asof", "ledgers", "pending", "statements", "integrals", "series", "matrix", "counterparties"):
+if only not in ("account", "balances", "change_events", "many", "asof", "ledgers", "pending", "statements", "integrals", "series", "matrix", "counterparties", "activity"):
     result["field_filters"] = measure_fields()
 print(json.dumps(result))

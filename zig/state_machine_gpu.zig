@@ -928,6 +928,37 @@ pub fn StateMachineType(
             return @as(usize, result.count) * @sizeOf(tbgpu.tbgpu_counterparty);
         }
 
+        /// The accounts the records of (t_open, t_close] name (tbgpu_get_active_accounts): a read, with
+        /// no operation in this reference's enum, so nothing in commit() dispatches to it
+        /// (INTEGRATION.md, "Active accounts"). Every distinct account id at or above `filter.id_min`
+        /// that a record carrying `filter.ledger` and `filter.code` (0: any) names yields one row of
+        /// 128 bytes into `output`, by id ascending or, under TBGPU_ACTIVE_BY_VOLUME, by posted volume
+        /// descending or, under TBGPU_ACTIVE_BY_TRANSFERS, by record count descending; returns the
+        /// bytes written. `matched` receives the number of groups; `complete` is false once transfers
+        /// were evicted or a matching post had lost its pending transfer.
+        pub fn get_active_accounts(
+            self: *StateMachine,
+            filter: *const tbgpu.tbgpu_activity_filter,
+            output: []align(16) u8,
+            matched: *u64,
+            complete: *bool,
+        ) usize {
+            var result: tbgpu.tbgpu_query_result = undefined;
+            result.count = 0;
+            result.complete = 1;
+            result.matched = 0;
+            check(tbgpu.tbgpu_get_active_accounts(
+                self.engine,
+                filter,
+                output.ptr,
+                @intCast(output.len / @sizeOf(tbgpu.tbgpu_account_activity)),
+                &result,
+            ));
+            matched.* = result.matched;
+            complete.* = result.complete != 0;
+            return @as(usize, result.count) * @sizeOf(tbgpu.tbgpu_account_activity);
+        }
+
         pub fn compact(self: *StateMachine, callback: *const fn (*StateMachine) void, op: u64) void {
             assert(self.compact_callback == null);
             assert(self.checkpoint_callback == null);
