@@ -243,6 +243,25 @@ def test_query_accounts_selection_at_capacity(world, gpu_engine_factory):
     assert matched == 1
 
 
+def test_query_accounts_select_early_exit(world, gpu_engine_factory):
+    """The select stops at the pass whose picked digit is wanted whole.  The facts about the fixture
+    that the expected pass counts rest on are asserted first."""
+    engine, accounts = accounts_engine(world, gpu_engine_factory), world["accounts"]
+    ts = accounts["timestamp"].astype(np.uint64)
+    lo, hi = int(ts.min()), int(ts.max())
+    assert len(ts) == N_ACCOUNTS and hi - lo == 1008999 and 1 << 11 <= hi - lo < 1 << 22  # the passes at shift 11 and 0 alone
+    digits = [np.bincount((v >> np.uint64(11)).astype(np.int64)) for v in (ts - np.uint64(lo), np.uint64(hi) - ts)]
+    assert digits[0][digits[0] > 0].tolist() == [2048, 2048, 2048, 2046, 810]  # the occupied digits, ascending
+    assert digits[1][digits[1] > 0].tolist()[:2] == [810, 662]                  # ... and under REVERSED
+    for rev, limit, scans in ((False, 2047, 2), (False, 2048, 1), (False, 2049, 2), (False, 4096, 1), (False, 8190, 1),
+                              (True, 809, 2), (True, 810, 1), (True, 811, 2)):
+        got, matched = check(engine.query_accounts, accounts, {}, reversed=rev, limit=limit)
+        assert matched == N_ACCOUNTS and len(got) == limit
+        assert engine.query_select_scans() == scans, (rev, limit)
+    got, matched = check(engine.query_accounts, accounts, {}, out_cap_records=0)
+    assert matched == N_ACCOUNTS and len(got) == 0
+
+
 def test_query_accounts_loaded_out_of_order(world, gpu_engine_factory):
     """The second prepare's accounts are created first; the first prepare's (earlier timestamps) are then
     loaded in shuffled order, all but ten of ledger 1.  The table's slots are in no order anyway; the

@@ -5,9 +5,9 @@
 //
 // k_counterparties.h groups around one subject: a record is a hit when it names the subject, and it
 // has one key.  Here there is no subject: every live record of the period is a hit on both of its
-// sides.  The group table, tb_cp_claim, tb_cp_merge, the select and the emit are k_counterparties.h's,
-// unchanged (the slot's `to` half holds `debits`, its `from` half `credits`; tb_cp_key has the
-// BY_TRANSFERS key); the new kernel is the scan:
+// sides.  The group table, tb_cp_claim, tb_cp_merge, the select's start (k_select.h does the rest) and
+// the emit are k_counterparties.h's, unchanged (the slot's `to` half holds `debits`, its `from` half
+// `credits`; tb_cp_key has the BY_TRANSFERS key); the new kernel is the scan:
 //   tb_activity_scan  the record step of tb_cp_scan's shape — the timestamp plane first, with word 14
 //                     (ledger and code) from the sector the timestamp field shares, against the filter;
 //                     a whole wave is skipped when no lane is in the period and carries the ledger and

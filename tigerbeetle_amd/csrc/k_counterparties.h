@@ -14,10 +14,9 @@
 //                  workgroup LDS bin claimed by {slot, direction} (tb_change_bin_claim), else into the
 //                  slot in HBM;
 //   the select     the first k of the occupied slots by a multi-word key — {id} by default, {~volume,
-//                  id} under BY_VOLUME, {~count, id} for k_activity.h's BY_TRANSFERS — by k_query_filter.h's most-significant-digit radix select,
-//                  over a key of up to four 64-bit words: tb_cp_count, tb_cp_begin, tb_cp_hist /
-//                  tb_cp_pick, tb_cp_collect;
-//   tb_cp_emit     ranks the collected keys by counting and writes the rows.
+//                  id} under BY_VOLUME, {~count, id} for k_activity.h's BY_TRANSFERS — by k_select.h,
+//                  which tb_cp_count and tb_cp_begin start;
+//   tb_cp_emit     tb_select_rank, then the rows.
 // A node: every shard scans its own log into its own table, then tb_cp_merge folds each peer's table
 // into the first shard's (plain loads of the peer's HBM once its stream is idle, the same find-or-claim
 // by id, local atomics), and the select and the emit run once there: a group's sums are whole before
@@ -38,6 +37,7 @@
 #pragma once
 
 #include "k_matrix.h"
+#include "k_select.h"
 
 #define CP_ROWS_MAX 8191u  // TBGPU_COUNTERPARTIES_ROWS_MAX
 #define CP_ROW_BYTES 128u
@@ -52,30 +52,24 @@
 #define CP_SIDE_DEBITS 1u   // TBGPU_FILTER_DEBITS: records whose debit account is the subject
 #define CP_SIDE_CREDITS 2u  // TBGPU_FILTER_CREDITS
 
-// The select (k_query_filter.h's, over CP_KEY_WORDS words, most significant first).
+// The select's key (k_select.h): CP_KEY_WORDS words, most significant first.
 #define CP_KEY_WORDS 4u
-#define CP_BITS 11u
-#define CP_BINS (1u << CP_BITS)
-#define CP_WORD_PASSES 6u  // 6 x 11 bits cover a 64-bit word
-#define CP_PASSES_MAX (CP_KEY_WORDS * CP_WORD_PASSES)
-#define CP_TILES 4u        // tiles of QUERY_THREADS slots one workgroup of tb_cp_hist / tb_cp_collect covers
-#define CP_KEY_STRIDE 5u   // a collected key: its CP_KEY_WORDS words, then its slot
+#define CP_PASSES_MAX (CP_KEY_WORDS * SEL_WORD_PASSES)
+#define CP_KEY_STRIDE (CP_KEY_WORDS + 1)  // a collected entry: the key's words, then its slot
 
-// Device state of one call, u64 words; the select's histograms follow: u32 [CP_PASSES_MAX][CP_BINS].
+// Device state of one call, u64 words: the select's (SEL_TOTAL: the occupied slots, the groups), the
+// scan's flags and the key bits tb_cp_count gathers.  Every wave of tb_cp_count ORs into CP_ONES and
+// CP_ZEROS, and where those atomics fall among the 128-byte lines decides its time: CP_ONES shares
+// the first line with SEL_TOTAL, CP_ZEROS has the second ("The select").
 enum : u32 {
-    CP_TOTAL = 0,     // M: the occupied slots (the groups)
-    CP_ORPHAN = 1,    // a matching post's pending transfer was not resident
-    CP_OVERFLOW = 2,  // a hit found no slot: more groups than the table holds
-    CP_RANK = 3,      // the selected key is the CP_RANK-th smallest (from 1) among the keys with the prefix
-    CP_DONE = 4,      // the prefix is final: every key at or below it is wanted
-    CP_SCANS = 5,     // select passes that ran
-    CP_NKEYS = 6,     // tb_cp_collect's counter
-    CP_PREFIX = 8,    // [CP_KEY_WORDS] the digits of the selected key chosen so far
-    CP_ONES = 12,     // [CP_KEY_WORDS] the OR of every key
-    CP_ZEROS = 16,    // [CP_KEY_WORDS] the OR of every key's complement
-    CP_WORDS = 20,
+    CP_ORPHAN = SEL_CALLER,        // a matching post's pending transfer was not resident
+    CP_OVERFLOW = SEL_CALLER + 1,  // a hit found no slot: more groups than the table holds
+    CP_ONES = SEL_CALLER + 3,      // [CP_KEY_WORDS] the OR of every key
+    CP_ZEROS = SEL_WORDS,          // [CP_KEY_WORDS] the OR of every key's complement
+    CP_WORDS = SEL_WORDS + 4,
 };
-#define CP_STATE_BYTES ((u64)CP_WORDS * 8 + (u64)CP_PASSES_MAX * CP_BINS * 4)
+static_assert(CP_ONES + CP_KEY_WORDS == 16 && CP_ZEROS >= 16 && CP_ZEROS + CP_KEY_WORDS <= 32, "the key bits' lines");
+#define CP_STATE_BYTES SEL_STATE_BYTES(CP_WORDS, CP_PASSES_MAX)
 
 struct CpFilter {
     u64 a_lo, a_hi;      // the subject
@@ -247,9 +241,6 @@ __device__ static inline bool tb_cp_key(const NodeTablesArgs& N, const u64* tabl
     return true;
 }
 
-__device__ static inline u32 cp_word(u32 pass) { return pass / CP_WORD_PASSES; }
-__device__ static inline u32 cp_shift(u32 pass) { return CP_BITS * (CP_WORD_PASSES - 1 - pass % CP_WORD_PASSES); }
-
 // A tile of QUERY_THREADS slots per workgroup: how many are occupied, into counts[b] and the total, and
 // which bits of the keys are ever one and ever zero.
 __global__ __launch_bounds__(QUERY_THREADS) void tb_cp_count(NodeTablesArgs N, const u64* table, u32 mask, u32 order, u32* counts,
@@ -280,7 +271,7 @@ __global__ __launch_bounds__(QUERY_THREADS) void tb_cp_count(NodeTablesArgs N, c
         u32 c = 0;
         for (u32 w = 0; w < QUERY_WAVES; w++) c += s_cnt[w];
         counts[blockIdx.x] = c;
-        if (c) atomicAdd((unsigned long long*)&st[CP_TOTAL], (unsigned long long)c);
+        if (c) atomicAdd((unsigned long long*)&st[SEL_TOTAL], (unsigned long long)c);
     }
 }
 
@@ -288,150 +279,31 @@ __global__ __launch_bounds__(QUERY_THREADS) void tb_cp_count(NodeTablesArgs N, c
 // digit no two keys differ in has nothing to decide.
 __global__ void tb_cp_begin(u32 k, u64* st) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    st[CP_RANK] = k;
-    for (u32 q = 0; q < CP_KEY_WORDS; q++) st[CP_PREFIX + q] = st[CP_ONES + q] & ~st[CP_ZEROS + q];
-}
-
-// Whether select pass `pass` has a digit to decide: more groups than wanted, a prefix that is not
-// final, and two keys that differ in the digit.  The same for every thread of every workgroup.
-__device__ static inline bool cp_pass_runs(const u64* st, u32 k, u32 pass) {
-    if (st[CP_TOTAL] <= k || st[CP_DONE]) return false;
-    const u64 varies = st[CP_ONES + cp_word(pass)] & st[CP_ZEROS + cp_word(pass)];
-    return ((varies >> cp_shift(pass)) & (CP_BINS - 1)) != 0;
-}
-
-// Whether K carries the digits chosen before `pass`.
-__device__ static inline bool cp_has_prefix(const u64 (&K)[CP_KEY_WORDS], const u64* prefix, u32 pass) {
-    const u32 w = cp_word(pass), above = cp_shift(pass) + CP_BITS;
-    for (u32 q = 0; q < w; q++) {
-        if (K[q] != prefix[q]) return false;
-    }
-    return above >= 64 || (K[w] >> above) == (prefix[w] >> above);
-}
-
-__global__ __launch_bounds__(QUERY_THREADS) void tb_cp_hist(NodeTablesArgs N, const u64* table, u32 mask, u32 order,
-                                                            const u32* counts, u32 nblocks, u32 k, u32 pass, const u64* st, u32* hist) {
-    __shared__ u32 s_hist[CP_BINS];
-    if (!cp_pass_runs(st, k, pass)) return;
-    for (u32 i = threadIdx.x; i < CP_BINS; i += QUERY_THREADS) s_hist[i] = 0;
-    __syncthreads();
-    u64 prefix[CP_KEY_WORDS];
-#pragma unroll
-    for (u32 q = 0; q < CP_KEY_WORDS; q++) prefix[q] = st[CP_PREFIX + q];
-    const u32 w = cp_word(pass), shift = cp_shift(pass);
-    bool any = false;
-    for (u32 t = 0; t < CP_TILES; t++) {
-        const u32 b = blockIdx.x * CP_TILES + t;
-        if (b >= nblocks || counts[b] == 0) continue;  // the whole workgroup alike
-        any = true;
-        u64 K[CP_KEY_WORDS];
-        if (!tb_cp_key(N, table, (u64)b * QUERY_THREADS + threadIdx.x, mask, order, K)) continue;
-        if (cp_has_prefix(K, prefix, pass)) atomicAdd(&s_hist[(K[w] >> shift) & (CP_BINS - 1)], 1u);
-    }
-    if (!any) return;
-    __syncthreads();
-    u32* out = hist + (u64)pass * CP_BINS;
-    for (u32 i = threadIdx.x; i < CP_BINS; i += QUERY_THREADS) {
-        const u32 c = s_hist[i];
-        if (c) __hip_atomic_fetch_add(&out[i], c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    st[SEL_RANK] = k;
+    for (u32 q = 0; q < CP_KEY_WORDS; q++) {
+        st[SEL_PREFIX + q] = st[CP_ONES + q] & ~st[CP_ZEROS + q];
+        st[SEL_VARIES + q] = st[CP_ONES + q] & st[CP_ZEROS + q];
     }
 }
 
-// One workgroup: the digit under which the CP_RANK-th smallest key falls.  Where that digit's keys are
-// all wanted — the rank is their count — the prefix is final: every bit below the digit becomes one,
-// and the remaining passes exit.
-__global__ __launch_bounds__(1024) void tb_cp_pick(u32 k, u32 pass, const u32* hist, u64* st) {
-    __shared__ u32 s_wave[1024 / 64];
-    static_assert(CP_BINS == 2 * 1024, "two bins a thread");
-    if (!cp_pass_runs(st, k, pass)) return;
-    const u32* h = hist + (u64)pass * CP_BINS;
-    const u32 c0 = h[2 * threadIdx.x], c1 = h[2 * threadIdx.x + 1];
-    u32 all;
-    const u64 before = tb_block_excl_sum(c0 + c1, s_wave, &all);
-    const u32 w = cp_word(pass), shift = cp_shift(pass);
-    const u64 rank = st[CP_RANK], prefix = st[CP_PREFIX + w];
-    __syncthreads();  // every thread has read the state before one rewrites it
-    if (rank > before && rank <= before + c0 + c1) {
-        const bool second = rank > before + c0;
-        const u64 digit = 2 * threadIdx.x + second, left = rank - before - (second ? c0 : 0);
-        u64 p = (prefix & ~((u64)(CP_BINS - 1) << shift)) | digit << shift;
-        if (left == (second ? c1 : c0)) {
-            p |= (1ULL << shift) - 1;
-            for (u32 q = w + 1; q < CP_KEY_WORDS; q++) st[CP_PREFIX + q] = ~0ULL;
-            st[CP_DONE] = 1;
-        }
-        st[CP_PREFIX + w] = p;
-        st[CP_RANK] = left;
-        st[CP_SCANS] += 1;
-    }
-}
+// The select's key source: tb_cp_key of the group table's slot.
+struct CpSource {
+    static constexpr u32 WORDS = CP_KEY_WORDS;
+    NodeTablesArgs N;
+    const u64* table;
+    u32 mask, order;
+    __device__ bool key(u64 slot, u64 (&K)[WORDS]) const { return tb_cp_key(N, table, slot, mask, order, K); }
+};
 
-// The groups whose key is at or below the selected one append {key, slot} to the k-entry key buffer
-// through one counter.  Ids are unique, so exactly min(k, M) qualify; the store is guarded all the same.
-__global__ __launch_bounds__(QUERY_THREADS) void tb_cp_collect(NodeTablesArgs N, const u64* table, u32 mask, u32 order,
-                                                               const u32* counts, u32 nblocks, u32 k, u64* st, u64* keys) {
-    const bool all = st[CP_TOTAL] <= k;  // every group
-    u64 limit[CP_KEY_WORDS];
-#pragma unroll
-    for (u32 q = 0; q < CP_KEY_WORDS; q++) limit[q] = all ? ~0ULL : st[CP_PREFIX + q];
-    for (u32 t = 0; t < CP_TILES; t++) {
-        const u32 b = blockIdx.x * CP_TILES + t;
-        if (b >= nblocks || counts[b] == 0) continue;
-        const u64 slot = (u64)b * QUERY_THREADS + threadIdx.x;
-        u64 K[CP_KEY_WORDS];
-        if (!tb_cp_key(N, table, slot, mask, order, K)) continue;
-        bool above = false, decided = false;
-#pragma unroll
-        for (u32 q = 0; q < CP_KEY_WORDS; q++) {
-            if (!decided && K[q] != limit[q]) above = K[q] > limit[q], decided = true;
-        }
-        if (above) continue;
-        const u64 i = atomicAdd((unsigned long long*)&st[CP_NKEYS], 1ULL);
-        if (i < k) {
-            u64* dst = keys + i * CP_KEY_STRIDE;
-#pragma unroll
-            for (u32 q = 0; q < CP_KEY_WORDS; q++) dst[q] = K[q];
-            dst[CP_KEY_WORDS] = slot;
-        }
-    }
-}
-
-// Rank by counting over the collected keys (at most k), tb_qa_emit's form: CP_EMIT_LANES lanes share a
-// key, each comparing it with its share of a staged tile; a tile's tail is padded with all-ones keys,
-// which rank before no key.  out[rank] = the row: the id its tag's record holds, then the slot's sums.
-#define CP_EMIT_LANES 16
-#define CP_EMIT_KEYS (QUERY_THREADS / CP_EMIT_LANES)
+// out[rank] = the row: the id its tag's record holds, then the slot's sums.
 __global__ __launch_bounds__(QUERY_THREADS) void tb_cp_emit(NodeTablesArgs N, const u64* table, u32 mask, u32 k, const u64* st,
                                                             const u64* keys, u8* out) {
-    __shared__ u64 s_key[QUERY_THREADS][CP_KEY_WORDS];
-    const u32 n = (u32)min((u64)k, st[CP_NKEYS]);
-    if (blockIdx.x * CP_EMIT_KEYS >= n) return;
-    const u32 sub = threadIdx.x % CP_EMIT_LANES, i = blockIdx.x * CP_EMIT_KEYS + threadIdx.x / CP_EMIT_LANES;
-    u64 mine[CP_KEY_WORDS];
-#pragma unroll
-    for (u32 q = 0; q < CP_KEY_WORDS; q++) mine[q] = i < n ? keys[(u64)i * CP_KEY_STRIDE + q] : ~0ULL;
-    u32 rank = 0;
-    for (u32 t0 = 0; t0 < n; t0 += QUERY_THREADS) {
-        const u32 j = t0 + threadIdx.x;
-#pragma unroll
-        for (u32 q = 0; q < CP_KEY_WORDS; q++) s_key[threadIdx.x][q] = j < n ? keys[(u64)j * CP_KEY_STRIDE + q] : ~0ULL;
-        __syncthreads();
-        for (u32 s = 0; s < QUERY_THREADS / CP_EMIT_LANES; s++) {
-            const u64* o = s_key[s * CP_EMIT_LANES + sub];
-            bool below = false, decided = false;
-#pragma unroll
-            for (u32 q = 0; q < CP_KEY_WORDS; q++) {
-                if (!decided && o[q] != mine[q]) below = o[q] < mine[q], decided = true;
-            }
-            rank += below;
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (u32 off = CP_EMIT_LANES / 2; off > 0; off >>= 1) rank += __shfl_xor(rank, off);
-    if (sub != 0 || i >= n || rank >= k) return;
-    const u64 slot = keys[(u64)i * CP_KEY_STRIDE + CP_KEY_WORDS];
-    if (slot > mask) return;
+    const u32 n = (u32)min((u64)k, st[SEL_NKEYS]);
+    if (blockIdx.x * SEL_EMIT_KEYS >= n) return;
+    u64 mine[CP_KEY_STRIDE];
+    const u32 rank = tb_select_rank<CP_KEY_WORDS>(keys, n, mine);
+    const u64 slot = mine[CP_KEY_WORDS];
+    if (threadIdx.x % SEL_EMIT_LANES != 0 || slot > mask || rank >= k) return;
     const u64* e = table + slot * CP_SLOT_WORDS;
     u64 lo, hi;
     if (!tb_cp_tag_id(N, e[0], lo, hi)) return;

@@ -10,48 +10,33 @@
 //                  window; the 32-B cold entry is read only under a user_data_* filter, by slots that
 //                  passed the hot tests;
 //   tb_qa_scan     one workgroup: the total M and the matches' global minimum and maximum;
-//   tb_qa_hist /   M > k only: a most-significant-digit radix select of the k-th smallest value of
-//   tb_qa_pick     v = timestamp - min (v = max - timestamp under REVERSED, so "smallest" is always
-//                  the wanted end), QA_BITS bits a pass.  A pass histograms the digit of the matches
-//                  that carry the prefix chosen so far (LDS per workgroup, non-returning global atomics
-//                  to merge) and one workgroup picks the digit.  The passes are enqueued back to back;
-//                  a pass whose digit the span max - min already decides (it is zero), or any pass
-//                  when M <= k, exits on what it reads from device memory;
-//   tb_qa_collect  the matches with v <= the selected value append {v, slot} to a k-entry key buffer
-//                  through one counter.  Account timestamps are unique, so exactly k qualify; the
-//                  store is guarded by index < k all the same;
-//   tb_qa_emit     rank by counting: sixteen lanes to a key, the keys staged through LDS a tile at a
-//                  time; out[rank] = the whole account at that slot, with its current balances.
+//   the select     M > k only: k_select.h's, over the one-word key v = timestamp - min (v = max -
+//                  timestamp under REVERSED, so "smallest" is always the wanted end).  tb_qa_scan starts
+//                  it: the prefix zero, and `varies` the span max - min with every bit below its top bit
+//                  set, so the passes that run are those whose digit the span reaches;
+//   tb_qa_emit     tb_select_rank by {v, slot}; out[rank] = the whole account at that slot, with its
+//                  current balances.
 // Every scan kernel skips a tile whose count is zero.  Plain launches: no grid barrier, no spin, no
 // wait on another workgroup; every loop is bounded by the grid, by k or by a constant.
 #pragma once
 
-#include "k_query.h"
+#include "k_select.h"
 
-#define QA_BITS 11
-#define QA_BINS (1u << QA_BITS)
-#define QA_PASSES 6  // 6 x 11 bits cover a 64-bit span
-#define QA_TILES 4   // tiles one workgroup of tb_qa_hist / tb_qa_collect covers
+#define QA_PASSES SEL_WORD_PASSES  // the key is one word
 
-// Device state of one query, u64 words.
+// Device state of one query, u64 words: the select's, with the matches' bounds beside them.
 enum : u32 {
-    QA_TOTAL = 0,   // M: the matches
-    QA_MIN = 1,     // their smallest timestamp
-    QA_MAX = 2,     // ... and largest
-    QA_PREFIX = 3,  // the digits of the selected value chosen so far
-    QA_RANK = 4,    // the selected value is the QA_RANK-th smallest (from 1) among the matches with the prefix
-    QA_SCANS = 5,   // select passes that ran (each one table scan)
-    QA_NKEYS = 6,   // tb_qa_collect's counter
-    QA_WORDS = 8,
+    QA_MIN = SEL_CALLER,      // the matches' smallest timestamp
+    QA_MAX = SEL_CALLER + 1,  // ... and largest
+    QA_WORDS = SEL_WORDS,
 };
+#define QA_STATE_BYTES SEL_STATE_BYTES(QA_WORDS, QA_PASSES)
 
 struct QaPred {
     QueryFieldFilter f;
     u32 world, self;  // a node shard answers for the accounts it owns (world 0: no owner test)
     u32 cold;         // a user_data_* field is filtered
 };
-
-__device__ static inline u32 qa_shift(u32 pass) { return QA_BITS * (QA_PASSES - 1 - pass); }
 
 // The matching slot's timestamp, or 0.
 __device__ static inline u64 tb_qa_hit(const Tables& T, const QaPred& P, u64 slot, u64 cap) {
@@ -138,124 +123,36 @@ __global__ __launch_bounds__(1024) void tb_qa_scan(const u32* counts, const u64*
             lo = min(lo, s_min[w]);
             hi = max(hi, s_max[w]);
         }
-        st[QA_TOTAL] = c;
+        const u64 span = c ? hi - lo : 0;
+        st[SEL_TOTAL] = c;
         st[QA_MIN] = c ? lo : 0;
         st[QA_MAX] = hi;
-        st[QA_PREFIX] = 0;
-        st[QA_RANK] = k;
-        st[QA_SCANS] = 0;
-        st[QA_NKEYS] = 0;
+        st[SEL_PREFIX] = 0;
+        st[SEL_RANK] = k;
+        st[SEL_VARIES] = span ? ~0ULL >> __clzll(span) : 0;
     }
 }
 
-// Whether select pass `pass` has a digit to decide: more matches than wanted, and a span that
-// reaches the digit.  The same for every thread of every workgroup of the pass.
-__device__ static inline bool qa_pass_runs(const u64* st, u32 k, u32 pass) {
-    return st[QA_TOTAL] > k && ((st[QA_MAX] - st[QA_MIN]) >> qa_shift(pass)) != 0;
-}
-
-__device__ static inline u64 qa_value(const u64* st, u32 reversed, u64 ts) {
-    return reversed ? st[QA_MAX] - ts : ts - st[QA_MIN];
-}
-
-// Whether v carries the digits chosen before `pass`.
-__device__ static inline bool qa_has_prefix(u64 v, u64 prefix, u32 pass) {
-    const u32 above = qa_shift(pass) + QA_BITS;
-    return above >= 64 || (v >> above) == (prefix >> above);
-}
-
-__global__ __launch_bounds__(QUERY_THREADS) void tb_qa_hist(Tables T, QaPred P, u64 cap, const u32* counts, u64 nblocks, u32 k,
-                                                            u32 reversed, u32 pass, const u64* st, u32* hist) {
-    __shared__ u32 s_hist[QA_BINS];
-    if (!qa_pass_runs(st, k, pass)) return;
-    for (u32 i = threadIdx.x; i < QA_BINS; i += QUERY_THREADS) s_hist[i] = 0;
-    __syncthreads();
-    const u64 prefix = st[QA_PREFIX];
-    const u32 shift = qa_shift(pass);
-    bool any = false;
-    for (u32 t = 0; t < QA_TILES; t++) {
-        const u64 b = (u64)blockIdx.x * QA_TILES + t;
-        if (b >= nblocks || counts[b] == 0) continue;  // the whole workgroup alike
-        any = true;
-        const u64 ts = tb_qa_hit(T, P, b * QUERY_THREADS + threadIdx.x, cap);
-        if (ts == 0) continue;
-        const u64 v = qa_value(st, reversed, ts);
-        if (qa_has_prefix(v, prefix, pass)) atomicAdd(&s_hist[(v >> shift) & (QA_BINS - 1)], 1u);
-    }
-    if (!any) return;
-    __syncthreads();
-    u32* out = hist + (u64)pass * QA_BINS;
-    for (u32 i = threadIdx.x; i < QA_BINS; i += QUERY_THREADS) {
-        const u32 c = s_hist[i];
-        if (c) __hip_atomic_fetch_add(&out[i], c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
-// One workgroup: the digit under which the QA_RANK-th smallest value falls.
-__global__ __launch_bounds__(1024) void tb_qa_pick(u32 k, u32 pass, const u32* hist, u64* st) {
-    __shared__ u32 s_wave[1024 / 64];
-    static_assert(QA_BINS == 2 * 1024, "two bins a thread");
-    if (!qa_pass_runs(st, k, pass)) return;
-    const u32* h = hist + (u64)pass * QA_BINS;
-    const u32 c0 = h[2 * threadIdx.x], c1 = h[2 * threadIdx.x + 1];
-    u32 all;
-    const u64 before = tb_block_excl_sum(c0 + c1, s_wave, &all);
-    const u64 rank = st[QA_RANK], prefix = st[QA_PREFIX];
-    __syncthreads();  // every thread has read the state before one rewrites it
-    if (rank > before && rank <= before + c0 + c1) {
-        const bool second = rank > before + c0;
-        st[QA_PREFIX] = prefix | ((u64)(2 * threadIdx.x + second) << qa_shift(pass));
-        st[QA_RANK] = rank - before - (second ? c0 : 0);
-        st[QA_SCANS] += 1;
-    }
-}
-
-__global__ __launch_bounds__(QUERY_THREADS) void tb_qa_collect(Tables T, QaPred P, u64 cap, const u32* counts, u64 nblocks,
-                                                               u32 k, u32 reversed, u64* st, u64* keys) {
-    const u64 limit = st[QA_TOTAL] > k ? st[QA_PREFIX] : ~0ULL;  // the selected value; M <= k: every match
-    for (u32 t = 0; t < QA_TILES; t++) {
-        const u64 b = (u64)blockIdx.x * QA_TILES + t;
-        if (b >= nblocks || counts[b] == 0) continue;
-        const u64 slot = b * QUERY_THREADS + threadIdx.x;
+// The select's key source: v of the matching slot.  st: the query's state, for the bounds.
+struct QaSource {
+    static constexpr u32 WORDS = 1;
+    Tables T;
+    QaPred P;
+    u64 cap;
+    u32 reversed;
+    const u64* st;
+    __device__ bool key(u64 slot, u64 (&K)[WORDS]) const {
         const u64 ts = tb_qa_hit(T, P, slot, cap);
-        if (ts == 0) continue;
-        const u64 v = qa_value(st, reversed, ts);
-        if (v > limit) continue;
-        const u64 i = atomicAdd((unsigned long long*)&st[QA_NKEYS], 1ULL);
-        if (i < k) {
-            keys[2 * i] = v;
-            keys[2 * i + 1] = slot;
-        }
+        if (ts == 0) return false;  // before the bounds are read: the collect re-reads them after every atomic
+        K[0] = reversed ? st[QA_MAX] - ts : ts - st[QA_MIN];
+        return true;
     }
-}
+};
 
-// Rank by counting over the collected keys (at most k): key i goes to out[its rank by {v, slot}].
-// QA_EMIT_LANES lanes share a key, each comparing it with its share of a staged tile (one serial loop
-// over 8190 keys a lane took most of the query's time); their counts meet by shuffles.  A tile's tail
-// is padded with {~0, ~0}, which ranks before no key.
-#define QA_EMIT_LANES 16
-#define QA_EMIT_KEYS (QUERY_THREADS / QA_EMIT_LANES)
 __global__ __launch_bounds__(QUERY_THREADS) void tb_qa_emit(Tables T, u64 cap, u32 k, const u64* st, const u64* keys, u8* out) {
-    __shared__ __attribute__((aligned(16))) ulonglong2 s_key[QUERY_THREADS];
-    const u32 n = (u32)min((u64)k, st[QA_NKEYS]);
-    if (blockIdx.x * QA_EMIT_KEYS >= n) return;
-    const ulonglong2* key = (const ulonglong2*)keys;
-    const u32 sub = threadIdx.x % QA_EMIT_LANES, i = blockIdx.x * QA_EMIT_KEYS + threadIdx.x / QA_EMIT_LANES;
-    const ulonglong2 pad{~0ULL, ~0ULL};
-    const ulonglong2 mine = i < n ? key[i] : pad;
-    u32 rank = 0;
-    for (u32 t0 = 0; t0 < n; t0 += QUERY_THREADS) {
-        const u32 j = t0 + threadIdx.x;
-        s_key[threadIdx.x] = j < n ? key[j] : pad;
-        __syncthreads();
-#pragma unroll
-        for (u32 s = 0; s < QUERY_THREADS / QA_EMIT_LANES; s++) {
-            const ulonglong2 o = s_key[s * QA_EMIT_LANES + sub];
-            rank += o.x < mine.x || (o.x == mine.x && o.y < mine.y);
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (u32 off = QA_EMIT_LANES / 2; off > 0; off >>= 1) rank += __shfl_xor(rank, off);
-    if (sub == 0 && i < n && rank < k && mine.y < cap) *(Account*)(out + (u64)rank * 128) = tb_account_load(T, (u32)mine.y);
+    const u32 n = (u32)min((u64)k, st[SEL_NKEYS]);
+    if (blockIdx.x * SEL_EMIT_KEYS >= n) return;
+    u64 mine[2];  // {v, slot}
+    const u32 rank = tb_select_rank<1>(keys, n, mine);
+    if (threadIdx.x % SEL_EMIT_LANES == 0 && mine[1] < cap && rank < k) *(Account*)(out + (u64)rank * 128) = tb_account_load(T, (u32)mine[1]);
 }

@@ -60,14 +60,13 @@ struct AccountQueryBufs {
     u32* d_counts = nullptr;  // [nb] matches per tile
     u64* d_mins = nullptr;    // [nb] their smallest timestamp
     u64* d_maxs = nullptr;    // [nb] ... and largest
-    u64* d_state = nullptr;   // [QA_WORDS], then the select's histograms: u32 [QA_PASSES][QA_BINS]
+    u64* d_state = nullptr;   // [QA_WORDS], then the select's histograms: u32 [QA_PASSES][SEL_BINS]
     u64* h_state = nullptr;   // pinned mirror of the QA_WORDS
     u64* d_keys = nullptr;    // [BATCH_EVENTS_MAX][2] {value, slot} of the selected matches
     u8* d_out = nullptr;      // [BATCH_EVENTS_MAX] the answer's records
     u32 k = 0;                // one query in flight between account_query_enqueue and _collect
     u64 last_scans = 0;       // select passes of the last query (tbgpu_bench_query_select_scans)
 };
-#define QA_STATE_BYTES ((u64)QA_WORDS * 8 + (u64)QA_PASSES * QA_BINS * 4)
 
 // tbgpu_get_change_events (k_change_events.h): the page's account set, the bins, the accounts' records
 // and the post rows' pending amounts, on the device and pinned; made by query_init and shared with
@@ -205,7 +204,7 @@ struct CounterpartyBufs {
     u64 slots = 0;            // a power of two, at least 2 * groups
     u64* d_table = nullptr;   // [slots][CP_SLOT_WORDS]
     u32* d_counts = nullptr;  // [slots / QUERY_THREADS, rounded up] occupied slots per tile
-    u64* d_state = nullptr;   // [CP_WORDS], then the select's histograms: u32 [CP_PASSES_MAX][CP_BINS]
+    u64* d_state = nullptr;   // [CP_WORDS], then the select's histograms: u32 [CP_PASSES_MAX][SEL_BINS]
     u64* h_state = nullptr;   // pinned mirror of the CP_WORDS
     u64* d_keys = nullptr;    // [CP_ROWS_MAX][CP_KEY_STRIDE] the selected groups' keys and slots
     u8* d_out = nullptr;      // [CP_ROWS_MAX] the answer's rows
@@ -991,6 +990,25 @@ extern "C" int tbgpu_query_transfers(tbgpu_t* E, const tbgpu_query_filter* filte
     return query_end(result, query_log_rows(c, query_fields_of(filter), reversed, (u8*)out, result));
 }
 
+// k_select.h's passes and its collect on `stream`, back to back, over source S's nb tiles (a pass with
+// nothing to decide exits on the device).  st: the state the caller started; hist: `passes` zeroed histograms.
+template <typename SRC>
+static void select_enqueue(hipStream_t stream, const SRC& S, u64 nb, u32 k, u32 passes, u64* st, u32* hist, const u32* counts, u64* keys) {
+    const unsigned wide = (unsigned)((nb + SEL_TILES - 1) / SEL_TILES);
+    for (u32 pass = 0; pass < passes; pass++) {
+        hipLaunchKernelGGL(tb_select_hist<SRC>, dim3(wide), dim3(QUERY_THREADS), 0, stream, S, counts, nb, k, pass, (const u64*)st, hist);
+        hipLaunchKernelGGL(tb_select_pick, dim3(1), dim3(1024), 0, stream, k, pass, (const u32*)hist, st);
+    }
+    hipLaunchKernelGGL(tb_select_collect<SRC>, dim3(wide), dim3(QUERY_THREADS), 0, stream, S, counts, nb, k, st, keys);
+}
+
+// The select's state words, back on the host: it collected the m = min(k, total) entries asked for.
+static int select_check(const char* name, const char* what, const u64* h_state, u32 k, u32 m) {
+    if (std::min<u64>(k, h_state[SEL_NKEYS]) == m) return TBGPU_STATUS_OK;
+    return fail(TBGPU_STATUS_PANIC, "%s: %llu keys selected for %u of %llu %s", name, (unsigned long long)h_state[SEL_NKEYS], m,
+                (unsigned long long)h_state[SEL_TOTAL], what);
+}
+
 // The account table in two halves, as the log scan: account_query_enqueue puts count -> scan -> the
 // select's passes -> collect -> emit on the engine stream, back to back (a pass that has nothing to
 // decide exits on the device); account_query_collect waits for the state words, then copies the
@@ -1009,22 +1027,16 @@ static int account_query_enqueue(tbgpu* E, const QueryFieldFilter& F, u32 world,
     P.self = self;
     P.cold = F.wants_u128() || F.u64v || F.u32v;
     const u64 cap = E->account_cap, nb = A.nb;
-    const u32 rev = reversed ? 1u : 0u;
-    const unsigned wide = (unsigned)((nb + QA_TILES - 1) / QA_TILES);
-    u32* hist = (u32*)(A.d_state + QA_WORDS);
     HIPCK(hipMemsetAsync(A.d_state, 0, QA_STATE_BYTES, E->stream));
     hipLaunchKernelGGL(tb_qa_count, dim3((unsigned)nb), dim3(QUERY_THREADS), 0, E->stream, E->T, P, cap, A.d_counts, A.d_mins,
                        A.d_maxs);
     hipLaunchKernelGGL(tb_qa_scan, dim3(1), dim3(1024), 0, E->stream, A.d_counts, A.d_mins, A.d_maxs, nb, k, A.d_state);
-    for (u32 pass = 0; pass < QA_PASSES; pass++) {
-        hipLaunchKernelGGL(tb_qa_hist, dim3(wide), dim3(QUERY_THREADS), 0, E->stream, E->T, P, cap, A.d_counts, nb, k, rev, pass,
-                           A.d_state, hist);
-        hipLaunchKernelGGL(tb_qa_pick, dim3(1), dim3(1024), 0, E->stream, k, pass, hist, A.d_state);
+    if (k) {
+        select_enqueue(E->stream, QaSource{E->T, P, cap, reversed ? 1u : 0u, A.d_state}, nb, k, QA_PASSES, A.d_state,
+                       (u32*)(A.d_state + QA_WORDS), A.d_counts, A.d_keys);
+        hipLaunchKernelGGL(tb_qa_emit, dim3((k + SEL_EMIT_KEYS - 1) / SEL_EMIT_KEYS), dim3(QUERY_THREADS), 0, E->stream, E->T, cap, k,
+                           A.d_state, A.d_keys, A.d_out);
     }
-    hipLaunchKernelGGL(tb_qa_collect, dim3(wide), dim3(QUERY_THREADS), 0, E->stream, E->T, P, cap, A.d_counts, nb, k, rev,
-                       A.d_state, A.d_keys);
-    hipLaunchKernelGGL(tb_qa_emit, dim3(std::max<u32>(1, (k + QA_EMIT_KEYS - 1) / QA_EMIT_KEYS)), dim3(QUERY_THREADS), 0,
-                       E->stream, E->T, cap, k, A.d_state, A.d_keys, A.d_out);
     HIPCK(hipGetLastError());
     HIPCK(hipMemcpyAsync(A.h_state, A.d_state, (u64)QA_WORDS * 8, hipMemcpyDeviceToHost, E->stream));
     return TBGPU_STATUS_OK;
@@ -1036,15 +1048,12 @@ static int account_query_collect(tbgpu* E, u8* out, u32* count, u64* matched) {
     *matched = 0;
     HIPCK(hipSetDevice(E->device));
     HIPCK(hipStreamSynchronize(E->stream));
-    const u64 total = A.h_state[QA_TOTAL];
+    const u64 total = A.h_state[SEL_TOTAL];
     const u32 m = (u32)std::min<u64>(A.k, total);
-    A.last_scans = A.h_state[QA_SCANS];
+    A.last_scans = A.h_state[SEL_SCANS];
     *matched = total;
     if (m == 0) return TBGPU_STATUS_OK;
-    if (std::min<u64>(A.k, A.h_state[QA_NKEYS]) != m) {
-        return fail(TBGPU_STATUS_PANIC, "query_accounts: %llu keys selected for %u of %llu matches",
-                    (unsigned long long)A.h_state[QA_NKEYS], m, (unsigned long long)total);
-    }
+    if (const int st = select_check("query_accounts", "matches", A.h_state, A.k, m)) return st;
     HIPCK(hipMemcpyAsync(out, A.d_out, (u64)m * 128, hipMemcpyDeviceToHost, E->stream));
     HIPCK(hipStreamSynchronize(E->stream));
     *count = m;
@@ -1817,25 +1826,18 @@ static int counterparty_enqueue_select(const QueryCall& c, const NodeTablesArgs&
     CounterpartyBufs& K = E->qs->qk;
     HIPCK(hipSetDevice(E->device));
     const u32 mask = (u32)(K.slots - 1), k = c.k;
-    const unsigned nb = (unsigned)((K.slots + QUERY_THREADS - 1) / QUERY_THREADS), wide = (nb + CP_TILES - 1) / CP_TILES;
+    const unsigned nb = (unsigned)((K.slots + QUERY_THREADS - 1) / QUERY_THREADS);
     for (u32 d = 1; d < c.world; d++) {
         hipLaunchKernelGGL(tb_cp_merge, dim3(nb), dim3(QUERY_THREADS), 0, E->stream, NT, (const u64*)c.Es[d]->qs->qk.d_table, K.d_table,
                            mask, K.d_state);
     }
-    u32* hist = (u32*)(K.d_state + CP_WORDS);
     hipLaunchKernelGGL(tb_cp_count, dim3(nb), dim3(QUERY_THREADS), 0, E->stream, NT, (const u64*)K.d_table, mask, order, K.d_counts,
                        K.d_state);
     if (k) {
         hipLaunchKernelGGL(tb_cp_begin, dim3(1), dim3(64), 0, E->stream, k, K.d_state);
-        const u32 passes = tb_cp_order_words(order) * CP_WORD_PASSES;  // by id the key is two words
-        for (u32 pass = 0; pass < passes; pass++) {
-            hipLaunchKernelGGL(tb_cp_hist, dim3(wide), dim3(QUERY_THREADS), 0, E->stream, NT, (const u64*)K.d_table, mask, order,
-                               (const u32*)K.d_counts, nb, k, pass, (const u64*)K.d_state, hist);
-            hipLaunchKernelGGL(tb_cp_pick, dim3(1), dim3(1024), 0, E->stream, k, pass, (const u32*)hist, K.d_state);
-        }
-        hipLaunchKernelGGL(tb_cp_collect, dim3(wide), dim3(QUERY_THREADS), 0, E->stream, NT, (const u64*)K.d_table, mask, order,
-                           (const u32*)K.d_counts, nb, k, K.d_state, K.d_keys);
-        hipLaunchKernelGGL(tb_cp_emit, dim3((k + CP_EMIT_KEYS - 1) / CP_EMIT_KEYS), dim3(QUERY_THREADS), 0, E->stream, NT,
+        select_enqueue(E->stream, CpSource{NT, K.d_table, mask, order}, nb, k, tb_cp_order_words(order) * SEL_WORD_PASSES, K.d_state,
+                       (u32*)(K.d_state + CP_WORDS), K.d_counts, K.d_keys);
+        hipLaunchKernelGGL(tb_cp_emit, dim3((k + SEL_EMIT_KEYS - 1) / SEL_EMIT_KEYS), dim3(QUERY_THREADS), 0, E->stream, NT,
                            (const u64*)K.d_table, mask, k, (const u64*)K.d_state, (const u64*)K.d_keys, K.d_out);
     }
     HIPCK(hipGetLastError());
@@ -1882,13 +1884,10 @@ static int counterparty_answer(QueryCall& c, NodeTablesArgs& NT, u32 order, cons
                                       "group table holds (capacity: %llu groups, %llu slots)",
                                       name, what, (unsigned long long)K.groups, (unsigned long long)K.slots));
     }
-    const u64 matched = K.h_state[CP_TOTAL];
+    const u64 matched = K.h_state[SEL_TOTAL];
     const u32 m = (u32)std::min<u64>(c.k, matched);
-    if (m && std::min<u64>(c.k, K.h_state[CP_NKEYS]) != m) {
-        return query_end(result, fail(TBGPU_STATUS_PANIC, "%s: %llu keys selected for %u of %llu groups", name,
-                                      (unsigned long long)K.h_state[CP_NKEYS], m, (unsigned long long)matched));
-    }
     if (m) {
+        if (const int s = select_check(name, "groups", K.h_state, c.k, m)) return query_end(result, s);
         HIPCK(hipSetDevice(E0->device));
         HIPCK(hipMemcpyAsync(out, K.d_out, (u64)m * CP_ROW_BYTES, hipMemcpyDeviceToHost, E0->stream));
         HIPCK(hipStreamSynchronize(E0->stream));
