@@ -31,6 +31,7 @@
  *   (no reference: who paid whom over a period)            tbgpu_get_account_flow_matrix (likewise)
  *   (no reference: who an account dealt with)              tbgpu_get_account_counterparties (likewise)
  *   (no reference: the accounts a period's records name)   tbgpu_get_active_accounts (likewise)
+ *   (no reference: a balance's low and high over a period) tbgpu_get_account_balance_extremes (likewise)
  *   `setup` action of the table tests (:1398-1407)         tbgpu_test_set_balances (test only)
  *   StateMachine.commit_timestamp field (:251)             tbgpu_commit_timestamp
  *
@@ -825,6 +826,82 @@ typedef struct tbgpu_account_balance_integral {   /* 256 bytes, little-endian, n
 int tbgpu_get_account_balance_integrals(tbgpu_t* engine, uint64_t t_open, uint64_t t_close,
                                         const void* ids /* n x {lo, hi} */, uint32_t n,
                                         void* out, uint32_t out_cap_rows, tbgpu_query_result* result);
+
+/* get_account_balance_extremes: for each account the caller names, over a period the caller names,
+ * the lowest and the highest value a balance reached, and when — what overdraft detection, a
+ * minimum-balance fee, the peak exposure on holds and margin or limit monitoring start from.  Every
+ * other query here is a sum over the log in any order; a running balance's extremes depend on the order
+ * of the records.  No reference has an operation for it, and paging tbgpu_get_account_balances per
+ * account to take the minimum on the host is one or two log scans per account per page of 8,190 rows;
+ * this call answers every id in one walk of the log in HBM and stores nothing at commit.  An entry
+ * point of its own, as above; this comment is its specification.
+ *   The value.  `measure` picks what is watched, a coefficient of -1, 0 or +1 per balance column:
+ *         v(a, t) = the sum over the four columns k of measure.k * balance_at(a, t).k
+ *     taken as a signed integer, where balance_at is tbgpu_lookup_accounts_at's formula word for word —
+ *     its anchor at the current balance, its effect table, the P rule, the orphan rule and the liveness
+ *     rule — and each column is an unsigned 128-bit value.  The TBGPU_MEASURE_* macros name the usual
+ *     ones: the net posted balance of a credit-normal account {0, -1, 0, +1}, its available balance
+ *     {-1, -1, 0, +1}, the same two for a debit-normal account, and each single column.
+ *   The period is (t_open, t_end], as tbgpu_get_account_balance_integrals' is: t_open == 0 is read
+ *     literally; t_close == 0 means t_end = tbgpu_commit_timestamp (a node: the node's own), read once
+ *     at the call; otherwise t_end = t_close.  The row carries the period as used.
+ *   Which rows, request order, repeated, absent and reserved ids, an account created after t_end,
+ *     matched, count and complete: tbgpu_get_account_balance_integrals' rules, with 192-byte rows.
+ *   opening = v(a, t_open), closing = v(a, t_end).
+ *   low, high.  Let r_1 .. r_m be the live resident records that name the account with t_open <
+ *     timestamp <= t_end, by timestamp, v_0 = opening and v_i = v(a, timestamp(r_i)).  low is the least
+ *     v_i and t_low the timestamp of the first i that reaches it, t_open for i = 0; high and t_high
+ *     likewise with the greatest.  records = m.  With m = 0, low = high = opening = closing and t_low =
+ *     t_high = t_open.  A post is one step: the release of its hold and its posting land together, so
+ *     a measure that adds a pending and a posted column does not dip between them.
+ *   The values are exact signed integers in 192 bits, two's complement, low word first.  One record's
+ *     step is below 2^130 in magnitude and a log holds fewer than 2^32 records, so no value the
+ *     definition walks through can wrap 192 bits.  They are computed from the records' steps: equal to
+ *     the definition wherever no balance_at column in the period falls below zero — which only a
+ *     tbgpu_test_set_balances or tbgpu_load_accounts step that set a balance below what the later
+ *     records release can cause; such a column counts as that negative number, as the integrals do.
+ *   A coefficient outside {-1, 0, +1}, a measure that is all zero, a non-zero reserved byte, a NULL
+ *     measure, ids, out or result with n > 0, or n > TBGPU_EXTREMES_MAX is TBGPU_STATUS_INVALID and
+ *     writes nothing.  t_open or t_close equal to 2^64-1, or t_end below t_open, returns
+ *     TBGPU_STATUS_OK with count = matched = 0.  n == 0 returns TBGPU_STATUS_OK and writes nothing.
+ *     After any failing status the result names no row.
+ *   The call contract of tbgpu_get_account_statements: synchronous, drains a pending
+ *     tbgpu_commit_device_async first, a read that changes nothing, works on an engine a device panic
+ *     stopped, allocates nothing on the device after tbgpu_init, legal beside an asynchronous write-back.
+ *   Cost.  One engine whose log lies in timestamp order (every log that commits built) is answered by
+ *     one ordered walk of the log, a few times the cost of tbgpu_get_account_statements.  A node
+ *     engine, whose shards interleave in time, and an engine whose log tbgpu_load_transfers filled out
+ *     of timestamp order are answered exactly, with the same bytes, but slowly: per found account the
+ *     balance history of the period is paged internally (tbgpu_get_account_balances' scans, 8,190 rows
+ *     a page) and reduced on the host — a log scan or two per account per page.  Keep n small there. */
+#define TBGPU_EXTREMES_MAX 4095u
+typedef struct tbgpu_balance_measure {   /* 8 bytes */
+    int8_t  debits_pending, debits_posted, credits_pending, credits_posted;  /* each -1, 0 or +1 */
+    uint8_t reserved[4];                                                     /* zero */
+} tbgpu_balance_measure;
+/* {debits_pending, debits_posted, credits_pending, credits_posted} */
+#define TBGPU_MEASURE_CREDIT_NET_POSTED   { 0, -1,  0, +1, {0, 0, 0, 0}}  /* credits_posted - debits_posted */
+#define TBGPU_MEASURE_CREDIT_AVAILABLE    {-1, -1,  0, +1, {0, 0, 0, 0}}  /* ... less the held debits */
+#define TBGPU_MEASURE_DEBIT_NET_POSTED    { 0, +1,  0, -1, {0, 0, 0, 0}}  /* debits_posted - credits_posted */
+#define TBGPU_MEASURE_DEBIT_AVAILABLE     { 0, +1, -1, -1, {0, 0, 0, 0}}  /* ... less the held credits */
+#define TBGPU_MEASURE_DEBITS_PENDING      {+1,  0,  0,  0, {0, 0, 0, 0}}
+#define TBGPU_MEASURE_DEBITS_POSTED       { 0, +1,  0,  0, {0, 0, 0, 0}}
+#define TBGPU_MEASURE_CREDITS_PENDING     { 0,  0, +1,  0, {0, 0, 0, 0}}
+#define TBGPU_MEASURE_CREDITS_POSTED      { 0,  0,  0, +1, {0, 0, 0, 0}}
+typedef struct tbgpu_account_balance_extreme {   /* 192 bytes, little-endian, no padding */
+    uint64_t id_lo, id_hi;
+    uint64_t opening[3], closing[3];   /* the measure at t_open and at t_end: signed, two's complement, 192 bits, low word first */
+    uint64_t low[3], high[3];          /* its minimum and maximum over [t_open, t_end] */
+    uint64_t t_low, t_high;            /* when each was first reached */
+    uint64_t records;                  /* live resident records of the period that name the account */
+    uint64_t t_open, t_end;            /* the period as used */
+    uint64_t measure;                  /* the request's 8 bytes, echoed */
+    uint64_t reserved[4];              /* zero */
+} tbgpu_account_balance_extreme;
+int tbgpu_get_account_balance_extremes(tbgpu_t* engine, uint64_t t_open, uint64_t t_close,
+                                       const tbgpu_balance_measure* measure,
+                                       const void* ids /* n x {lo, hi} */, uint32_t n,
+                                       void* out, uint32_t out_cap_rows, tbgpu_query_result* result);
 
 /* get_account_statement_series: tbgpu_get_account_statements cut into consecutive periods — for each
  * account the caller names, one statement row per bucket: daily closing balances for a month, monthly

@@ -120,6 +120,24 @@ class tbgpu_account_balance_integral(ctypes.Structure):
 
 
 INTEGRALS_MAX = 4095  # TBGPU_INTEGRALS_MAX
+
+
+class tbgpu_balance_measure(ctypes.Structure):
+    _fields_ = [("debits_pending", ctypes.c_int8), ("debits_posted", ctypes.c_int8),
+                ("credits_pending", ctypes.c_int8), ("credits_posted", ctypes.c_int8),
+                ("reserved", ctypes.c_uint8 * 4)]
+
+
+class tbgpu_account_balance_extreme(ctypes.Structure):
+    _fields_ = [("id_lo", ctypes.c_uint64), ("id_hi", ctypes.c_uint64),
+                ("opening", ctypes.c_uint64 * 3), ("closing", ctypes.c_uint64 * 3),
+                ("low", ctypes.c_uint64 * 3), ("high", ctypes.c_uint64 * 3),
+                ("t_low", ctypes.c_uint64), ("t_high", ctypes.c_uint64), ("records", ctypes.c_uint64),
+                ("t_open", ctypes.c_uint64), ("t_end", ctypes.c_uint64), ("measure", ctypes.c_uint64),
+                ("reserved", ctypes.c_uint64 * 4)]
+
+
+EXTREMES_MAX = 4095  # TBGPU_EXTREMES_MAX
 SERIES_ROWS_MAX = 4095  # TBGPU_SERIES_ROWS_MAX
 
 
@@ -298,6 +316,7 @@ SIGNATURES = [
     ("tbgpu_get_pending_transfers", ctypes.c_int, [_P, _P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_get_account_statements", ctypes.c_int, [_P, _U64, _U64, _P, _U32, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_get_account_balance_integrals", ctypes.c_int, [_P, _U64, _U64, _P, _U32, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
+    ("tbgpu_get_account_balance_extremes", ctypes.c_int, [_P, _U64, _U64, _P, _P, _U32, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_get_account_statement_series", ctypes.c_int, [_P, _P, _U32, _P, _U32, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_get_account_flow_matrix", ctypes.c_int, [_P, _U64, _U64, _P, _U32, _P, _U32, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),
     ("tbgpu_get_account_counterparties", ctypes.c_int, [_P, _P, _P, _U32, ctypes.POINTER(tbgpu_query_result)]),

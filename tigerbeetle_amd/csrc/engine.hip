@@ -40,6 +40,7 @@
 #include "k_asof.h"
 #include "k_statement.h"
 #include "k_integral.h"
+#include "k_extremes.h"
 #include "k_series.h"
 #include "k_matrix.h"
 #include "k_counterparties.h"

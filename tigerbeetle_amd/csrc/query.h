@@ -173,6 +173,25 @@ struct IntegralBufs {
 };
 #define INTEGRAL_BIN_BYTES(n) (((u64)(n) * INTEGRAL_BIN_WORDS + 1) * 8)
 
+// tbgpu_get_account_balance_extremes (k_extremes.h): a statements call's request, set, records, flags,
+// rows and result words (QueryState::qt; its rows are narrower), and its own: the [S][n] element array
+// the slabs fill, the zone 0 sums with the flag words behind them, and the two knobs read at init.
+// The array has room for one slab per CU of the largest part at the largest request, 4,095 ids: 292
+// slabs of 458,640 B in 128 MB — fewer where the log cannot hold that many spans of
+// CHANGE_THREADS * CHANGE_TILES records.  A smaller request gets more, shorter slabs from the same
+// bytes, down to one per span and up to EXTREME_SLABS_MAX.
+struct ExtremeBufs {
+    u64* d_elems = nullptr;  // [slabs][n][EXTREME_ELEM_WORDS]
+    u64 elem_bytes = 0;
+    u64* d_zone0 = nullptr;  // [EXTREME_IDS_MAX][3] the sums of the records above t_end, then EXTREME_FLAG_WORDS
+    u64* h_flags = nullptr;  // pinned: the flag words, back after the emit
+    u32 slabs_cap = 0;       // TBGPU_EXTREMES_SLABS: at most that many slabs (0: no cap) — tests force 1, 2 or many
+    bool exact = false;      // TBGPU_EXTREMES_EXACT=1: the exact path on an ordered single engine too
+};
+#define EXTREME_ELEM_BYTES ((u64)EXTREME_ELEM_WORDS * 8)
+#define EXTREME_ZONE0_BYTES(n) (((u64)(n) * 3 + EXTREME_FLAG_WORDS) * 8)
+#define EXTREME_ARRAY_BYTES (128ull << 20)
+
 // tbgpu_get_account_statement_series (k_series.h): a statements call's request, set, records, flags,
 // rows and result words (QueryState::qt: n * n_buckets rows are at most STATEMENT_IDS_MAX), its own
 // bounds and its own bins, one per key.
@@ -228,6 +247,7 @@ struct QueryState {
     AccountScanBufs qx;
     MatrixBufs qxm;
     CounterpartyBufs qk;
+    ExtremeBufs qe;
 };
 
 // One AccountScanBufs for `ids` request ids: in this order, which tests/test_gpu_alloc.py counts by.
@@ -385,6 +405,16 @@ static int query_init(tbgpu* E) {
         HIPCK(tbHostMalloc(E->own, &K.h_state, (u64)CP_WORDS * 8, hipHostMallocDefault));
         HIPCK(tbMalloc(E->own, &K.d_keys, (u64)CP_ROWS_MAX * CP_KEY_STRIDE * 8));
         HIPCK(tbMalloc(E->own, &K.d_out, (u64)CP_ROWS_MAX * CP_ROW_BYTES));
+    }
+    {  // tbgpu_get_account_balance_extremes: the element array, zone 0 and the flag words; the rest is the statements call's
+        ExtremeBufs& X = E->qs->qe;
+        const u64 per = (u64)CHANGE_THREADS * CHANGE_TILES, spans = std::max<u64>((E->xlog_cap + per - 1) / per, 1);
+        X.elem_bytes = std::min<u64>(EXTREME_ARRAY_BYTES, std::min<u64>(spans, EXTREME_SLABS_MAX) * EXTREME_IDS_MAX * EXTREME_ELEM_BYTES);
+        HIPCK(tbMalloc(E->own, &X.d_elems, X.elem_bytes));
+        HIPCK(tbMalloc(E->own, &X.d_zone0, EXTREME_ZONE0_BYTES(EXTREME_IDS_MAX)));
+        HIPCK(tbHostMalloc(E->own, &X.h_flags, EXTREME_FLAG_WORDS * 8, hipHostMallocDefault));
+        if (const char* v = getenv("TBGPU_EXTREMES_SLABS")) X.slabs_cap = (u32)std::max(atoi(v), 0);
+        if (const char* v = getenv("TBGPU_EXTREMES_EXACT")) X.exact = atoi(v) != 0;
     }
     return TBGPU_STATUS_OK;
 }
@@ -1605,6 +1635,156 @@ extern "C" int tbgpu_get_account_balance_integrals(tbgpu_t* E, uint64_t t_open, 
         memcpy(rows + first * INTEGRAL_ROW_BYTES, row, sizeof row);
         return 1;
     });
+}
+
+// get_account_balance_extremes (k_extremes.h).  One engine: T = t_end, the statements call's buffers,
+// and in place of bins the zone 0 sums and the element array, which the scan's launch cuts into slabs.
+// The exact path below answers a node, an engine whose log turned out not to lie in timestamp order
+// (the walk says so), and any engine under TBGPU_EXTREMES_EXACT=1.
+
+// How the walk is cut: `tiles` tiles of CHANGE_THREADS positions into slabs of whole spans of
+// CHANGE_TILES tiles, as many as the element array holds for n ids, at most EXTREME_SLABS_MAX and
+// `cap` (0: none).  Returns the tiles a slab holds; *slabs: how many there are.
+static u32 extreme_slabs(u64 tiles, u32 n, u64 elem_bytes, u32 cap, u32* slabs) {
+    u64 most = std::min<u64>(elem_bytes / ((u64)n * EXTREME_ELEM_BYTES), EXTREME_SLABS_MAX);
+    if (cap) most = std::min<u64>(most, cap);
+    most = std::max<u64>(most, 1);
+    const u64 spans = (tiles + CHANGE_TILES - 1) / CHANGE_TILES, spans_per = (spans + most - 1) / most;
+    const u64 slab_tiles = std::max<u64>(spans_per, 1) * CHANGE_TILES;
+    *slabs = (u32)((tiles + slab_tiles - 1) / slab_tiles);
+    return (u32)slab_tiles;
+}
+
+// The exact path, from what the other calls answer: which ids yield a row and their closing records
+// (lookup_accounts_at at t_end), the opening records (lookup_accounts_at at t_open; an account created
+// inside the period has no record there, and none before its own timestamp, so it is asked at that),
+// and per found account the balance history of (t_open, t_end] page by page (get_account_balances),
+// folded with the walk's own operator.  A log scan or two per account per page.
+static int extremes_exact(tbgpu* E, u64 t_open, u64 t_end, u64 measure, const void* ids, u32 n, void* out, u32 cap,
+                          tbgpu_query_result* result) {
+    std::vector<u8> closing((u64)n * 128), opening((u64)n * 128), page((u64)BATCH_EVENTS_MAX * 128);
+    tbgpu_query_result rc{}, ro{}, rp{};
+    if (const int st = tbgpu_lookup_accounts_at(E, t_end, ids, n, closing.data(), n, &rc)) return query_end(result, st);
+    if (t_open) {  // (0 would ask for the records as they are now; no account was created at or before 0)
+        if (const int st = tbgpu_lookup_accounts_at(E, t_open, ids, n, opening.data(), n, &ro)) return query_end(result, st);
+    } else {
+        ro.complete = 1;
+    }
+    u32 complete = rc.complete & ro.complete, k = 0, written = 0;
+    for (u32 j = 0; j < rc.count; j++) {
+        if (j >= cap) break;
+        u64 account[16], first[16];
+        memcpy(account, closing.data() + (u64)j * 128, 128);
+        if (t_open && account[15] <= t_open) {
+            if (k >= ro.count) return query_end(result, fail(TBGPU_STATUS_PANIC, "get_account_balance_extremes: an account of t_end is missing at t_open"));
+            memcpy(first, opening.data() + (u64)k++ * 128, 128);
+        } else {
+            tbgpu_query_result r1{};
+            if (const int st = tbgpu_lookup_accounts_at(E, account[15], account, 1, first, 1, &r1)) return query_end(result, st);
+            if (r1.count != 1) return query_end(result, fail(TBGPU_STATUS_PANIC, "get_account_balance_extremes: an account is missing at its own timestamp"));
+            complete &= r1.complete;
+        }
+        if (first[0] != account[0] || first[1] != account[1]) {
+            return query_end(result, fail(TBGPU_STATUS_PANIC, "get_account_balance_extremes: the opening and closing records differ in order"));
+        }
+        const U192 v0 = tb_extreme_measure_of(measure, first + 2);
+        U192 v = v0;
+        ExtremeElem e = tb_extreme_empty();
+        bool unordered = false;
+        tbgpu_account_filter f{};
+        f.account_id_lo = account[0], f.account_id_hi = account[1];
+        f.timestamp_min = t_open + 1, f.timestamp_max = t_end;
+        f.limit = BATCH_EVENTS_MAX, f.flags = TBGPU_FILTER_DEBITS | TBGPU_FILTER_CREDITS;
+        while (f.timestamp_min <= t_end) {
+            if (const int st = tbgpu_get_account_balances(E, &f, page.data(), BATCH_EVENTS_MAX, &rp)) return query_end(result, st);
+            if (rp.count == 0) break;
+            complete &= rp.complete;
+            for (u32 i = 0; i < rp.count; i++) {
+                u64 row[9];
+                memcpy(row, page.data() + (u64)i * 128, sizeof row);
+                const U192 next = tb_extreme_measure_of(measure, row);
+                e = tb_extreme_compose(e, tb_extreme_leaf(tb_sub192(next, v), row[8]), &unordered);
+                v = next;
+            }
+            if (rp.count == rp.matched) break;
+            f.timestamp_min = e.last_ts + 1;
+        }
+        if (unordered) return query_end(result, fail(TBGPU_STATUS_PANIC, "get_account_balance_extremes: a balance history out of timestamp order"));
+        u64 row[EXTREME_ROW_BYTES / 8];
+        tb_extreme_row(account[0], account[1], v0, e, t_open, t_end, measure, row);
+        memcpy((u8*)out + (u64)written++ * EXTREME_ROW_BYTES, row, sizeof row);
+    }
+    result->count = written;
+    result->matched = rc.matched;
+    result->complete = complete;
+    return TBGPU_STATUS_OK;
+}
+
+extern "C" int tbgpu_get_account_balance_extremes(tbgpu_t* E, uint64_t t_open, uint64_t t_close, const tbgpu_balance_measure* measure,
+                                                  const void* ids, uint32_t n, void* out, uint32_t out_cap_rows,
+                                                  tbgpu_query_result* result) {
+    static_assert(sizeof(tbgpu_account_balance_extreme) == EXTREME_ROW_BYTES && sizeof(tbgpu_balance_measure) == 8 &&
+                      EXTREME_IDS_MAX == TBGPU_EXTREMES_MAX && EXTREME_IDS_MAX == STATEMENT_IDS_MAX &&
+                      EXTREME_ROW_BYTES <= STATEMENT_ROW_BYTES && sizeof(ExtremeElem) == EXTREME_ELEM_BYTES &&
+                      EXTREME_ZONE0 == EXTREME_ELEM_WORDS && EXTREME_ZONE0 + 3 == EXTREME_BIN_WORDS,
+                  "k_extremes.h's constants are the header's, and the statements call's buffers fit");
+    static_assert((size_t)CHANGE_LDS_BINS_SLOTS_MAX * 4 + (size_t)EXTREME_LDS_BINS * (EXTREME_BIN_WORDS * 8 + 4) + 2 * EXTREME_WAVES * 4 <= 65536,
+                  "set, bins, tags and hit words stay within 64 KB a workgroup");
+    static_assert(EXTREME_ARRAY_BYTES / (EXTREME_IDS_MAX * EXTREME_ELEM_BYTES) >= 256, "a slab per CU at the largest request");
+    API_ENTER(E, false);
+    if (n > TBGPU_EXTREMES_MAX) return fail(TBGPU_STATUS_INVALID, "get_account_balance_extremes: %u ids (at most %u)", n, TBGPU_EXTREMES_MAX);
+    if (n == 0) return TBGPU_STATUS_OK;
+    if (!measure || !ids || !out || !result) return fail(TBGPU_STATUS_INVALID, "get_account_balance_extremes: NULL measure, ids, out or result");
+    const int8_t coefs[4] = {measure->debits_pending, measure->debits_posted, measure->credits_pending, measure->credits_posted};
+    bool some = false;
+    for (const int8_t c : coefs) {
+        if (c < -1 || c > 1) return fail(TBGPU_STATUS_INVALID, "get_account_balance_extremes: a coefficient of %d (-1, 0 or +1)", (int)c);
+        some |= c != 0;
+    }
+    if (!some) return fail(TBGPU_STATUS_INVALID, "get_account_balance_extremes: a measure of no column");
+    for (const uint8_t b : measure->reserved) {
+        if (b) return fail(TBGPU_STATUS_INVALID, "get_account_balance_extremes: a non-zero reserved byte in the measure");
+    }
+    u64 mword;
+    memcpy(&mword, measure, 8);
+    QueryCall c;
+    NodeTablesArgs NT;
+    if (const int st = account_scan_begin(E, "get_account_balance_extremes", &QueryState::qt, n, TBGPU_EXTREMES_MAX, ids, out, result, &c,
+                                          &NT, [&] { return t_open != ~0ULL && t_close != ~0ULL; })) {
+        return st == SCAN_ANSWERED ? TBGPU_STATUS_OK : st;
+    }
+    const u64 t_end = t_close ? t_close : tbgpu_commit_timestamp(E);  // read once, after the drain
+    if (t_end < t_open || t_end == 0) return TBGPU_STATUS_OK;
+    if (E->node || E->qs->qe.exact) return extremes_exact(E, t_open, t_end, mword, ids, n, out, out_cap_rows, result);
+    AccountScan s = account_scan_of_rows("get_account_balance_extremes", n, t_end);
+    s.row_bytes = EXTREME_ROW_BYTES;
+    s.bins = [](QueryState& q) { return ScanBins{q.qe.d_zone0, nullptr}; };
+    s.bin_bytes = EXTREME_ZONE0_BYTES(n), s.flag_word = (u64)n * 3 + EXTREME_FLAG_ORPHAN;
+    u32 slabs = 0;  // what the scan's launch cut the walk into, for the emit; none without a record
+    s.launch_scan = [&, n, mword](const ScanLaunch& L) -> int {
+        ExtremeBufs& X = L.E->qs->qe;
+        const u64 tiles = (L.records + CHANGE_THREADS - 1) / CHANGE_THREADS;
+        const u32 slab_tiles = extreme_slabs(tiles, n, X.elem_bytes, X.slabs_cap, &slabs);
+        HIPCK(hipMemsetAsync(X.d_elems, 0, (u64)slabs * n * EXTREME_ELEM_BYTES, L.E->stream));
+        const size_t lds = (size_t)L.slots * 4 + (size_t)EXTREME_LDS_BINS * (EXTREME_BIN_WORDS * 8 + 4) + 2 * EXTREME_WAVES * 4;
+        hipLaunchKernelGGL(tb_extreme_effects, dim3(slabs), dim3(CHANGE_THREADS), lds, L.E->stream, L.NT, L.self, L.records, t_open, t_end,
+                           mword, (const u32*)L.B.d_set, L.mask, (const u64*)L.B.d_ids, n, slab_tiles, X.d_elems, L.d_bins);
+        return TBGPU_STATUS_OK;
+    };
+    s.launch_emit = [&, n, mword](const ScanLaunch& L) -> int {
+        ExtremeBufs& X = L.E->qs->qe;
+        hipLaunchKernelGGL(tb_extreme_emit, dim3((n + QUERY_THREADS - 1) / QUERY_THREADS), dim3(QUERY_THREADS), 0, L.E->stream,
+                           (const u64*)L.B.d_ids, n, (const u8*)L.B.d_accounts, (const u32*)L.B.d_found, (const u32*)L.B.d_set, L.mask,
+                           (const u64*)X.d_elems, slabs, L.d_bins, t_open, t_end, mword, L.cap, L.B.d_out, L.B.d_res);
+        HIPCK(hipGetLastError());
+        HIPCK(hipMemcpyAsync(X.h_flags, L.d_bins + (u64)n * 3, EXTREME_FLAG_WORDS * 8, hipMemcpyDeviceToHost, L.E->stream));
+        return TBGPU_STATUS_OK;
+    };
+    const int st = account_scan_run_node(c, s, NT, out_cap_rows, out, result, [] {});
+    if (st == TBGPU_STATUS_OK && E->qs->qe.h_flags[EXTREME_FLAG_UNORDERED]) {
+        return extremes_exact(E, t_open, t_end, mword, ids, n, out, out_cap_rows, result);
+    }
+    return st;
 }
 
 // get_account_statement_series (k_series.h): T = the last bound, B + 1 buckets for the statements

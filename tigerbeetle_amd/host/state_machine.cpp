@@ -342,6 +342,14 @@ tbgpu_query_result StateMachine::get_account_balance_integrals(uint64_t t_open, 
     return r;
 }
 
+tbgpu_query_result StateMachine::get_account_balance_extremes(uint64_t t_open, uint64_t t_close, const tbgpu_balance_measure& measure,
+                                                              const void* ids, uint32_t n, void* out, uint32_t out_cap_rows) {
+    tbgpu_query_result r{};
+    check(tbgpu_get_account_balance_extremes(engine_, t_open, t_close, &measure, ids, n, out, out_cap_rows, &r),
+          "get_account_balance_extremes");
+    return r;
+}
+
 tbgpu_query_result StateMachine::get_account_statement_series(const uint64_t* bounds, uint32_t n_buckets, const void* ids, uint32_t n,
                                                               void* out, uint32_t out_cap_rows) {
     tbgpu_query_result r{};

@@ -301,6 +301,17 @@ public:
     tbgpu_query_result get_account_balance_integrals(uint64_t t_open, uint64_t t_close, const void* ids, uint32_t n, void* out,
                                                      uint32_t out_cap_rows);
 
+    // A balance's low and high over the period [t_open, t_end] (tbgpu_get_account_balance_extremes; a
+    // read, and no reference operation behind it): one 192-byte tbgpu_account_balance_extreme per id
+    // the table holds and that existed at t_end, in request order — the measure (a coefficient of -1, 0
+    // or +1 per balance column; the TBGPU_MEASURE_* macros) at the period's start and end, its minimum
+    // and maximum as signed 192-bit values, when each was first reached and the period's records.
+    // ids: n x {lo, hi}, at most TBGPU_EXTREMES_MAX.  t_open 0 is read literally; t_close 0: t_end is
+    // commit_timestamp.  One ordered walk of the log on a single engine; a node engine and a log loaded
+    // out of timestamp order are answered exactly, by a scan or two per account per page of its history.
+    tbgpu_query_result get_account_balance_extremes(uint64_t t_open, uint64_t t_close, const tbgpu_balance_measure& measure,
+                                                    const void* ids, uint32_t n, void* out, uint32_t out_cap_rows);
+
     // get_account_statements cut into consecutive periods (tbgpu_get_account_statement_series; a read,
     // and no reference operation behind it): bucket k is (bounds[k], bounds[k + 1]], and every account
     // the table holds and that existed at the last bound yields n_buckets tbgpu_account_statement

@@ -317,6 +317,9 @@ std::string run_table(tb::StateMachine& sm, const std::string& text) {
 // t_close and n ids}, answered by get_account_statements (the records are tbgpu_account_statement rows).
 // --query-integrals (tests/test_gpu_integrals_cpp.py): the same request, answered by
 // get_account_balance_integrals (the records are tbgpu_account_balance_integral rows).
+// --query-extremes (tests/test_gpu_extremes_cpp.py): the prepares ending in {0, 0, 24 + n * 16, t_open, t_close,
+// the 8 bytes of a tbgpu_balance_measure and n ids}, answered by get_account_balance_extremes (the records are
+// tbgpu_account_balance_extreme rows).
 // --query-series (tests/test_gpu_series_cpp.py): the prepares ending in {0, 0, the body's length, u32 n_buckets,
 // u32 n_ids, n_buckets + 1 bounds and n_ids ids}, answered by get_account_statement_series (the records are
 // tbgpu_account_statement rows).
@@ -329,7 +332,7 @@ std::string run_table(tb::StateMachine& sm, const std::string& text) {
 // answered by get_active_accounts (the records are tbgpu_account_activity rows).
 enum QueryKind { ACCOUNT_TRANSFERS, ACCOUNT_BALANCES, QUERY_TRANSFERS, QUERY_ACCOUNTS, CHANGE_EVENTS, ACCOUNT_TRANSFERS_MANY, ACCOUNTS_AT,
                  LEDGER_BALANCES, PENDING_TRANSFERS, ACCOUNT_STATEMENTS, ACCOUNT_INTEGRALS, ACCOUNT_SERIES, ACCOUNT_FLOW_MATRIX,
-                 ACCOUNT_COUNTERPARTIES, ACTIVE_ACCOUNTS };
+                 ACCOUNT_COUNTERPARTIES, ACTIVE_ACCOUNTS, ACCOUNT_EXTREMES };
 
 int run_query(tb::StateMachine& sm, QueryKind kind, const char* in_path, const char* out_path) {
     std::ifstream in(in_path, std::ios::binary);
@@ -437,6 +440,24 @@ int run_query(tb::StateMachine& sm, QueryKind kind, const char* in_path, const c
             sm.get_account_balance_integrals(period[0], period[1], body.data() + 16, (uint32_t)n, out.data(), TBGPU_INTEGRALS_MAX);
         std::ofstream o(out_path, std::ios::binary);
         o.write((const char*)&r, sizeof(r)).write((const char*)out.data(), (size_t)r.count * sizeof(tbgpu_account_balance_integral));
+        printf("query: %u of %llu rows, complete %u\n", r.count, (unsigned long long)r.matched, r.complete);
+        return o ? 0 : 2;
+    }
+    if (kind == ACCOUNT_EXTREMES) {
+        const size_t n = body.size() >= 24 ? (body.size() - 24) / 16 : 0;
+        if (body.size() % 16 != 8 || body.size() < 24 || n > TBGPU_EXTREMES_MAX) {
+            fprintf(stderr, "%s: t_open, t_close, a measure of 8 bytes and at most %u ids of 16 bytes\n", in_path, TBGPU_EXTREMES_MAX);
+            return 2;
+        }
+        uint64_t period[2] = {0, 0};
+        tbgpu_balance_measure measure;
+        memcpy(period, body.data(), 16);
+        memcpy(&measure, body.data() + 16, 8);
+        std::vector<uint8_t> out((size_t)TBGPU_EXTREMES_MAX * sizeof(tbgpu_account_balance_extreme));
+        const tbgpu_query_result r =
+            sm.get_account_balance_extremes(period[0], period[1], measure, body.data() + 24, (uint32_t)n, out.data(), TBGPU_EXTREMES_MAX);
+        std::ofstream o(out_path, std::ios::binary);
+        o.write((const char*)&r, sizeof(r)).write((const char*)out.data(), (size_t)r.count * sizeof(tbgpu_account_balance_extreme));
         printf("query: %u of %llu rows, complete %u\n", r.count, (unsigned long long)r.matched, r.complete);
         return o ? 0 : 2;
     }
@@ -554,12 +575,13 @@ int main(int argc, char** argv) {
     const bool pending = argc > 1 && std::string(argv[1]) == "--query-pending";
     const bool statements = argc > 1 && std::string(argv[1]) == "--query-statements";
     const bool integrals = argc > 1 && std::string(argv[1]) == "--query-integrals";
+    const bool extremes = argc > 1 && std::string(argv[1]) == "--query-extremes";
     const bool series = argc > 1 && std::string(argv[1]) == "--query-series";
     const bool matrix = argc > 1 && std::string(argv[1]) == "--query-flow-matrix";
     const bool counterparties = argc > 1 && std::string(argv[1]) == "--query-counterparties";
     const bool active = argc > 1 && std::string(argv[1]) == "--query-active";
-    const bool query = active || counterparties || matrix || fields || balances || changes || many || at || ledgers || pending || statements || integrals || series || (argc > 1 && std::string(argv[1]) == "--query");
-    QueryKind kind = active ? ACTIVE_ACCOUNTS : counterparties ? ACCOUNT_COUNTERPARTIES : matrix ? ACCOUNT_FLOW_MATRIX : series ? ACCOUNT_SERIES : balances ? ACCOUNT_BALANCES : changes ? CHANGE_EVENTS : many ? ACCOUNT_TRANSFERS_MANY : at ? ACCOUNTS_AT : ledgers ? LEDGER_BALANCES : pending ? PENDING_TRANSFERS : statements ? ACCOUNT_STATEMENTS : integrals ? ACCOUNT_INTEGRALS : ACCOUNT_TRANSFERS;
+    const bool query = active || counterparties || matrix || fields || balances || changes || many || at || ledgers || pending || statements || integrals || extremes || series || (argc > 1 && std::string(argv[1]) == "--query");
+    QueryKind kind = extremes ? ACCOUNT_EXTREMES : active ? ACTIVE_ACCOUNTS : counterparties ? ACCOUNT_COUNTERPARTIES : matrix ? ACCOUNT_FLOW_MATRIX : series ? ACCOUNT_SERIES : balances ? ACCOUNT_BALANCES : changes ? CHANGE_EVENTS : many ? ACCOUNT_TRANSFERS_MANY : at ? ACCOUNTS_AT : ledgers ? LEDGER_BALANCES : pending ? PENDING_TRANSFERS : statements ? ACCOUNT_STATEMENTS : integrals ? ACCOUNT_INTEGRALS : ACCOUNT_TRANSFERS;
     const char* self = argv[0];
     if (fields && argc > 2) {
         const std::string which = argv[2];
@@ -578,12 +600,13 @@ int main(int argc, char** argv) {
                 "       %s --query-pending <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-statements <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-integrals <prepares.bin> <answer.bin> [device]\n"
+                "       %s --query-extremes <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-series <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-flow-matrix <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-counterparties <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-active <prepares.bin> <answer.bin> [device]\n"
                 "       %s --query-fields <transfers|accounts> <prepares.bin> <answer.bin> [device]\n",
-                self, self, self, self, self, self, self, self, self, self, self, self, self, self, self);
+                self, self, self, self, self, self, self, self, self, self, self, self, self, self, self, self);
         return 2;
     }
     if (query) {

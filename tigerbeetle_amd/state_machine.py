@@ -23,7 +23,7 @@ import numpy as np
 
 from . import _lib
 from .types import (ACCOUNT_BALANCE_DTYPE, ACCOUNT_DTYPE, ACCOUNT_FILTER_DTYPE, BATCH_MAX, CHANGE_EVENT_DTYPE, CHANGE_EVENTS_FILTER_DTYPE,
-                    CHANGE_EVENTS_MAX, LEDGER_BALANCE_DTYPE, LEDGERS_MAX, PENDING_FILTER_DTYPE, PENDING_ROW_DTYPE, PENDING_ROWS_MAX, PENDING_STATES, STATEMENT_DTYPE, INTEGRAL_DTYPE, FLOW_CELL_DTYPE, COUNTERPARTY_DTYPE, COUNTERPARTIES_BY_VOLUME, COUNTERPARTIES_ROWS_MAX, pack_counterparty_filter, ACCOUNT_ACTIVITY_DTYPE, ACTIVE_BY_TRANSFERS, ACTIVE_BY_VOLUME, ACTIVE_ROWS_MAX, pack_activity_filter, FILTER_CREDITS, FILTER_DEBITS, FILTER_REVERSED, pack_change_events_filter, QUERY_FILTER_DTYPE, QUERY_REVERSED, TRANSFER_DTYPE, U64_MAX, Operation)
+                    CHANGE_EVENTS_MAX, LEDGER_BALANCE_DTYPE, LEDGERS_MAX, PENDING_FILTER_DTYPE, PENDING_ROW_DTYPE, PENDING_ROWS_MAX, PENDING_STATES, STATEMENT_DTYPE, INTEGRAL_DTYPE, EXTREME_DTYPE, pack_balance_measure, FLOW_CELL_DTYPE, COUNTERPARTY_DTYPE, COUNTERPARTIES_BY_VOLUME, COUNTERPARTIES_ROWS_MAX, pack_counterparty_filter, ACCOUNT_ACTIVITY_DTYPE, ACTIVE_BY_TRANSFERS, ACTIVE_BY_VOLUME, ACTIVE_ROWS_MAX, pack_activity_filter, FILTER_CREDITS, FILTER_DEBITS, FILTER_REVERSED, pack_change_events_filter, QUERY_FILTER_DTYPE, QUERY_REVERSED, TRANSFER_DTYPE, U64_MAX, Operation)
 
 
 def average_balances(row):
@@ -555,6 +555,50 @@ class Engine:
         src = ctypes.create_string_buffer(id_bytes, len(id_bytes))
         _lib.check(self.lib.tbgpu_get_account_balance_integrals(self.h, int(t_open), int(t_close), src, n, out.ctypes.data, cap,
                                                                 ctypes.byref(res)))
+        return out[:res.count], int(res.matched), bool(res.complete)
+
+    EXTREMES_MAX = 4095  # TBGPU_EXTREMES_MAX
+
+    def get_account_balance_extremes(self, ids, t_open, t_close, measure, out_cap_rows=None):
+        """The lowest and the highest value a balance of the accounts `ids` reached over the period
+        [t_open, t_end], and when (tbgpu_get_account_balance_extremes).  `measure`: the coefficients of
+        (debits_pending, debits_posted, credits_pending, credits_posted), each -1, 0 or +1 — the
+        types.MEASURE_* tuples name the usual ones.  One EXTREME_DTYPE row per id the table holds and
+        that existed at t_end, in request order, a repeated id once per occurrence: the measure at both
+        ends, its low and high as signed 192-bit values (types.extreme_value reads one), the timestamps
+        where each was first reached (t_open: the opening itself) and the period's records.  t_open 0
+        is read literally; t_close 0: t_end is commit_timestamp.  Returns (rows, matched, complete).
+        An invalid period matches nothing; an invalid measure raises.  One ordered walk of the log on a
+        single engine; a node engine, and a log loaded out of timestamp order, are answered exactly
+        but by a scan or two per account per page of its history."""
+        ids = [int(i) for i in ids]
+        if len(ids) > self.EXTREMES_MAX:
+            raise ValueError("at most %d ids in one call" % self.EXTREMES_MAX)
+        body = b"".join(i.to_bytes(16, "little") for i in ids)
+        return self.get_account_balance_extremes_raw(body, t_open, t_close, pack_balance_measure(measure), out_cap_rows)
+
+    def get_account_balance_extremes_raw(self, id_bytes, t_open, t_close, measure_bytes, out_cap_rows=None):
+        """get_account_balance_extremes from the ids' bytes, 16 each ({lo, hi}, little-endian), and the
+        measure's 8 bytes as they are (the library validates them)."""
+        id_bytes, measure_bytes = bytes(id_bytes), bytes(measure_bytes)
+        if len(id_bytes) % 16 != 0:
+            raise ValueError("an id is 16 bytes")
+        if len(measure_bytes) != 8:
+            raise ValueError("a measure is 8 bytes")
+        n = len(id_bytes) // 16
+        if n > self.EXTREMES_MAX:
+            raise ValueError("at most %d ids in one call" % self.EXTREMES_MAX)
+        if n == 0:  # the library returns at once and leaves its result alone
+            return np.zeros(0, dtype=EXTREME_DTYPE), 0, True
+        cap = n if out_cap_rows is None else int(out_cap_rows)
+        if cap < 0 or cap >> 32:
+            raise ValueError("out_cap_rows is 32 bits")
+        out = np.zeros(max(cap, 1), dtype=EXTREME_DTYPE)
+        res = _lib.tbgpu_query_result()
+        src = ctypes.create_string_buffer(id_bytes, len(id_bytes))
+        m = ctypes.create_string_buffer(measure_bytes, 8)
+        _lib.check(self.lib.tbgpu_get_account_balance_extremes(self.h, int(t_open), int(t_close), m, src, n, out.ctypes.data, cap,
+                                                               ctypes.byref(res)))
         return out[:res.count], int(res.matched), bool(res.complete)
 
     SERIES_ROWS_MAX = 4095  # TBGPU_SERIES_ROWS_MAX
@@ -1126,6 +1170,10 @@ class StateMachine:
     def get_account_balance_integrals(self, ids, t_open, t_close, out_cap_rows=None):
         """Time-weighted balances over a period (Engine.get_account_balance_integrals): a read, not a commit."""
         return self.engine.get_account_balance_integrals(ids, t_open, t_close, out_cap_rows)
+
+    def get_account_balance_extremes(self, ids, t_open, t_close, measure, out_cap_rows=None):
+        """A balance's low and high over a period (Engine.get_account_balance_extremes): a read, not a commit."""
+        return self.engine.get_account_balance_extremes(ids, t_open, t_close, measure, out_cap_rows)
 
     def get_account_statement_series(self, ids, bounds, cap=None):
         """Statement headers per bucket (Engine.get_account_statement_series): a read, not a commit."""

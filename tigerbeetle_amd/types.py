@@ -155,6 +155,45 @@ INTEGRAL_DTYPE = np.dtype(
 assert INTEGRAL_DTYPE.itemsize == 256
 INTEGRALS_MAX = 4095
 
+# tbgpu_account_balance_extreme (include/tbgpu.h tbgpu_get_account_balance_extremes): 192 bytes, no
+# padding; the measure at the period's start and end, its minimum and maximum over the period (signed,
+# two's complement, 192 bits, low word first), when each was first reached, the period's records, the
+# period as used and the request's measure.
+EXTREME_DTYPE = np.dtype(
+    _u128("id")
+    + [(v + w, "<u8") for v in ("opening", "closing", "low", "high") for w in ("_w0", "_w1", "_w2")]
+    + [("t_low", "<u8"), ("t_high", "<u8"), ("records", "<u8"), ("t_open", "<u8"), ("t_end", "<u8"), ("measure", "<u8"),
+       ("reserved", "<u8", (4,))])
+assert EXTREME_DTYPE.itemsize == 192
+EXTREMES_MAX = 4095
+# The usual measures (TBGPU_MEASURE_*): the coefficients of (debits_pending, debits_posted,
+# credits_pending, credits_posted), each -1, 0 or +1.
+MEASURE_CREDIT_NET_POSTED = (0, -1, 0, 1)
+MEASURE_CREDIT_AVAILABLE = (-1, -1, 0, 1)
+MEASURE_DEBIT_NET_POSTED = (0, 1, 0, -1)
+MEASURE_DEBIT_AVAILABLE = (0, 1, -1, -1)
+MEASURE_DEBITS_PENDING = (1, 0, 0, 0)
+MEASURE_DEBITS_POSTED = (0, 1, 0, 0)
+MEASURE_CREDITS_PENDING = (0, 0, 1, 0)
+MEASURE_CREDITS_POSTED = (0, 0, 0, 1)
+
+
+def pack_balance_measure(measure, reserved=b"\0\0\0\0"):
+    """The 8 bytes of a tbgpu_balance_measure from four coefficients (each must fit a signed byte; the
+    library checks the rest)."""
+    coefficients = [int(c) for c in measure]
+    reserved = bytes(reserved)
+    if len(coefficients) != 4 or len(reserved) != 4 or not all(-128 <= c <= 127 for c in coefficients):
+        raise ValueError("a measure is four coefficients, each a signed byte, and four reserved bytes")
+    return bytes(c & 0xFF for c in coefficients) + reserved
+
+
+def extreme_value(row, name):
+    """Field `name` ("opening", "closing", "low" or "high") of an EXTREME_DTYPE row as a Python int."""
+    v = sum(int(row["%s_w%d" % (name, k)]) << (64 * k) for k in range(3))
+    return v - (1 << 192) if v >> 191 else v
+
+
 # tbgpu_get_account_statement_series: STATEMENT_DTYPE rows, ids x buckets of them at most.
 SERIES_ROWS_MAX = 4095
 

@@ -1,7 +1,7 @@
 """The account-filter scan (tbgpu_get_account_transfers, csrc/k_query.h) over a 16M-transfer log (2 GB)
 against a device-to-device copy of the same log range, in one process.
 
-usage: python tools/gpu/query_scan.py [transfers] [runs] [--only account|fields|balances|change_events|many|asof|ledgers|pending|statements|integrals|series|matrix]
+usage: python tools/gpu/query_scan.py [transfers] [runs] [--only account|fields|balances|change_events|many|asof|ledgers|pending|statements|integrals|extremes|series|matrix]
 
 The log is built by the device generator, committed in place (the way tools/gpu/device_pass.py builds
 a pass): once with uniform C2 ids, where the queried account is a cold one (a few dozen matches), and
@@ -71,6 +71,11 @@ tbgpu_get_account_statements call with the same ids and period.  An older librar
 TBGPU_AB_LIB lacks the call: its get_account_statements alone is timed then, the yardstick to hold this
 build's call against.
 
+`--only extremes` (tbgpu_get_account_balance_extremes) times the C call alone, into buffers made
+once, on both logs: n = 1 (a cold and the hottest account), 64 and 4,095 ids, the whole log and its middle half,
+each beside tbgpu_get_account_statements for the same ids and period, the order-free yardstick; then engines made
+under TBGPU_EXTREMES_SLABS (256, 64, 16, 1) for n = 4,095 and under TBGPU_EXTREMES_EXACT=1 for n = 1 hottest and
+n = 64 (three runs each; --skip-exact leaves them out).
 `--only series` (tbgpu_get_account_statement_series) times the C call alone, into buffers made
 once, on both logs, at (ids, buckets) = (4095, 1), (136, 30), (11, 365) and (1, 4095) with equal buckets over
 the whole log and --only statements' ids.  The yardsticks run in the same process: the same question asked as
@@ -601,6 +606,109 @@ def measure_integrals():
                 entry = row(med, lo_ms, hi_ms, over_statements=round(med / st_med, 2), **entry)
             out["%s_integrals_%s" % (name, leg)] = entry
     e.close()
+    return out
+
+
+def measure_extremes():
+    """get_account_balance_extremes beside get_account_statements — the order-free yardstick for what ordering
+    costs — with the same ids and period, on both logs, in one process; then engines made under the call's knobs:
+    the walk cut into at most 256, 64, 16 and 1 slabs (n = 4,095, the whole log), and the exact path, what a caller
+    has today (n = 1 hottest and n = 64, three runs each: it pages the account's history)."""
+    import ctypes
+
+    from tigerbeetle_amd import _lib
+    from tigerbeetle_amd.types import MEASURE_CREDIT_NET_POSTED, pack_balance_measure
+    os.environ["TBGPU_QUERY_COOP"] = "0"
+    n_ids = 4095
+    h_out = np.zeros(n_ids * 256, dtype=np.uint8)
+    h_res = _lib.tbgpu_query_result()
+    measure = ctypes.create_string_buffer(pack_balance_measure(MEASURE_CREDIT_NET_POSTED), 8)
+    out = {}
+
+    def engine_of(exact, slabs):
+        os.environ["TBGPU_EXTREMES_EXACT"] = "1" if exact else "0"
+        os.environ.pop("TBGPU_EXTREMES_SLABS", None)
+        if slabs:
+            os.environ["TBGPU_EXTREMES_SLABS"] = str(slabs)
+        e = Engine(Options(accounts_max=n_acct, transfers_max=n_xfer, pass_events_max=pb * batch, pass_batches_max=pb))
+        a_lens = batches(n_acct, batch)
+        a_ts, t = timestamps(a_lens, 1_000_000_000)
+        acct = e.alloc(n_acct * 128)
+        e.generate_accounts(acct, 0, n_acct, seed=42)
+        res = e.alloc(max(n_acct, n_xfer) * 8)
+        rb = e.alloc((n_xfer // batch + 2) * 4)
+        e.commit_device_async(128, a_ts, a_lens, acct, res, rb)
+        e.sync()
+        return e, res, rb, t
+
+    def fill(e, res, rb, t, name, kind):
+        if name != "uniform":
+            e.reset_transfers()
+        log = e.log_window(n_xfer)
+        e.generate_transfers(log, 0, n_xfer, n_acct, seed=42, kind=KINDS[kind])
+        e.sync()
+        x_lens = batches(n_xfer, batch)
+        x_ts, t = timestamps(x_lens, t + 10)
+        e.commit_device_async(129, x_ts, x_lens, log, res, rb)
+        e.sync()
+        oldest, _, _ = e.query_transfers(limit=1)
+        newest, _, _ = e.query_transfers(reversed=True, limit=1)
+        t_first, t_last = int(oldest["timestamp"][0]), int(newest["timestamp"][0])
+        sample = e.to_host(log + (n_xfer // 2) * 128, min(n_xfer // 2, 1 << 16) * 128).view(TRANSFER_DTYPE)
+        accounts, counts = np.unique(sample[["debit_account_id_lo", "debit_account_id_hi"]], return_counts=True)
+        order = np.argsort(-counts, kind="stable")
+        ids = [int(lo) | (int(hi) << 64) for lo, hi in accounts[order[:n_ids]].tolist()]
+        cold = [int(lo) | (int(hi) << 64) for lo, hi in accounts[order[-1:]].tolist()]
+        assert len(ids) == n_ids
+        return t, t_first, t_last, ids, cold
+
+    def raw(e, fn, ids, t_open, t_close, with_measure):
+        body = b"".join(i.to_bytes(16, "little") for i in ids)
+        src = ctypes.create_string_buffer(body, len(body))
+        if with_measure:
+            return lambda: _lib.check(fn(e.h, t_open, t_close, measure, src, len(ids), h_out.ctypes.data, len(ids), ctypes.byref(h_res)))
+        return lambda: _lib.check(fn(e.h, t_open, t_close, src, len(ids), h_out.ctypes.data, len(ids), ctypes.byref(h_res)))
+
+    def few(e, fn, n=3):
+        took = []
+        for i in range(1 + n):
+            e.marker(0)
+            fn()
+            e.marker(1)
+            e.sync()
+            if i:
+                took.append(e.marker_elapsed_ms(0, 1))
+        return statistics.median(took), min(took), max(took)
+
+    e, res, rb, t = engine_of(False, 0)
+    for name, kind in (("uniform", "c2"), ("zipf", "c3")):
+        t, t_first, t_last, ids, cold = fill(e, res, rb, t, name, kind)
+        quarter = (t_last - t_first) // 4
+        rows, matched, complete = e.get_account_balance_extremes(ids, t_first + quarter, t_last - quarter, MEASURE_CREDIT_NET_POSTED)
+        assert complete and matched == n_ids and int(rows["records"].sum()) > n_ids // 2
+        for who, request in (("1_cold", cold), ("1_hottest", ids[:1]), ("64", ids[:64]), ("4095", ids)):
+            for leg, t_open, t_close in (("whole_log", t_first - 1, t_last), ("middle_half", t_first + quarter, t_last - quarter)):
+                st_med, st_lo, st_hi = timed(e, raw(e, e.lib.tbgpu_get_account_statements, request, t_open, t_close, False))
+                med, lo_ms, hi_ms = timed(e, raw(e, e.lib.tbgpu_get_account_balance_extremes, request, t_open, t_close, True))
+                out["%s_extremes_%s_%s" % (name, who, leg)] = row(med, lo_ms, hi_ms, ids=len(request), statements_ms=round(st_med, 4),
+                                                                   statements_min_ms=round(st_lo, 4), statements_max_ms=round(st_hi, 4),
+                                                                   over_statements=round(med / st_med, 2))
+    e.close()
+    for slabs in (256, 64, 16, 1):
+        e, res, rb, t = engine_of(False, slabs)
+        for name, kind in (("uniform", "c2"), ("zipf", "c3")):
+            t, t_first, t_last, ids, cold = fill(e, res, rb, t, name, kind)
+            med, lo_ms, hi_ms = (few if slabs == 1 else timed)(e, raw(e, e.lib.tbgpu_get_account_balance_extremes, ids, t_first - 1, t_last, True))
+            out["%s_extremes_4095_whole_log_slabs_%d" % (name, slabs)] = row(med, lo_ms, hi_ms, ids=n_ids, slabs_cap=slabs)
+        e.close()
+    if "--skip-exact" not in sys.argv:
+        e, res, rb, t = engine_of(True, 0)
+        for name, kind in (("uniform", "c2"), ("zipf", "c3")):
+            t, t_first, t_last, ids, cold = fill(e, res, rb, t, name, kind)
+            for who, request in (("1_hottest", ids[:1]), ("64", ids[:64])):
+                med, lo_ms, hi_ms = few(e, raw(e, e.lib.tbgpu_get_account_balance_extremes, request, t_first - 1, t_last, True))
+                out["%s_extremes_%s_whole_log_exact_path" % (name, who)] = row(med, lo_ms, hi_ms, ids=len(request), runs=3)
+        e.close()
     return out
 
 
@@ -1204,6 +1312,8 @@ elif only == "statements":
     result["statements"] = measure_statements()
 elif only == "integrals":
     result["integrals"] = measure_integrals()
+elif only == "extremes":
+    result["extremes"] = measure_extremes()
 elif only == "series":
     result["series"] = measure_series()
 elif only == "matrix":
@@ -1223,6 +1333,6 @@ elif only != "fields":
     for shape in ("lane_per_record", "cooperative"):
         r = result[shape]
         r["bar_query_le_copy"] = all(v["ms"] <= r["copy_d2d"]["ms"] for k, v in r.items() if k != "copy_d2d")
-if only not in ("account", "balances", "change_events", "many", "asof", "ledgers", "pending", "statements", "integrals", "series", "matrix", "counterparties", "activity"):
+if only not in ("account", "balances", "change_events", "many", "asof", "ledgers", "pending", "statements", "integrals", "extremes", "series", "matrix", "counterparties", "activity"):
     result["field_filters"] = measure_fields()
 print(json.dumps(result))

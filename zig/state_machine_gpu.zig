@@ -826,6 +826,44 @@ pub fn StateMachineType(
             return @as(usize, result.count) * @sizeOf(tbgpu.tbgpu_account_balance_integral);
         }
 
+        /// The lowest and the highest value a balance of the accounts `ids` reached over the period
+        /// [t_open, t_end], and when (tbgpu_get_account_balance_extremes; t_close 0: t_end is
+        /// commit_timestamp): a read, with no operation in this reference's enum, so nothing in
+        /// commit() dispatches to it (INTEGRATION.md, "A balance's low and high over a period").
+        /// `measure` has a coefficient of -1, 0 or +1 per balance column. One 192-byte
+        /// tbgpu_account_balance_extreme per id the engine holds and that existed at t_end, in
+        /// request order, into `output`; returns the bytes written. `complete` is false once
+        /// transfers were evicted or a post in the period had lost its pending transfer: the caller
+        /// then merges with the forest.
+        pub fn get_account_balance_extremes(
+            self: *StateMachine,
+            t_open: u64,
+            t_close: u64,
+            measure: tbgpu.tbgpu_balance_measure,
+            ids: []const u128,
+            output: []align(16) u8,
+            complete: *bool,
+        ) usize {
+            assert(ids.len <= tbgpu.TBGPU_EXTREMES_MAX);
+            var result: tbgpu.tbgpu_query_result = undefined;
+            result.count = 0;
+            result.complete = 1;
+            result.matched = 0;
+            check(tbgpu.tbgpu_get_account_balance_extremes(
+                self.engine,
+                t_open,
+                t_close,
+                &measure,
+                ids.ptr,
+                @intCast(ids.len),
+                output.ptr,
+                @intCast(output.len / @sizeOf(tbgpu.tbgpu_account_balance_extreme)),
+                &result,
+            ));
+            complete.* = result.complete != 0;
+            return @as(usize, result.count) * @sizeOf(tbgpu.tbgpu_account_balance_extreme);
+        }
+
         /// Statement headers for the accounts `ids` per bucket (bounds[k], bounds[k + 1]]
         /// (tbgpu_get_account_statement_series; a first bound of 0: from before every record, a last
         /// bound of 0: up to now): a read, with no operation in this reference's enum, so nothing in
